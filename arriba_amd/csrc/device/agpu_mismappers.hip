@@ -19,6 +19,7 @@
 #include "agpu_context.hpp"
 #include "mismapper_core.hpp"
 #include "device_utils.hpp"
+#include "mismapper_heavy.hpp"
 
 using namespace agpu;
 
@@ -175,75 +176,14 @@ __global__ void __launch_bounds__(ALIGN_BLOCK, 5) mismapper_verdict_kernel(Batch
 	block_tally(mine, &counters[1], &block_sum);
 }
 
-// Second pass, one wavefront per heavy read: the read positions one after the other, the seeds of a position split among the 64 lanes (every seed of the outermost
-// loop of align() is an independent attempt), full stack, no budget; the segment in LDS is shared by the lanes, and so is the memo of failed nested calls
-// (AlignMemo, mismapper_core.hpp: it turns the exponential re-evaluation of the reference's recursion into one search per distinct call).  The workgroups are
-// persistent: each owns one memo table in HBM and takes the next heavy read from a queue (counters[4]) when it is done with one -- the searches differ in
-// length by orders of magnitude, a fixed share per workgroup would wait for the unluckiest one.  The kernel waits for dependent loads (k-mer table -> hit list ->
-// genome bases -> memo slot), so the number of wavefronts in flight is what sets its speed: 5120 workgroups of one wavefront = 5 per SIMD.
+// Second pass, one wavefront per heavy read: mismapper_heavy_kernel (mismapper_heavy.hpp; its instantiations are compiled in files of their own, agpu_mismappers_heavy_*.hip)
 const uint32_t MEMO_SLOTS_LOG2 = 16;    // 512 KB per workgroup, 2.7 GB for 5120 of them.  2^20 (8 MB, 41 GB in all, cleared per sample) until round 6, sized for the reads of long genes that make 10^5..10^6
                                         // distinct nested calls -- but the time of the kernel is the same from 2^11 to 2^20 slots at 10^8 fragments (profiles/r06e_heavy_ab.txt: 363 / 369 / 368 ms):
                                         // a full table costs repeated searches, never correctness, and the 38 GB are the difference between a rank that holds its share of a sample beside
                                         // the tables and one that does not.  ARRIBA_MEMO_SLOTS_LOG2 for measurements
 const uint32_t TASK_CAPACITY_LOG2 = 15; // 2^15 listed calls of 16 bytes per workgroup, and as many for the calls of a block beyond the memory of the sweep: 5 GB for 5120 workgroups (2^17, 21 GB,
                                         // until round 6; the longest list of the 10^8-fragment sample has 1 600 calls).  A search that lists more is done by the recursion.  ARRIBA_TASK_CAPACITY_LOG2
-const uint32_t HEAVY_WORKGROUPS = 5120; // five wavefronts per SIMD (launch bounds below)
-// Tried and taken back in round 5 (profiles/r05o_waves6.json, r05p_*, r05q_*): (a) six wavefronts per SIMD -- 80 VGPRs, 177 spilled: 457 ms instead of 419 at 10^8 fragments;
-// (b) TWO searches per wavefront, the two strands of a gene at once on 32 lanes each with a sweep, a memo and lists of their own (the calls of a block kept in LDS cut from 256 to
-// 64 to make room): the same verdict bytes under every schedule of the GPU tier, but 496 ms -- the halves of a wavefront go separate ways through the walks and the look-ups of the
-// read positions take twice the turns; with 64 calls in LDS and one search per wavefront: 432 ms.
-// SWEEP_ONLY: the searches go through the sweep or are given up -- no recursion, no stack of frames in the kernel; the reads of the searches given up are appended to `leftover`
-// (counters[5]) and done by the instantiation that holds everything.  queue: the index of the queue's counter (the second launch has a queue of its own).
-template <int WAVES_PER_SIMD, bool SWEEP_ONLY> __global__ void __launch_bounds__(64, WAVES_PER_SIMD) mismapper_heavy_kernel(BatchView b, AnnotationView ann, GenomeView genome, KmerIndexView kmers, SpliceSiteView splice, const uint32_t* heavy, uint32_t n_heavy, int32_t max_mate_gap,
-                                                             unsigned long long* memo_tables, uint32_t memo_slots, unsigned long long* task_lists, uint32_t task_capacity, bool by_sweep, unsigned long long* read_times, unsigned int* counters, uint32_t* leftover, int queue, bool lds_front, bool strands_together) {
-	__shared__ uint8_t segment_bases[2 * 304]; // (the segment being searched and its reverse complement)
-	__shared__ uint8_t segment_chars[2 * 312];  // (... as characters, eight zero bytes behind each)
-	__shared__ AlignSweep sweep;
-	__shared__ AlignMemo memo;
-	__shared__ AlignWorklist worklist;
-	__shared__ uint32_t worklist_state[4];
-	__shared__ unsigned long long memo_front[ALIGN_MEMO_FRONT_SLOTS]; // (mismapper_core.hpp: the first keys of a search never leave the CU)
-	__shared__ unsigned long long list_head[2 * ALIGN_LIST_HEAD_TASKS];
-	__shared__ uint32_t memo_spilled;
-	__shared__ uint32_t next_job;
-	__shared__ uint32_t study[16];
-	if (threadIdx.x == 0) {
-		worklist.stats = read_times != nullptr ? study : nullptr;
-		memo.slots = memo_tables + (size_t) blockIdx.x * memo_slots; memo.mask = memo_slots - 1; memo.epoch = 0;
-		memo.front = lds_front ? memo_front : nullptr; memo.front_mask = lds_front ? ALIGN_MEMO_FRONT_SLOTS - 1 : 0; memo.spilled = lds_front ? &memo_spilled : nullptr; memo_spilled = 0;
-		worklist.head = lds_front ? list_head : nullptr; worklist.head_capacity = lds_front ? ALIGN_LIST_HEAD_TASKS : 0;
-		worklist.words = task_lists != nullptr ? task_lists + (size_t) blockIdx.x * task_capacity * 2 : nullptr; worklist.capacity = task_capacity; worklist.state = worklist_state;
-		worklist.sweep = by_sweep ? &sweep : nullptr; // one sweep over the read positions, every seed walked once (mismapper_core.hpp: AlignSweep)
-		worklist.relevant_words = task_lists != nullptr ? task_lists + ((size_t) gridDim.x + blockIdx.x) * task_capacity * 2 : nullptr; worklist.relevant_capacity = task_capacity; // (the second half of the buffer: the calls of a block beyond those kept in LDS)
-	}
-	for (uint32_t k = threadIdx.x; k < ALIGN_MEMO_FRONT_SLOTS; k += 64) memo_front[k] = 0; // (epoch 0 = free)
-	__syncthreads();
-	__shared__ int64_t given_up; // (SWEEP_ONLY: < 0 when a search of the read was not one for the sweep)
-	AlignFrame stack[SWEEP_ONLY ? 1 : ALIGN_MAX_DEPTH];
-	AlignRunnerT<SWEEP_ONLY> runner; runner.stack = stack; runner.lane = threadIdx.x; runner.lanes = 64; runner.budget = SWEEP_ONLY ? &given_up : nullptr; runner.max_depth = SWEEP_ONLY ? 1 : ALIGN_MAX_DEPTH;
-	runner.lanes_share_seeds = true; // a read lands here because its search is long: the lanes split the seeds of every read position (when the task list is off or overflows)
-	runner.memo = &memo;
-	runner.worklist = task_lists != nullptr ? &worklist : nullptr; // the search as rounds of up to 64 tasks (mismapper_core.hpp: AlignWorklist)
-	runner.cache = segment_bases; runner.cache_stride = 1; runner.cache_capacity = 304; runner.cache2 = segment_bases + 304; runner.strands_together = strands_together; runner.chars = segment_chars; runner.chars2 = segment_chars + 312;
-	while (true) {
-		__syncthreads(); // (every lane has read next_job of the previous round)
-		if (threadIdx.x == 0) { next_job = atomicAdd(&counters[queue], 1u); given_up = 0; }
-		__syncthreads();
-		if (next_job >= n_heavy) break;
-		const uint32_t read = heavy[next_job];
-		const unsigned long long started = read_times != nullptr ? wall_clock64() : 0ull;
-		if (read_times != nullptr && threadIdx.x == 0) for (int k = 0; k < 16; ++k) study[k] = 0;
-		const bool verdict = is_mismapper(b, ann, genome, kmers, splice, read, max_mate_gap, runner);
-		if (SWEEP_ONLY && runner.exhausted()) { if (threadIdx.x == 0) leftover[atomicAdd(&counters[5], 1u)] = read; continue; } // (the same for every lane: written behind a barrier)
-		if (verdict && threadIdx.x == 0) { b.filter[read] = FILTER_mismappers; atomicAdd(&counters[1], 1u); }
-		if (read_times != nullptr && threadIdx.x == 0) { // (ARRIBA_MISMAPPER_TIMES=1: ticks of the 100 MHz clock per read, and what the search of the read consisted of)
-			read_times[4 * (size_t) next_job] = wall_clock64() - started; read_times[4 * (size_t) next_job + 1] = (unsigned long long) study[0] << 32 | study[1]; read_times[4 * (size_t) next_job + 2] = (unsigned long long) study[2] << 32 | study[3];
-			read_times[4 * (size_t) next_job + 3] = (unsigned long long) read << 8 | b.n_aln[read];
-			atomicAdd(&read_times[4 * (size_t) n_heavy], (unsigned long long) study[4]); atomicAdd(&read_times[4 * (size_t) n_heavy + 1], (unsigned long long) study[5]); atomicAdd(&read_times[4 * (size_t) n_heavy + 2], (unsigned long long) study[6]);
-			for (int k = 8; k < 16; ++k) atomicAdd(&read_times[4 * (size_t) n_heavy + 4 + (k - 8)], (unsigned long long) study[k]);
-		}
-	}
-}
+const uint32_t HEAVY_WORKGROUPS = 5120; // five wavefronts per SIMD (the launch bounds of mismapper_heavy_kernel, mismapper_heavy.hpp)
 
 // filter_mismappers shared out over several GPUs that hold the same batch: the jobs of one part, the verdicts of a part for the exchange, the verdicts of all parts applied
 __global__ void mismapper_take_part_kernel(const uint32_t* jobs, uint32_t n_jobs, uint32_t part, uint32_t parts, uint32_t* mine) {
@@ -520,11 +460,11 @@ int filter_mismappers_phases(agpu_ctx* ctx, int phases, int32_t max_mate_gap, ui
 				if (sweep_kernel_first) {
 					{ KernelTimer timer(ctx, "mismapper_heavy_kernel", (uint64_t) n_heavy * 300);
 					  const int heavy_waves = getenv("ARRIBA_HEAVY_WAVES") != nullptr ? atoi(getenv("ARRIBA_HEAVY_WAVES")) : 5; // (6 with ARRIBA_HEAVY_WORKGROUPS=6144: 80 VGPRs, 177 spilled -- for measurements; launch bounds of 8 are not honoured: 122 VGPRs, four wavefronts)
-					  if (heavy_waves == 6) mismapper_heavy_kernel<6, true><<<workgroups, 64, 0, s>>>(ctx->batch, ctx->annotation, ctx->genome, kmers, splice, heavy.as<uint32_t>(), n_heavy, max_mate_gap, memo_tables.as<unsigned long long>(), memo_slots, task_lists.as<unsigned long long>(), task_capacity,
+					  if (heavy_waves == 6) launch_mismapper_heavy_6_sweep_only(workgroups, s, ctx->batch, ctx->annotation, ctx->genome, kmers, splice, heavy.as<uint32_t>(), n_heavy, max_mate_gap, memo_tables.as<unsigned long long>(), memo_slots, task_lists.as<unsigned long long>(), task_capacity,
 					                                                true, want_times ? read_times.as<unsigned long long>() : nullptr, device_counters, leftover.as<uint32_t>(), 4, lds_front, strands_together);
-					  else if (!four_waves) mismapper_heavy_kernel<5, true><<<workgroups, 64, 0, s>>>(ctx->batch, ctx->annotation, ctx->genome, kmers, splice, heavy.as<uint32_t>(), n_heavy, max_mate_gap, memo_tables.as<unsigned long long>(), memo_slots, task_lists.as<unsigned long long>(), task_capacity,
+					  else if (!four_waves) launch_mismapper_heavy_5_sweep_only(workgroups, s, ctx->batch, ctx->annotation, ctx->genome, kmers, splice, heavy.as<uint32_t>(), n_heavy, max_mate_gap, memo_tables.as<unsigned long long>(), memo_slots, task_lists.as<unsigned long long>(), task_capacity,
 					                                                true, want_times ? read_times.as<unsigned long long>() : nullptr, device_counters, leftover.as<uint32_t>(), 4, lds_front, strands_together);
-					  else mismapper_heavy_kernel<4, true><<<workgroups, 64, 0, s>>>(ctx->batch, ctx->annotation, ctx->genome, kmers, splice, heavy.as<uint32_t>(), n_heavy, max_mate_gap, memo_tables.as<unsigned long long>(), memo_slots, task_lists.as<unsigned long long>(), task_capacity,
+					  else launch_mismapper_heavy_4_sweep_only(workgroups, s, ctx->batch, ctx->annotation, ctx->genome, kmers, splice, heavy.as<uint32_t>(), n_heavy, max_mate_gap, memo_tables.as<unsigned long long>(), memo_slots, task_lists.as<unsigned long long>(), task_capacity,
 					                                                true, want_times ? read_times.as<unsigned long long>() : nullptr, device_counters, leftover.as<uint32_t>(), 4, lds_front, strands_together); }
 					HIP_CHECK(hipMemcpyAsync(&n_todo, device_counters + 5, 4, hipMemcpyDeviceToHost, s));
 					HIP_CHECK(hipStreamSynchronize(s));
@@ -535,9 +475,9 @@ int filter_mismappers_phases(agpu_ctx* ctx, int phases, int32_t max_mate_gap, ui
 					const uint32_t groups = std::min<uint32_t>(n_todo, workgroups);
 					if (sweep_kernel_first) HIP_CHECK(hipMemsetAsync(memo_tables.ptr, 0, (size_t) groups * memo_slots * 8, s)); // (the epochs of the memo start again: nothing of the first kernel's searches may match)
 					KernelTimer timer(ctx, sweep_kernel_first ? "mismapper_heavy_kernel(searches the sweep gave up)" : "mismapper_heavy_kernel", (uint64_t) n_todo * 300);
-					if (!four_waves) mismapper_heavy_kernel<5, false><<<groups, 64, 0, s>>>(ctx->batch, ctx->annotation, ctx->genome, kmers, splice, todo, n_todo, max_mate_gap, memo_tables.as<unsigned long long>(), memo_slots, use_worklist ? task_lists.as<unsigned long long>() : nullptr, task_capacity,
+					if (!four_waves) launch_mismapper_heavy_5_everything(groups, s, ctx->batch, ctx->annotation, ctx->genome, kmers, splice, todo, n_todo, max_mate_gap, memo_tables.as<unsigned long long>(), memo_slots, use_worklist ? task_lists.as<unsigned long long>() : nullptr, task_capacity,
 					                                                by_sweep, want_times && !sweep_kernel_first ? read_times.as<unsigned long long>() : nullptr, device_counters, nullptr, sweep_kernel_first ? 6 : 4, lds_front, strands_together);
-					else mismapper_heavy_kernel<4, false><<<groups, 64, 0, s>>>(ctx->batch, ctx->annotation, ctx->genome, kmers, splice, todo, n_todo, max_mate_gap, memo_tables.as<unsigned long long>(), memo_slots, use_worklist ? task_lists.as<unsigned long long>() : nullptr, task_capacity,
+					else launch_mismapper_heavy_4_everything(groups, s, ctx->batch, ctx->annotation, ctx->genome, kmers, splice, todo, n_todo, max_mate_gap, memo_tables.as<unsigned long long>(), memo_slots, use_worklist ? task_lists.as<unsigned long long>() : nullptr, task_capacity,
 					                                                by_sweep, want_times && !sweep_kernel_first ? read_times.as<unsigned long long>() : nullptr, device_counters, nullptr, sweep_kernel_first ? 6 : 4, lds_front, strands_together);
 				}
 				if (want_times) {

@@ -18,6 +18,10 @@ with one all-reduce of the verdicts, rank 0 writes the files (with the one-GPU s
 time ("scaling": "strong").  --per-rank-samples gives every rank a sample of its own instead (no collective on the data path; "weak").  Rank 0 prints ONE JSON line.
 
 The CPU baseline is the oracle build of the UNMODIFIED reference (oracle/_ref/arriba_ref, single-threaded by design) on a bounded sample of the same workload.
+A plain run does what the headline figure needs and no more: it sets up, warms up, times the steps and prints the line.  --full adds what else this script measures and checks,
+as before behind the timed steps: the post-conditions of the last step and the comparison of its fusions.tsv with the reference's file, one sample alone (latency_s, the kernels by
+themselves), the legs with deflated BGZF blocks, with ordinary proper pairs and of config 3, and the CPU baseline.  --dump-outputs DIR writes what the last timed step gave its
+caller as DIR/<name>.npy (dump_outputs below); the sample is generated from fixed seeds, so two builds run with the same arguments can be compared array by array.
 --host-only: no GPU needed -- generates a small sample, runs the file side of the device ingest (BamFeed) and the classic host ingest from a named pipe and
 from a file, prints their rates; run it in the CPU container before committing a change under arriba_amd/csrc/host/.
 """
@@ -111,6 +115,49 @@ def generate_sample(fragments, seed, directory, read_seed=0, stress=False, threa
         return prefix, 0.0  # (A/B measurements on one GPU lease: the sample of an earlier run with --keep)
     subprocess.run([datasets.GEN_SYNTH, "--out", prefix, "--threads", str(threads)] + workload_args(fragments, seed, read_seed, stress), check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
     return prefix, time.time() - started
+
+
+def host_holds_large_sample(samples=1):
+    """the host side of the choice of the default sample: (whether this box can hold `samples` samples of 10^8 fragments in memory -- 54 GB of BAM each, in a tmpfs or the
+    temporary directory --, its memory, the free bytes of its tmpfs).  Read before a generator begins to fill the tmpfs; the device's side (HBM) is main()'s."""
+    memory = os.sysconf("SC_PAGE_SIZE") * os.sysconf("SC_PHYS_PAGES")
+    shm_free = shutil.disk_usage("/dev/shm").free if os.path.isdir("/dev/shm") else 0
+    return memory > samples * (160 << 30) and max(shm_free, shutil.disk_usage(tempfile.gettempdir()).free) > samples * (80 << 30), memory, shm_free
+
+
+def start_sample_ahead(args):
+    """A plain run on one GPU starts the generator of its sample before anything else -- before torch is imported, the device context made and build() looked at: those take
+    ~2 s that the generator (20 s for 10^8 fragments) does not need.  Without --fragments the 100 M sample is begun if the HOST can hold it; if the device turns out too small
+    for it, main() ends this generator and makes the 10 M sample as before.  None where that is not possible (the generator not built yet or older than its sources: build()
+    comes first then) or not wanted (--full, --keep, several ranks, a sample given from outside)."""
+    import datasets
+    if args.full or args.keep or args.gpus != 1 or "WORLD_SIZE" in os.environ or any(os.environ.get(name) for name in ("ARRIBA_BENCH_SCRATCH", "ARRIBA_BENCH_REUSE", "ARRIBA_BENCH_CHILD")):
+        return None
+    sources = [os.path.join(ROOT, "tools", name) for name in ("gen_synth.cpp", "gen_synth.hpp")]
+    try:
+        if os.path.getmtime(datasets.GEN_SYNTH) < max(os.path.getmtime(path) for path in sources):
+            return None
+    except OSError:
+        return None
+    host = host_holds_large_sample()
+    fragments = args.fragments
+    if fragments is None:
+        if not host[0]:
+            return None
+        fragments = 100000000
+    directory = scratch_directory(fragments * 600)
+    prefix = os.path.join(directory, "bench")
+    process = subprocess.Popen([datasets.GEN_SYNTH, "--out", prefix, "--threads", str(min(64, cpu_budget()))] + workload_args(fragments, 1000, 0, args.stress), stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
+    import atexit
+    atexit.register(end_sample_ahead, {"process": process, "directory": directory})  # (however the run ends: no generator and no sample stay behind)
+    return {"process": process, "directory": directory, "prefix": prefix, "fragments": fragments, "started": time.time(), "host": host}
+
+
+def end_sample_ahead(ahead):
+    if ahead["process"].poll() is None:
+        ahead["process"].kill()
+    ahead["process"].wait()
+    shutil.rmtree(ahead["directory"], ignore_errors=True)
 
 
 def run_reference(command, cwd=None):
@@ -209,7 +256,7 @@ def stress_leg(fragments, steps=2, warmup=1):
     """BASELINE.json's config 3 at its stated size in the default run (review of round 5): the mismapper stress -- clipped segments of 40-70 nt copied from the partner gene,
     `-U 32767`, so that filter_mismappers sees every read and the candidates list 92.7 G supporting reads at 10^8 fragments (discordant lists implicit) -- as a run of this script
     of its own (a session of its own: -U is a parameter of the session, and the sample wants the device to itself), behind the session of the headline sample.  Its line, in short."""
-    command = [sys.executable, os.path.abspath(__file__), "--stress", "--fragments", str(fragments), "--steps", str(steps), "--warmup", str(warmup), "--no-cpu-baseline", "--no-deflated-leg"]
+    command = [sys.executable, os.path.abspath(__file__), "--stress", "--fragments", str(fragments), "--steps", str(steps), "--warmup", str(warmup), "--full", "--no-cpu-baseline", "--no-deflated-leg"]
     started = time.time()
     result = subprocess.run(command, stdout=subprocess.PIPE, stderr=subprocess.PIPE, universal_newlines=True, env=dict(os.environ, ARRIBA_BENCH_NO_STRESS_LEG="1"))
     lines = [line for line in result.stdout.splitlines() if line.startswith("{") and '"metric"' in line]
@@ -263,6 +310,43 @@ def deflated_leg(pipeline, directory, fragments, stress, stored_output, steps=2,
             # pass 1, the stream for pass 2 and the CRC)
             "container_kernels": {name: {"launches": values["launches"], "ms_per_launch": round(values["ms"] / values["launches"], 3), "ms_per_fed_sample": round(values["ms"] / (steps + 1), 1),
                                          "GB_per_s": round(values["bytes"] / max(values["ms"], 1e-9) / 1e6, 1)} for name, values in container_kernels.items()}}
+
+
+PLAIN_NUMBER = re.compile(rb"[+-]?(\d+\.?\d*|\.\d+)\Z")
+DUMP_ROWS = 50000  # --dump-outputs keeps at most this many lines of a file (50000 lines x ~32 fields x 8 bytes = 13 MB per file)
+
+
+def table_of_file(path, numpy):
+    """a tab-separated file of the workflow as numbers: one row per line (the header left out), one column per field -- the number of a field written as a plain decimal
+    number (PLAIN_NUMBER: digits, with a sign and a decimal point at the most; not "1e5", "1_0" or "inf"), for any other text the CRC-32 of its bytes -- and a last column
+    with the CRC-32 of the whole line.  Of a file of more than DUMP_ROWS lines a fixed, seeded sample of the lines is kept (the same lines in every run); the second array
+    holds the number of lines of the file and the CRC-32 of all of its bytes."""
+    import zlib
+    data = open(path, "rb").read()
+    lines = [line for line in data.split(b"\n") if line and not line.startswith(b"#")]
+    kept = lines
+    if len(lines) > DUMP_ROWS:
+        kept = [lines[k] for k in numpy.sort(numpy.random.default_rng(20240601).choice(len(lines), DUMP_ROWS, replace=False))]
+    width = max([line.count(b"\t") + 1 for line in kept] or [0])
+    table = numpy.zeros((len(kept), width + 1), dtype=numpy.float64)
+    for row, line in enumerate(kept):
+        for column, field in enumerate(line.split(b"\t")):
+            table[row, column] = float(field) if PLAIN_NUMBER.match(field) else float(zlib.crc32(field))
+        table[row, width] = float(zlib.crc32(line))
+    return table, numpy.array([len(lines), zlib.crc32(data)], dtype=numpy.float64)
+
+
+def dump_outputs(directory, stage_log, files):
+    """--dump-outputs: what the caller of the timed call holds after the last timed step -- the counts the call reports stage by stage (stage_counts.npy, in the order of the
+    stages) and the files it wrote (fusions.npy + fusions_file.npy, with --discarded also discarded.npy + discarded_file.npy: table_of_file above).  float64 throughout."""
+    import numpy
+    os.makedirs(directory, exist_ok=True)
+    numpy.save(os.path.join(directory, "stage_counts.npy"), numpy.array([count for _, count, _ in stage_log], dtype=numpy.float64))
+    for name, path in files:
+        if path:
+            table, whole = table_of_file(path, numpy)
+            numpy.save(os.path.join(directory, name + ".npy"), table)
+            numpy.save(os.path.join(directory, name + "_file.npy"), whole)
 
 
 def host_only(args):
@@ -337,6 +421,8 @@ def main():
     parser.add_argument("--no-stress-leg", action="store_true", help="skip the secondary measurement of BASELINE.json's config 3 (value_stress: the mismapper stress with -U 32767 at the size of the headline sample, a run of its own behind it)")
     parser.add_argument("--no-normal-pairs", action="store_true", help="skip the secondary measurement on the 10 M sample with 4 N ordinary proper pairs (value_with_normal_pairs)")
     parser.add_argument("--host-only", action="store_true")
+    parser.add_argument("--full", action="store_true", help="behind the timed steps, everything else this script measures and checks: the post-conditions of the last step and its fusions.tsv against the reference's, one sample alone (latency_s, kernel_ms_alone), the legs value_deflated, value_with_normal_pairs and value_stress, the CPU baseline (each of them has its own --no-... switch); without it: set up, warm up, the timed steps, the line")
+    parser.add_argument("--dump-outputs", metavar="DIR", help="write what the last timed step gave its caller as DIR/<name>.npy (float64): the counts of the stage log and the rows of the files written (dump_outputs)")
     parser.add_argument("--keep", help="keep the sample and the output files in this directory")
     parser.add_argument("--per-rank-samples", action="store_true", help="with --gpus N: every rank works on a sample of its own (weak scaling, no collective) instead of all ranks on one sample")
     args = parser.parse_args()
@@ -365,6 +451,7 @@ def main():
         command = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(args.gpus), "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(sys.argv[0])] + sys.argv[1:]  # (sys.argv[0]: bench.py, or the harness the CPU tier runs it on)
         progress("launching %d ranks: %s" % (args.gpus, " ".join(command)))
         raise SystemExit(subprocess.run(command, env=dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))).returncode)
+    ahead = start_sample_ahead(args)
     import torch
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
@@ -397,11 +484,12 @@ def main():
     if args.fragments is None:
         # BASELINE.json quotes the metric on the 100 M-read synthetic: that is the default where the box can hold it (54 GB of BAM in memory per GPU, ~140 GB of HBM
         # at the peak); otherwise config 2 (10 M).
-        memory = os.sysconf("SC_PAGE_SIZE") * os.sysconf("SC_PHYS_PAGES")
-        shm_free = shutil.disk_usage("/dev/shm").free if os.path.isdir("/dev/shm") else 0
         device_memory = torch.cuda.get_device_properties(local_rank).total_memory
-        samples = 1 if one_sample else world
-        fits = memory > samples * (160 << 30) and max(shm_free, shutil.disk_usage(tempfile.gettempdir()).free) > samples * (80 << 30) and device_memory > (200 << 30)
+        host_fits, memory, shm_free = ahead["host"] if ahead else host_holds_large_sample(1 if one_sample else world)  # (ahead: one GPU, and read before the generator began to fill the tmpfs)
+        fits = host_fits and device_memory > (200 << 30)
+        if ahead and not fits:  # (the host holds the 100 M sample, the device does not: the sample begun is given up)
+            end_sample_ahead(ahead)
+            ahead = None
         if distributed:  # (every rank must come to the same conclusion)
             verdict = torch.tensor([int(fits)], device="cuda" if dist.get_backend() == "nccl" else "cpu")
             dist.all_reduce(verdict, op=dist.ReduceOp.MIN)
@@ -409,12 +497,13 @@ def main():
         args.fragments = 100000000 if fits else 10000000
         if not fits:
             fallback_reason = "10 M fragments (BASELINE.json config 2) instead of the 100 M sample: host memory %.0f GB, tmpfs %.0f GB free, HBM %.0f GB" % (memory / 2**30, shm_free / 2**30, device_memory / 2**30)
-        elif not distributed and not os.environ.get("ARRIBA_BENCH_CHILD"):
+        elif args.full and not distributed and not os.environ.get("ARRIBA_BENCH_CHILD"):  # (a plain run: N steps of the sample, in this process, and no more)
             # the large sample runs in a child with a time limit: if it does not come back with a line (a time-out, an error), the line of config 2 is printed instead,
             # with the reason -- a bench without a line is worth nothing
             command = [sys.executable, os.path.abspath(__file__), "--fragments", str(args.fragments), "--steps", str(args.steps), "--warmup", str(args.warmup)]
             command += (["--subsampling-threshold", str(args.subsampling_threshold)] if args.subsampling_threshold is not None else []) + (["--name-length", str(args.name_length)] if args.name_length else [])
-            command += [flag for flag, on in (("--stress", args.stress), ("--discarded", args.discarded), ("--host-ingest", args.host_ingest), ("--python-stages", args.python_stages), ("--no-cpu-baseline", args.no_cpu_baseline), ("--no-normal-pairs", args.no_normal_pairs), ("--no-deflated-leg", args.no_deflated_leg), ("--no-pipeline", args.no_pipeline), ("--no-deferred-output", args.no_deferred_output)) if on]
+            command += (["--dump-outputs", os.path.abspath(args.dump_outputs)] if args.dump_outputs else [])
+            command += [flag for flag, on in (("--full", args.full), ("--stress", args.stress), ("--discarded", args.discarded), ("--host-ingest", args.host_ingest), ("--python-stages", args.python_stages), ("--no-cpu-baseline", args.no_cpu_baseline), ("--no-normal-pairs", args.no_normal_pairs), ("--no-deflated-leg", args.no_deflated_leg), ("--no-pipeline", args.no_pipeline), ("--no-deferred-output", args.no_deferred_output)) if on]
             # the driver gives a bench run 1800 s; the large sample gets what is left of ~1500 s after a reserve for the line of config 2 (generation, 25 steps of ~1 s, the
             # reference on its bounded sample: ~150 s), and its child decides after every step whether the steps asked for still fit (ARRIBA_BENCH_DEADLINE)
             total_limit = float(os.environ.get("ARRIBA_BENCH_TOTAL_LIMIT", "1500"))
@@ -444,8 +533,9 @@ def main():
         dist.broadcast_object_list(shared, src=0)
         directory = shared[0]
     else:
-        directory = args.keep or os.environ.get("ARRIBA_BENCH_SCRATCH") or scratch_directory(args.fragments * 600)
+        directory = ahead["directory"] if ahead else args.keep or os.environ.get("ARRIBA_BENCH_SCRATCH") or scratch_directory(args.fragments * 600)
     os.makedirs(directory, exist_ok=True)
+    cleaner = None
     try:
         if one_sample:
             timing = [None, None]
@@ -453,10 +543,18 @@ def main():
                 timing = list(generate_sample(args.fragments, 1000, directory, stress=args.stress))
             dist.broadcast_object_list(timing, src=0)  # (also the barrier behind which the files exist)
             prefix, generate_seconds = timing
+        elif ahead:  # the generator is at work since the start of the run: assembly and annotation are complete once it has begun the BAM file, and are loaded while it writes that
+            prefix = ahead["prefix"]
+            while ahead["process"].poll() is None and not os.path.exists(prefix + ".bam"):
+                time.sleep(0.05)
         else:
             prefix, generate_seconds = generate_sample(args.fragments, 1000, directory, read_seed=0 if world == 1 else 7000 + rank, stress=args.stress, threads=max(1, min(64, cpu_budget() // world)))
-        bam_bytes = os.path.getsize(prefix + ".bam")
-        progress("sample generated: %d fragments, %.1f GB BAM in %.1f s (%s)" % (args.fragments, bam_bytes / 1e9, generate_seconds, directory))
+
+        def sample_is_there():
+            progress("sample generated: %d fragments, %.1f GB BAM in %.1f s (%s)" % (args.fragments, os.path.getsize(prefix + ".bam") / 1e9, generate_seconds, directory))
+            return os.path.getsize(prefix + ".bam")
+        if not ahead:
+            bam_bytes = sample_is_there()
         subsampling = args.subsampling_threshold if args.subsampling_threshold is not None else (32767 if args.stress else 300)
         params = {"subsampling_threshold": subsampling} if subsampling != 300 else None
         pipeline = None
@@ -498,6 +596,11 @@ def main():
         else:
             session = HostSession(prefix + ".fa", prefix + ".gtf")  # assembly + annotation, once (resident)
         progress("assembly and annotation loaded")
+        if ahead:
+            if ahead["process"].wait() != 0:
+                raise SystemExit("the generator of the sample failed with exit code %d" % ahead["process"].returncode)
+            generate_seconds = time.time() - ahead["started"]
+            bam_bytes = sample_is_there()
 
         def step():
             nonlocal pipeline
@@ -607,12 +710,22 @@ def main():
             dist.barrier()
         elapsed = time.time() - started
         n = pipeline.n
+        writes_files = rank == 0 or not one_sample
         sample_alone, timed_profile, alone_profile = None, None, None
-        if pipelined:  # the sample submitted behind the last timed step is thrown away; then one sample alone, for the time from its file to its fusions.tsv when nothing overlaps it
+        if pipelined:  # the sample submitted behind the last timed step is thrown away; then (--full) one sample alone, for the time from its file to its fusions.tsv when nothing overlaps it
             pipeline.cancel()
             pipeline.defer_output(False)
             pipeline.finish_ahead(False)
             timed_profile = pipeline.kernel_profile()  # (the launches of the timed steps; the sample alone is profiled on its own)
+        if not args.full and not args.keep and not distributed:
+            # a plain run is done with its sample: the 54 GB of the file are given back by a thread while the outputs are dumped, the line is put together and the session closed (one after the other: 7 s)
+            import threading
+            cleaner = threading.Thread(target=lambda: os.path.exists(prefix + ".bam") and os.remove(prefix + ".bam"))  # (the rest of the directory goes at the end, as ever)
+            cleaner.start()
+        if args.dump_outputs and rank == 0:  # (the files of the last timed step, before anything else writes to their names)
+            dump_outputs(args.dump_outputs, stage_log, [("fusions", outputs[0]), ("discarded", outputs[1])])
+            progress("outputs of the last timed step written to %s" % args.dump_outputs)
+        if pipelined and args.full:
             pipeline.set_profiling(True)
             primed[0], pipelined = False, False
             alone_started = time.perf_counter()
@@ -640,18 +753,17 @@ def main():
         # post-conditions of the last step on the full-size batch (untimed; no oracle involved): a kernel that silently skipped a part of the batch would
         # leave alignments without a gene, or read filter counts that do not add up; the output file must exist and hold the fusions the log counted
         self_check = []
-        for slot in (0, 1):
+        for slot in (0, 1) if args.full else ():
             without_gene = int((pipeline.gene_sets(slot)[0] == 0).sum())
             if without_gene:
                 self_check.append("%d alignments in slot %d have no gene after annotate" % (without_gene, slot))
-        writes_files = rank == 0 or not one_sample
-        fusion_lines = sum(1 for line in open(outputs[0]) if not line.startswith("#")) if writes_files else stage_log[-1][1]
+        fusion_lines = sum(1 for line in open(outputs[0]) if not line.startswith("#")) if writes_files and args.full else stage_log[-1][1]  # (a plain run: the count of the last stage)
         if not stage_log or stage_log[-1][0] != "recover_isoforms" or fusion_lines != stage_log[-1][1]:
             self_check.append("fusions.tsv holds %d fusions, the last stage counted %s" % (fusion_lines, stage_log[-1:] or None))
         # the sample of config 2 (10 M fragments) is the one the unmodified reference was run on once (tests/golden/bench10m): the file written by the last timed step must be its file
         reference_check = None
         golden = os.path.join(ROOT, "tests", "golden", ("stress%dm" if args.stress else "bench%dm") % (args.fragments // 1000000), "meta.json")
-        if writes_files and args.fragments % 1000000 == 0 and subsampling == (32767 if args.stress else 300) and not args.discarded and not args.name_length and os.path.exists(golden):
+        if args.full and writes_files and args.fragments % 1000000 == 0 and subsampling == (32767 if args.stress else 300) and not args.discarded and not args.name_length and os.path.exists(golden):
             import hashlib
             meta = json.load(open(golden))
             if hashlib.sha256(open(outputs[0], "rb").read()).hexdigest() != meta["fusions_tsv_sha256"]:
@@ -738,7 +850,7 @@ def main():
                 "unit": "chimeric reads/s",
                 "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
                 "ms_per_step": elapsed / args.steps * 1e3,
-                "higher_is_better": True, "scaling": "strong" if one_sample else "weak", "vs_baseline": None, "dtype": "int32", "data": "synthetic",
+                "higher_is_better": True, "full": bool(args.full), "scaling": "strong" if one_sample else "weak", "vs_baseline": None, "dtype": "int32", "data": "synthetic",
                 "config": {"workload": "synthetic %d chimeric fragments " % args.fragments + ("in one sample" if one_sample else "per GPU") + " (%d BAM records, %.1f GB uncompressed BGZF; 2x100 bp, 24-contig synthetic genome, GENCODE-like GTF)%s, default filters, BAM file in memory -> fusions.tsv%s"
                                        % (pipeline.records if through_workflow_library else pipeline.ingest_result.records if pipeline.ingest_result else -1, bam_bytes / 1e9, (", mismapper stress (clips of 40-70 nt copied from the partner gene, -U %d)" % subsampling) if args.stress else ((", -U %d" % subsampling) if subsampling != 300 else "") + ((", read names of %d characters" % args.name_length) if args.name_length else ""),
                                           " + discarded.tsv" if args.discarded else ""),
@@ -785,28 +897,35 @@ def main():
                 line["stage_kernel_ms"] = {stage: round(values["ms"], 3) for stage, values in pipeline.timings.items()}
                 line["device_resident_step"] = {"what": "round 1's figure: resident batch -> filter_relative_support (kernel time of the stages between the ingest and the candidate-level filters)", "ms": round(resident_ms, 3),
                                                 "chimeric_reads_per_s": n / (resident_ms * 1e-3) if resident_ms > 0 else None}
-            line["self_check"] = "every alignment has a gene; fusions.tsv holds the fusions the last stage counted" + ("; " + reference_check if reference_check else
+            line["self_check"] = "not made: a plain run times the steps and no more (--full)" if not args.full else "every alignment has a gene; fusions.tsv holds the fusions the last stage counted" + ("; " + reference_check if reference_check else
                 "; NO file of the reference exists for a sample of this size (it needs ~1 GB per million fragments): parity at this size rests on the same code having produced the reference's fusions.tsv and discarded.tsv "
                 "at 10 M and 20 M fragments of config 2 and at 3 M of config 3 (SHA-256, GPU tier: tests/golden/bench10m, bench20m, stress3m) and on the legs of this line giving one another's file")
-            progress("self-check done, kernel profile read")
-            if through_workflow_library and not distributed and not args.no_deflated_leg:
+            progress("self-check done, kernel profile read" if args.full else "kernel profile of the timed steps read")
+            if args.full and through_workflow_library and not distributed and not args.no_deflated_leg:
                 progress("the same sample with deflated BGZF blocks")
                 line["value_deflated"] = deflated_leg(pipeline, directory, args.fragments, args.stress, outputs[0], finish_ahead=finish_ahead[0])
                 if not line["value_deflated"]["fusions_tsv_equals_the_stored_sample's"]:
                     raise SystemExit("bench self-check failed: the deflated sample gives another fusions.tsv than the stored one")
-            if through_workflow_library and not distributed and not args.stress and not args.no_normal_pairs:
+            if args.full and through_workflow_library and not distributed and not args.stress and not args.no_normal_pairs:
                 progress("the sample with 4 N ordinary proper pairs")
                 line["value_with_normal_pairs"] = normal_pairs_leg(pipeline, directory, fragments=min(10000000, args.fragments))
-            if args.no_cpu_baseline or distributed:  # (timed at N = 1 only)
-                line["cpu_baseline"] = {"value": None, "unit": "chimeric reads/s", "cores": 1, "kind": "reference", "sample": "skipped: the reference is timed by the run with 1 GPU" if distributed else "skipped"}
+            if not args.full or args.no_cpu_baseline or distributed:  # (timed at N = 1 only)
+                line["cpu_baseline"] = {"value": None, "unit": "chimeric reads/s", "cores": 1, "kind": "reference", "sample": "skipped: the reference is timed by the run with 1 GPU" if distributed else "skipped" if args.full else "skipped: the reference is timed by a run with --full"}
             else:
                 line["cpu_baseline"] = cpu_baseline(1000, directory, stress=args.stress, subsampling=subsampling, timed_fragments=total_fragments, sample_fragments=150000 if args.stress else 800000)  # (config 3: the reference needs 5 1/2 minutes for 1 M fragments)
-            if through_workflow_library and not distributed and not args.stress and not args.no_stress_leg and not os.environ.get("ARRIBA_BENCH_NO_STRESS_LEG") and args.fragments >= 10000000:
+            if args.full and through_workflow_library and not distributed and not args.stress and not args.no_stress_leg and not os.environ.get("ARRIBA_BENCH_NO_STRESS_LEG") and args.fragments >= 10000000:
                 progress("BASELINE.json config 3 at the size of the headline sample: the mismapper stress with -U 32767, in a session of its own")
                 pipeline.close()  # (the stress sample wants the device to itself: 92.7 G list entries at 10^8 fragments)
                 line["value_stress"] = stress_leg(args.fragments)
             print(json.dumps(line))
+            sys.stdout.flush()
+        if cleaner is not None and pipeline is not None:
+            pipeline.close()
+            progress("session closed")
     finally:
+        if cleaner is not None:
+            cleaner.join()
+            progress("sample removed")
         if one_sample:
             try:
                 dist.barrier()  # nobody removes the sample while another rank still reads it

@@ -79,7 +79,7 @@ def test_bench_launches_its_own_ranks_and_refuses_a_wrong_world_size(built, emu_
 def test_bench_with_one_rank_times_the_workflow_library(flags, built, emu_api, tmp_path):
     """bench.py as the driver runs it at N = 1: the timed call is arriba_workflow_sample of the product library (here its build over the stepping harness,
     tests/emu/libworkflow_on_harness.so), with --python-stages the ctypes mirror of the stage order; both end with the same counts and one line of the contract."""
-    command = [sys.executable, os.path.join(ROOT, "tests", "bench_on_harness.py"), "--steps", "2", "--warmup", "1", "--fragments", "20000", "--no-cpu-baseline"] + flags
+    command = [sys.executable, os.path.join(ROOT, "tests", "bench_on_harness.py"), "--steps", "2", "--warmup", "1", "--fragments", "20000", "--full", "--no-cpu-baseline"] + flags
     result = subprocess.run(command, stdout=subprocess.PIPE, stderr=subprocess.PIPE, universal_newlines=True, timeout=1500)
     assert result.returncode == 0, result.stderr[-3000:]
     lines = [line for line in result.stdout.splitlines() if line.startswith("{")]
@@ -94,6 +94,35 @@ def test_bench_with_one_rank_times_the_workflow_library(flags, built, emu_api, t
     if not flags:  # the leg with 4 N ordinary proper pairs beside the chimeric fragments: five times the records, more chimeric fragments (read-through pairs among the ordinary ones)
         leg = line["value_with_normal_pairs"]
         assert leg["chimeric_reads_per_s"] > 0 and leg["bam_records_per_s"] > 4 * leg["chimeric_reads_per_s"] and "4 N ordinary proper pairs" in leg["what"]
+
+
+def test_a_plain_bench_run_dumps_the_same_outputs_twice(built, emu_api, tmp_path):
+    """bench.py without --full, the run that is repeated for every change: the sample generated ahead of the session, the timed steps, --dump-outputs, the line -- and
+    nothing of what --full adds.  Two runs with the same arguments work on the same sample and leave the same arrays, so that two builds can be compared array by array."""
+    import numpy
+    dumps = []
+    for run in ("a", "b"):
+        directory = str(tmp_path / run)
+        command = [sys.executable, os.path.join(ROOT, "tests", "bench_on_harness.py"), "--steps", "2", "--warmup", "1", "--fragments", "20000", "--dump-outputs", directory]
+        result = subprocess.run(command, stdout=subprocess.PIPE, stderr=subprocess.PIPE, universal_newlines=True, timeout=1500)
+        assert result.returncode == 0, result.stderr[-3000:]
+        lines = [line for line in result.stdout.splitlines() if line.startswith("{")]
+        assert len(lines) == 1, result.stdout[-2000:]
+        line = json.loads(lines[0])
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "steps", "warmup", "ms_per_step", "full"):
+            assert key in line, key
+        assert line["full"] is False and line["steps"] == 2 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["value"] > 0
+        assert line["config"]["fragments_per_gpu"] == 20886 and line["config"]["fusions"] == 343
+        for key in ("value_with_normal_pairs", "value_deflated", "value_stress"):  # (what moved behind --full)
+            assert key not in line, key
+        assert line["latency_s"] is None and line["cpu_baseline"]["value"] is None and line["self_check"].startswith("not made")
+        dumps.append({name: numpy.load(os.path.join(directory, name)) for name in sorted(os.listdir(directory))})
+    first, second = dumps
+    assert sorted(first) == ["fusions.npy", "fusions_file.npy", "stage_counts.npy"] and sorted(second) == sorted(first)
+    for name in first:
+        assert first[name].dtype == numpy.float64 and first[name].shape == second[name].shape and (first[name] == second[name]).all(), name
+    assert first["fusions.npy"].shape[0] == 343 and first["fusions_file.npy"][0] == 343  # one row per fusion of the last timed step
+    assert first["stage_counts.npy"][-1] == 343 and sum(array.nbytes for array in first.values()) < (64 << 20)
 
 
 def test_an_error_on_one_rank_ends_the_run_on_all(dataset_files, emu_api, tmp_path):

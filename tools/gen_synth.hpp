@@ -80,7 +80,7 @@ typedef std::function<void(const uint8_t*, size_t)> ByteSink;
 class Generator {
 public:
 	explicit Generator(const Config& config);
-	void build_reference();                       // genome + genes + junction table
+	void build_reference(unsigned int n_threads = 1); // genome + genes + junction table (the bases of the genome drawn by up to n_threads threads: the same genome for every number)
 	void write_fasta(const std::string& path) const;
 	void write_gtf(const std::string& path) const;
 	void write_rule_files(const std::string& blacklist_path, const std::string& known_fusions_path) const; // a blacklist and a known-fusions file derived from the junction table

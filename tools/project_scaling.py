@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""What the read-sharded split of one sample over N GPUs can be expected to take, from the MEASURED phases of a one-GPU line of bench.py:
+"""What the read-sharded split of one sample over N GPUs can be expected to take, from the MEASURED phases of a one-GPU line of bench.py --full:
     python tools/project_scaling.py profiles/r06b_bench100m.json [N ...]
 
 No multi-GPU box was available to any round: this is a projection, and it says which of its terms are measurements (every kernel's own time in the sample that ran alone:
