@@ -87,7 +87,11 @@ class IngestResult(ctypes.Structure):
 
 
 class BamPiece(ctypes.Structure):
-    _fields_ = [("stored_bgzf", c_int), ("bytes", c_size_t), ("stream_bytes", c_size_t), ("n_blocks", c_uint32)]
+    """ahost_bam_piece: stored_bgzf is the KIND of the piece -- 0 stream bytes, 1 stored BGZF, 2 deflated BGZF, 3 lines of SAM text (first_line: the number of its first line)"""
+    _fields_ = [("stored_bgzf", c_int), ("bytes", c_size_t), ("stream_bytes", c_size_t), ("n_blocks", c_uint32), ("first_line", c_uint64)]
+
+
+PIECE_STREAM, PIECE_STORED_BGZF, PIECE_DEFLATED_BGZF, PIECE_SAM_TEXT = 0, 1, 2, 3
 
 
 class BatchRows(ctypes.Structure):
@@ -213,6 +217,9 @@ def bind_device_api(lib, prefix="agpu_"):
         "ingest_begin": (c_int, [ctx, POINTER(IngestConfig)]),
         "ingest_push": (c_int, [ctx, c_void_p, c_size_t]),
         "ingest_push_bgzf": (c_int, [ctx, c_void_p, c_size_t, POINTER(BgzfBlock), c_uint32, c_size_t]),
+        "ingest_sam_targets": (c_int, [ctx, c_void_p, c_void_p, c_uint32]),
+        "ingest_push_sam": (c_int, [ctx, c_void_p, c_size_t, c_uint64]),
+        "sam_transcode": (c_int, [ctx, c_void_p, c_size_t, c_void_p, c_void_p, c_uint32, c_void_p, c_size_t, POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64)]),
         "ingest_finish": (c_int, [ctx, POINTER(IngestResult)]),
         "shard_export_size": (c_int, [ctx, POINTER(c_uint64)]),
         "shard_export": (c_int, [ctx, c_void_p, c_uint64]),
@@ -285,6 +292,8 @@ def bind_host_api(lib):
         "ahost_bam_open_part": (c_int, [session, c_char_p, c_int, ctypes.c_uint, ctypes.c_uint, ctypes.c_uint, POINTER(IngestConfig)]),
         "ahost_bam_next": (c_int, [session, c_void_p, c_size_t, POINTER(BgzfBlock), c_uint32, POINTER(BamPiece)]),
         "ahost_bam_close": (None, [session]),
+        "ahost_bam_sam_targets": (c_int, [session, POINTER(c_void_p), POINTER(c_void_p), POINTER(c_uint32)]),
+        "ahost_sam_transcode": (c_int, [c_void_p, c_size_t, c_void_p, c_void_p, c_uint32, c_void_p, c_size_t, POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64)]),
         "ahost_adopt_device_ingest": (c_int, [session, POINTER(IngestResult), c_void_p, c_void_p, c_void_p, c_void_p]),
         "ahost_set_batch_rows": (c_int, [session, POINTER(BatchRows), c_void_p]),
         "ahost_fusion_table_reads": (c_int, [POINTER(FusionTable), c_int, c_void_p, c_uint64, POINTER(c_uint64)]),

@@ -175,6 +175,7 @@ struct agpu_ctx {
 	uint32_t ingest_n_targets = 0, ingest_max_itd_length = 100, ingest_pushes = 0, ingest_host_buffers = 2;
 	uint8_t ingest_external_duplicate_marking = 0;
 	bool ingest_active = false, ingest_finishing = false /* inside agpu_ingest_finish: its tables are in use although the feed is over */, batch_from_ingest = false, ingest_part_of_sample = false, ingest_verify_crc = false, ingest_deflated_pieces = false /* a piece of this ingest went through bgzf_inflate_kernel */;
+	bool ingest_sam = false; uint32_t sam_n_targets = 0, sam_table_mask = 0; // the pieces of this ingest are SAM text (agpu_sam.hip: agpu_ingest_sam_targets uploaded the @SQ names to "sam.names" / "sam.name_offset" / "sam.table")
 	agpu::DeviceBuffer ingest_qname_keys; uint64_t ingest_qname_runs = 0; // a part of a sample: 128-bit keys of the runs of read names in its stream
 	agpu_ingest_result ingest_result; uint64_t ingest_pool_sizes[2] = { 0, 0 }; // what the last ingest (or merge of parts) reported; CIGAR words and sequence bytes of its pools
 	agpu::IngestProgress ingest_progress;
@@ -237,6 +238,12 @@ namespace agpu {
 
 // agpu_ingest.hip: the stream and the per-record tables of the last ingest given back to the device (they are kept for the next sample as long as memory allows); true if there were any
 bool release_ingest_buffers(agpu_ctx* ctx);
+// agpu_ingest.hip, for the pushes of agpu_sam.hip: room for `needed` bytes in the stream (it moves when it grows), and what every push ends with (the caller's buffer of the push
+// before is free, the windows of the front go on over what has arrived)
+int ingest_grow_stream(agpu_ctx* ctx, uint64_t needed);
+int ingest_piece_pushed(agpu_ctx* ctx);
+// agpu_sam.hip, for agpu_ingest_finish: AGPU_ERR_INVALID with "failed to load alignments: SAM line N: <reason>" if a line of the SAM text of this ingest was malformed
+int sam_ingest_verdict(agpu_ctx* ctx);
 // agpu_api.hip: the buffers that hold a sample (batch, gene sets, candidates, read lists, k-mer index, ...) change hands between the lanes of a session: `ctx`, about to build
 // its batch, takes what its sibling -- whose sample is done on the device -- holds wherever that is the larger buffer; the sibling's sample is gone afterwards
 void take_sample_buffers(agpu_ctx* ctx, bool batch_group = true, bool stage_group = true);

@@ -906,13 +906,21 @@ void fill_pack_target(agpu_ctx* ctx, PackTarget& out) {
 
 }
 
+int agpu::ingest_grow_stream(agpu_ctx* ctx, uint64_t needed) { return grow_stream(ctx, needed); }
+int agpu::ingest_piece_pushed(agpu_ctx* ctx) {
+	TRY(wait_for_previous_push(ctx));
+	++ctx->ingest_pushes;
+	return windows_after_push(ctx);
+}
+
 bool agpu::release_ingest_buffers(agpu_ctx* ctx) {
 	bool released = ctx->ingest_stream.ptr != nullptr;
 	ctx->ingest_stream.release(); for (int k = 0; k < AGPU_PIECE_SLOTS; ++k) ctx->ingest_raw[k].release();
 	if (!ctx->ingest_part_of_sample) ctx->coverage_windows32.release(); // (a part of a sample hands the windows on as they are: agpu_shard_export)
 	static const char* const temporary[] = { "ingest.record_offset", "ingest.keys", "ingest.keys_sorted", "ingest.record_bits", "ingest.sorted_records", "ingest.head", "ingest.group_start", "ingest.first_flags", "ingest.stream_rank", "ingest.group_first", "ingest.group_begin", "ingest.group_count", "ingest.plain_plans", "ingest.itd_plans",
 		"ingest.valid", "ingest.sizes", "ingest.refs", "ingest.order", "ingest.order_keys", "ingest.order_keys_sorted", "ingest.cigar_words", "ingest.sequence_bytes", "ingest.name_lengths", "ingest.new_group", "ingest.cigar_base",
-		"ingest.sequence_base", "ingest.name_base", "ingest.group_id", "ingest.qname_differs", "ingest.qname_run", "ingest.run_keys", "ingest.run_keys_sorted", "ingest.window_rocprim", "ingest.segment_first", "ingest.segment_end", "ingest.segment_end_before", "ingest.segment_count", "ingest.segment_base", "ingest.segment_mismatch", "ingest.rocprim", "ingest.coverage_summed", "ingest.hit_index" };
+		"ingest.sequence_base", "ingest.name_base", "ingest.group_id", "ingest.qname_differs", "ingest.qname_run", "ingest.run_keys", "ingest.run_keys_sorted", "ingest.window_rocprim", "ingest.segment_first", "ingest.segment_end", "ingest.segment_end_before", "ingest.segment_count", "ingest.segment_base", "ingest.segment_mismatch", "ingest.rocprim", "ingest.coverage_summed", "ingest.hit_index",
+		"sam.wave_count", "sam.wave_base", "sam.line_start", "sam.record_size", "sam.record_offset", "sam.rocprim", "sam.tool_text", "sam.tool_records" };
 	for (size_t k = 0; k < sizeof(temporary) / sizeof(temporary[0]); ++k) { DeviceBuffer& buffer = ctx->scratch(temporary[k]); if (buffer.ptr != nullptr) released = true; buffer.release(); }
 	return released;
 }
@@ -946,7 +954,7 @@ int agpu_ingest_begin(agpu_ctx* ctx, const agpu_ingest_config* config) {
 	}
 	if (config->host_buffers > AGPU_PIECE_SLOTS) { set_last_error("agpu_ingest_config.host_buffers: at most 4"); return AGPU_ERR_INVALID; }
 	ctx->ingest_host_buffers = config->host_buffers < 2 ? 2 : config->host_buffers;
-	ctx->ingest_n_targets = config->n_targets; ctx->ingest_first_record = config->first_record_offset; ctx->ingest_stream_size = 0; ctx->ingest_pushes = 0; ctx->ingest_deflated_pieces = false;
+	ctx->ingest_n_targets = config->n_targets; ctx->ingest_first_record = config->first_record_offset; ctx->ingest_stream_size = 0; ctx->ingest_pushes = 0; ctx->ingest_deflated_pieces = false; ctx->ingest_sam = false;
 	{ const char* knob = getenv("ARRIBA_VERIFY_CRC"); ctx->ingest_verify_crc = !(knob != nullptr && knob[0] == '0'); } // (the stored blocks are checked as htslib checks them; "0": a measurement without)
 	ALLOC(ctx->scratch("ingest.crc_mismatches"), 8); // [0] blocks whose payload does not give the CRC-32 of their trailer, [1] deflated blocks that did not decode (read whatever ARRIBA_VERIFY_CRC says)
 	if (ctx->ingest_verify_crc && ctx->scratch("ingest.crc_tables").ptr == nullptr) {
@@ -1101,6 +1109,10 @@ int agpu_ingest_finish(agpu_ctx* ctx, agpu_ingest_result* result) {
 		HIP_CHECK(hipMemcpyAsync(mismatches, ctx->scratch("ingest.crc_mismatches").ptr, 8, hipMemcpyDeviceToHost, s));
 		HIP_CHECK(hipStreamSynchronize(s));
 		if (mismatches[1] > 0 || (ctx->ingest_verify_crc && mismatches[0] > 0)) { set_last_error("failed to load alignments"); return AGPU_ERR_INVALID; }
+	}
+	if (ctx->ingest_sam) { // SAM text: a malformed line left no record in the stream; the sample fails here, with the number of the first one
+		const int verdict = agpu::sam_ingest_verdict(ctx);
+		if (verdict != AGPU_OK) { if (ctx->ingest_progress.work) HIP_CHECK(hipStreamSynchronize(ctx->ingest_progress.work)); /* (the windows in flight: the next sample begins with a quiet device) */ return verdict; }
 	}
 	DeviceBuffer& counters = ctx->scratch("ingest.counters"); DeviceBuffer& rocprim_scratch = ctx->scratch("ingest.rocprim");
 	ALLOC(counters, IC_COUNT * 4);

@@ -10,6 +10,7 @@
 
 #include <cstdint>
 #include "../../../include/arriba_host.h"
+#include "../device/sam_core.hpp"
 #include <map>
 #include <string>
 #include <unordered_map>
@@ -204,6 +205,23 @@ struct ByteSource { virtual size_t read(uint8_t* buffer, size_t capacity) = 0; v
 ByteSource* open_bam_file(const std::string& path);               // BGZF/gzip or raw BAM, file or /dev/stdin
 ByteSource* open_memory_source(const uint8_t* data, size_t size); // raw (already inflated) BAM stream
 
+// SAM text: the header lines, the @SQ names as sam_core.hpp looks them up, and the lines stepped on the host (ingest.cpp)
+struct SamHeader {
+	std::vector<std::string> names; std::vector<uint32_t> lengths; bool sorted_by_coordinate = false; uint64_t bytes = 0, lines = 0;
+	bool scan(const uint8_t* text, size_t size, bool at_end);
+	void bam_header(const uint8_t* text, std::vector<uint8_t>& out) const;
+};
+struct SamTargetTable {
+	std::string names; std::vector<uint32_t> offsets, table;
+	void build(const char* all_names, const uint32_t* name_offset, uint32_t n);
+	void build(const std::vector<std::string>& list);
+	agpu::SamTargets view() const;
+};
+bool head_is_sam_text(const uint8_t* head, size_t size);
+void sam_transcode_lines(const uint8_t* text, size_t size, const agpu::SamTargets& targets, uint64_t first_line_number, std::vector<uint8_t>& out, uint64_t& n_records, uint64_t& n_lines, uint64_t& bad_line, uint32_t& bad_reason);
+std::string sam_line_error(uint64_t line, uint32_t reason);
+ByteSource* text_or_bam_source(ByteSource* inner); // takes `inner`; BAM bytes pass through, SAM text comes out as the BAM stream of the same alignments
+
 // The file side of the device ingest (agpu_ingest_*): container recognised from the one open stream, BAM header parsed, bytes handed on in pieces.
 class BamFeed;
 BamFeed* open_bam_feed(const std::string& path);
@@ -211,6 +229,7 @@ void close_bam_feed(BamFeed* feed);
 uint64_t bam_feed_header(BamFeed* feed, std::vector<std::string>& target_names); // returns the size of the header = offset of the first record in the uncompressed stream
 uint64_t bam_feed_take_part(BamFeed* feed, uint32_t part, uint32_t parts);            // the feed delivers only part `part` of `parts` of the records from now on; returns the offset of its first record in the stream
 uint64_t bam_feed_size_hint(BamFeed* feed);                                       // expected size of the uncompressed stream, 0 = unknown
+const SamTargetTable* bam_feed_sam_targets(BamFeed* feed);                        // the @SQ names when the file is SAM text (its pieces are of kind 3), NULL for BAM
 bool bam_feed_next(BamFeed* feed, uint8_t* buffer, size_t capacity, agpu_bgzf_block* blocks, uint32_t block_capacity, ahost_bam_piece& piece);
 
 // reference: source/read_chimeric_alignments.cpp:560-773 with separate_chimeric_bam_file=false, is_rna_bam_file=true

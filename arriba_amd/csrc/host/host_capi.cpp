@@ -555,6 +555,34 @@ int ahost_bam_next(ahost_session* session, void* buffer, size_t capacity, agpu_b
 	catch (const std::exception& e) { g_error = e.what(); return -1; }
 }
 
+int ahost_bam_sam_targets(ahost_session* session, const char** names, const uint32_t** name_offset, uint32_t* n_targets) {
+	if (!session || !session->feed || !names || !name_offset || !n_targets) { g_error = "ahost_bam_open must run first"; return -1; }
+	const SamTargetTable* table = bam_feed_sam_targets(session->feed);
+	if (table == NULL) return 0;
+	*names = table->names.data(); *name_offset = table->offsets.data(); *n_targets = (uint32_t) table->offsets.size() - 1;
+	return 1;
+}
+
+int ahost_sam_transcode(const void* text, size_t size, const char* names, const uint32_t* name_offset, uint32_t n_targets, void* out, size_t capacity, uint64_t* out_bytes, uint64_t* n_records, uint64_t* bad_line) {
+	if ((!text && size > 0) || !name_offset || !out_bytes || !n_records || !bad_line) { g_error = "null argument"; return -1; }
+	try {
+		*out_bytes = 0; *n_records = 0; *bad_line = 0;
+		SamTargetTable targets;
+		targets.build(names ? names : "", name_offset, n_targets);
+		const uint8_t* bytes = (const uint8_t*) text;
+		size_t at = 0; uint64_t header_lines = 0;
+		while (at < size && bytes[at] == '@') { const uint8_t* feed = (const uint8_t*) memchr(bytes + at, '\n', size - at); at = feed ? (size_t) (feed - bytes) + 1 : size; ++header_lines; }
+		std::vector<uint8_t> records;
+		uint64_t lines = 0; uint32_t reason = 0;
+		sam_transcode_lines(bytes + at, size - at, targets.view(), header_lines + 1, records, *n_records, lines, *bad_line, reason);
+		*out_bytes = records.size();
+		if (records.size() > capacity) { g_error = "the buffer is too small for the records"; return -1; }
+		if (!records.empty()) memcpy(out, records.data(), records.size());
+		if (*bad_line != 0) { g_error = sam_line_error(*bad_line, reason); return -1; }
+		return 0;
+	} catch (const std::exception& e) { g_error = e.what(); return -1; }
+}
+
 void ahost_bam_close(ahost_session* session) { if (session && session->feed) { close_bam_feed(session->feed); session->feed = nullptr; } }
 
 int ahost_adopt_device_ingest(ahost_session* session, const agpu_ingest_result* result, const uint64_t* viral_read_counts, const uint16_t* coverage, const uint8_t* fragment_starts, const uint8_t* fragment_ends) {
@@ -644,7 +672,7 @@ int ahost_set_batch_rows(ahost_session* session, const agpu_batch_rows* rows, co
 }
 
 int ahost_ingest_bam_memory(ahost_session* session, const uint8_t* data, size_t size, int external_duplicate_marking, unsigned int max_itd_length) {
-	return ingest(session, open_memory_source(data, size), external_duplicate_marking, max_itd_length);
+	return ingest(session, text_or_bam_source(open_memory_source(data, size)), external_duplicate_marking, max_itd_length);
 }
 
 const agpu_annotation_view* ahost_annotation_view(ahost_session* session) { return &session->annotation_view; }

@@ -1108,9 +1108,10 @@ ByteSource* open_bam_file(const std::string& path) {
 		if (n == 0) break;
 		got += n;
 	}
-	if (BgzfSource::is_bgzf_header(header, got)) return new BgzfSource(file, header, got, ingest_threads());
-	if (got >= 2 && header[0] == 31 && header[1] == 139) return new GzipSource(file, header, got);
-	return new RawSource(file, header, got);
+	// (what comes out of the container is BAM or SAM text: text_or_bam_source looks at the uncompressed head)
+	if (BgzfSource::is_bgzf_header(header, got)) return text_or_bam_source(new BgzfSource(file, header, got, ingest_threads()));
+	if (got >= 2 && header[0] == 31 && header[1] == 139) return text_or_bam_source(new GzipSource(file, header, got));
+	return text_or_bam_source(new RawSource(file, header, got));
 }
 
 // reference: source/read_chimeric_alignments.cpp:560-773
@@ -1313,6 +1314,154 @@ struct FileBytes {
 
 }
 
+// ---- SAM text (sam_open reads SAM text as well as BAM: source/read_chimeric_alignments.cpp:563) ----------------------------------------------------------
+// The header is parsed here; the alignment lines become BAM records through ../device/sam_core.hpp -- on the device (agpu_ingest_push_sam) or, for the
+// host ingest and ahost_sam_transcode, stepped on the host by sam_transcode_lines below.
+
+// true: the uncompressed head of a file is SAM text ('@' header lines or an alignment line); false: BAM.  Anything else is no input of the reference's.
+bool head_is_sam_text(const uint8_t* head, size_t size) {
+	if (size >= 4 && memcmp(head, "BAM\1", 4) == 0) return false;
+	if (size == 0) throw std::runtime_error("failed to read SAM header");
+	if (head[0] == '@') return true;
+	size_t tabs = 0, at = 0;
+	for (; at < size && head[at] != '\n'; ++at) { if (head[at] == '\t') ++tabs; else if (head[at] < 32 && head[at] != '\r') throw std::runtime_error("failed to read SAM header"); }
+	if (tabs < 10) throw std::runtime_error("failed to read SAM header");
+	return true;
+}
+
+// the '@' lines at the start of text[0 .. size).  false: the header may go on behind `size` (read more, unless the stream has ended: at_end)
+bool SamHeader::scan(const uint8_t* text, size_t size, bool at_end) {
+	names.clear(); lengths.clear(); sorted_by_coordinate = false; bytes = 0; lines = 0;
+	size_t at = 0;
+	while (at < size) {
+		if (text[at] != '@') { bytes = at; return true; }
+		const uint8_t* feed = (const uint8_t*) memchr(text + at, '\n', size - at);
+		if (feed == NULL && !at_end) return false;
+		size_t end = feed != NULL ? (size_t) (feed - text) : size;
+		const size_t next = feed != NULL ? end + 1 : size;
+		if (end > at && text[end - 1] == '\r') --end;
+		const std::string line((const char*) text + at, end - at);
+		if (line.compare(0, 3, "@HD") == 0 && lines == 0) sorted_by_coordinate = line.find("SO:coordinate") != std::string::npos;
+		if (line.compare(0, 4, "@SQ\t") == 0) {
+			std::string name; uint64_t length = 0;
+			for (size_t field = 4; field < line.size(); ) {
+				size_t field_end = line.find('\t', field);
+				if (field_end == std::string::npos) field_end = line.size();
+				if (line.compare(field, 3, "SN:") == 0) name = line.substr(field + 3, field_end - field - 3);
+				else if (line.compare(field, 3, "LN:") == 0) length = strtoull(line.c_str() + field + 3, NULL, 10);
+				field = field_end + 1;
+			}
+			if (name.empty()) throw std::runtime_error("failed to read SAM header");
+			names.push_back(name); lengths.push_back((uint32_t) length);
+		}
+		++lines; at = next;
+	}
+	bytes = at;
+	return at_end;
+}
+// the BAM header `samtools view -b` writes in front of the records (SAMv1 section 4.2)
+void SamHeader::bam_header(const uint8_t* text, std::vector<uint8_t>& out) const {
+	auto put32 = [&out](uint32_t v) { for (int k = 0; k < 4; ++k) out.push_back((uint8_t) (v >> (8 * k))); };
+	out.assign({ 'B', 'A', 'M', 1 });
+	put32((uint32_t) bytes); out.insert(out.end(), text, text + bytes);
+	put32((uint32_t) names.size());
+	for (size_t t = 0; t < names.size(); ++t) { put32((uint32_t) names[t].size() + 1); out.insert(out.end(), names[t].begin(), names[t].end()); out.push_back(0); put32(lengths[t]); }
+}
+
+void SamTargetTable::build(const char* all_names, const uint32_t* name_offset, uint32_t n) {
+	names.assign(all_names, all_names + name_offset[n]); offsets.assign(name_offset, name_offset + n + 1);
+	table.resize(agpu::sam_table_slots(n));
+	agpu::sam_build_table(names.data(), offsets.data(), n, table.data());
+}
+void SamTargetTable::build(const std::vector<std::string>& list) {
+	std::string all; std::vector<uint32_t> offset(1, 0);
+	for (size_t t = 0; t < list.size(); ++t) { all += list[t]; offset.push_back((uint32_t) all.size()); }
+	build(all.data(), offset.data(), (uint32_t) list.size());
+}
+agpu::SamTargets SamTargetTable::view() const { agpu::SamTargets t = { names.data(), offsets.data(), table.data(), (uint32_t) table.size() - 1, (uint32_t) offsets.size() - 1 }; return t; }
+
+// Whole lines text[0 .. size) (the last one may lack its "\n") -> their records appended to `out`, sam_core.hpp stepped line by line.  A malformed line gives no record; the
+// first one is noted (line numbers count from first_line_number).  ARRIBA_SAM_ISOLATE_LINES=1: every line is parsed from a heap copy of exactly its size, so that a build
+// with AddressSanitizer (tools/sanitize_host.sh) sees any read outside the line.
+void sam_transcode_lines(const uint8_t* text, size_t size, const agpu::SamTargets& targets, uint64_t first_line_number, std::vector<uint8_t>& out, uint64_t& n_records, uint64_t& n_lines, uint64_t& bad_line, uint32_t& bad_reason) {
+	const bool isolate = getenv("ARRIBA_SAM_ISOLATE_LINES") != NULL && getenv("ARRIBA_SAM_ISOLATE_LINES")[0] == '1';
+	n_records = 0; n_lines = 0;
+	for (size_t at = 0; at < size; ) {
+		const size_t feed = (size_t) agpu::sam_line_feed(text, at, size);
+		size_t end = feed;
+		if (end > at && text[end - 1] == '\r') --end;
+		const uint8_t* line = text + at;
+		std::unique_ptr<uint8_t[]> copy;
+		if (isolate) { copy.reset(new uint8_t[end - at]); memcpy(copy.get(), line, end - at); line = copy.get(); }
+		uint32_t reason = 0;
+		const uint32_t bytes = end - at > 0xFFFFFFF0u ? 0 : agpu::sam_line<false>(line, (uint32_t) (end - at), targets, NULL, reason);
+		if (bytes == 0) { if (bad_line == 0) { bad_line = first_line_number + n_lines; bad_reason = reason; } }
+		else {
+			const size_t before = out.size();
+			out.resize(before + bytes);
+			agpu::sam_line<true>(line, (uint32_t) (end - at), targets, &out[before], reason);
+			++n_records;
+		}
+		++n_lines; at = feed + 1;
+	}
+}
+std::string sam_line_error(uint64_t line, uint32_t reason) { return "failed to load alignments: SAM line " + std::to_string(line) + ": " + agpu::sam_reason_text(reason); }
+
+namespace {
+// What open_bam_file and ahost_ingest_bam_memory hand to the host ingest: BAM bytes pass through; SAM text is turned into the BAM stream of the same alignments on the way
+class TextOrBamSource: public ByteSource {
+public:
+	explicit TextOrBamSource(ByteSource* inner): inner_(inner), served_(0), sniffed_(false), sam_(false), end_(false), lines_(0) {}
+	size_t read(uint8_t* buffer, size_t capacity) {
+		if (!sniffed_) sniff();
+		while (served_ == out_.size()) {
+			out_.clear(); served_ = 0;
+			if (!sam_) return inner_->read(buffer, capacity);
+			if (end_ && text_.empty()) return 0;
+			more(4u << 20);
+			size_t whole = text_.size();
+			if (!end_) { while (whole > 0 && text_[whole - 1] != '\n') --whole; }
+			uint64_t n_records = 0, n_lines = 0, bad_line = 0; uint32_t bad_reason = 0;
+			sam_transcode_lines(text_.data(), whole, targets_.view(), lines_ + 1, out_, n_records, n_lines, bad_line, bad_reason);
+			if (bad_line != 0) throw std::runtime_error(sam_line_error(bad_line, bad_reason));
+			lines_ += n_lines;
+			text_.erase(text_.begin(), text_.begin() + whole);
+		}
+		const size_t n = std::min(capacity, out_.size() - served_);
+		memcpy(buffer, &out_[served_], n);
+		served_ += n;
+		return n;
+	}
+private:
+	void more(size_t bytes) { // appends up to `bytes` of the inner stream to text_
+		const size_t before = text_.size();
+		text_.resize(before + bytes);
+		size_t got = 0;
+		while (got < bytes) { const size_t n = inner_->read(&text_[before + got], bytes - got); if (n == 0) { end_ = true; break; } got += n; }
+		text_.resize(before + got);
+	}
+	void sniff() {
+		sniffed_ = true;
+		more(1u << 16);
+		sam_ = head_is_sam_text(text_.data(), text_.size());
+		if (!sam_) { out_.swap(text_); return; } // (the bytes read so far are the start of the BAM stream)
+		SamHeader header;
+		while (!header.scan(text_.data(), text_.size(), end_)) more(4u << 20);
+		header.bam_header(text_.data(), out_);
+		targets_.build(header.names);
+		lines_ = header.lines;
+		text_.erase(text_.begin(), text_.begin() + header.bytes);
+	}
+	std::unique_ptr<ByteSource> inner_;
+	std::vector<uint8_t> text_, out_;
+	size_t served_;
+	bool sniffed_, sam_, end_;
+	uint64_t lines_;
+	SamTargetTable targets_;
+};
+}
+ByteSource* text_or_bam_source(ByteSource* inner) { return new TextOrBamSource(inner); }
+
 class BamFeed {
 public:
 	enum Mode { RAW, BGZF_STORED, BGZF_DEFLATED, GZIP };
@@ -1352,7 +1501,18 @@ public:
 				}
 			}
 			uint64_t size = 0;
-			if (parse_header(head, target_names, size)) {
+			const bool too_short = head.size() < 4; // (to tell BAM\1 from text: read more)
+			if (!too_short) sam_ = head_is_sam_text(head.data(), head.size()); // by content, never by the name of the file
+			if (too_short) {}
+			else if (sam_) {
+				if (sam_header_.scan(head.data(), head.size(), file_ended_)) {
+					target_names = sam_header_.names; n_targets_ = (uint32_t) target_names.size(); sorted_by_coordinate_ = sam_header_.sorted_by_coordinate;
+					sam_targets_.build(target_names);
+					sam_skip_ = sam_header_.bytes; sam_lines_ = sam_header_.lines; header_size_ = 0;
+					if (mode_ == BGZF_STORED) mode_ = BGZF_DEFLATED; // (compressed TEXT is inflated here, whatever its blocks are: the device takes text as it is)
+					return 0; // the stream the device gets holds records only
+				}
+			} else if (parse_header(head, target_names, size)) {
 				n_targets_ = (uint32_t) target_names.size(); header_size_ = size;
 				// BGZF: the file offset of the block that holds the first record, and where that record starts inside it
 				if (mode_ == BGZF_STORED || mode_ == BGZF_DEFLATED) {
@@ -1373,15 +1533,49 @@ public:
 			pending_.resize(before + (4u << 20));
 			const size_t got = file_.read(&pending_[before], pending_.size() - before);
 			pending_.resize(before + got);
-			if (got == 0) throw std::runtime_error("failed to read SAM header");
+			if (got == 0) { if (sam_ && !file_ended_) { file_ended_ = true; continue; } throw std::runtime_error("failed to read SAM header"); } // (a SAM file may be nothing but its header)
 		}
 	}
-	uint64_t stream_size_hint() const { return (mode_ == RAW || mode_ == BGZF_STORED) ? file_size_ + (1u << 20) : 0; }
+	bool is_sam_text() const { return sam_; }
+	const SamTargetTable& sam_targets() const { return sam_targets_; }
+	uint64_t stream_size_hint() const { return (mode_ == RAW || (mode_ == BGZF_STORED && !sam_)) ? file_size_ + (1u << 20) : 0; } // (SAM text: the records of a line are rarely larger than the line)
 
 	// the next piece; false at the end of the file.  kind 1: `buffer` holds raw BGZF bytes whose blocks are all stored, `blocks` their table
 	bool next(uint8_t* buffer, size_t capacity, agpu_bgzf_block* blocks, uint32_t block_capacity, ahost_bam_piece& piece) {
-		memset(&piece, 0, sizeof(piece));
 		if (capacity < (1u << 20)) throw std::runtime_error("piece buffer too small");
+		if (sam_) return next_sam(buffer, capacity, piece);
+		return next_of_container(buffer, capacity, blocks, block_capacity, piece);
+	}
+	// SAM text (piece kind 3): whole lines only -- what follows the last "\n" waits in sam_carry_ for the next piece -- and the number of the first line
+	bool next_sam(uint8_t* buffer, size_t capacity, ahost_bam_piece& piece) {
+		memset(&piece, 0, sizeof(piece));
+		size_t n = sam_carry_.size();
+		if (n > 0) memcpy(buffer, sam_carry_.data(), n);
+		sam_carry_.clear();
+		size_t whole = 0;
+		while (true) {
+			if (!sam_end_) {
+				if (capacity - n < (64u << 10)) throw std::runtime_error("failed to load alignments: a SAM line does not fit the piece buffer");
+				ahost_bam_piece inner;
+				if (!next_of_container(buffer + n, capacity - n, NULL, 0, inner)) sam_end_ = true;
+				size_t got = inner.bytes;
+				if (sam_skip_ > 0 && got > 0) { const size_t skip = (size_t) std::min<uint64_t>(sam_skip_, got); memmove(buffer + n, buffer + n + skip, got - skip); got -= skip; sam_skip_ -= skip; } // (the header lines)
+				n += got;
+			}
+			whole = n;
+			if (!sam_end_) while (whole > 0 && buffer[whole - 1] != '\n') --whole;
+			if (whole > 0 || sam_end_) break;
+		}
+		if (whole == 0) return false;
+		sam_carry_.assign(buffer + whole, buffer + n);
+		uint64_t lines = 0;
+		for (const uint8_t* at = buffer; at < buffer + whole; ) { const uint8_t* feed = (const uint8_t*) memchr(at, '\n', buffer + whole - at); ++lines; if (feed == NULL) break; at = feed + 1; }
+		piece.stored_bgzf = 3; piece.bytes = whole; piece.stream_bytes = 0; piece.first_line = sam_lines_ + 1;
+		sam_lines_ += lines;
+		return true;
+	}
+	bool next_of_container(uint8_t* buffer, size_t capacity, agpu_bgzf_block* blocks, uint32_t block_capacity, ahost_bam_piece& piece) {
+		memset(&piece, 0, sizeof(piece));
 		if (mode_ == RAW) {
 			size_t n = take_pending(buffer, capacity);
 			if (n < capacity && !end_) { const size_t got = file_.read(buffer + n, capacity - n); if (got == 0) end_ = true; n += got; }
@@ -1426,7 +1620,7 @@ public:
 		// BGZF_DEFLATED: the blocks go to the device as they are, with their table (piece.stored_bgzf = 2): bgzf_inflate_kernel makes the stream in HBM, a quarter of the bytes
 		// cross the link.  ARRIBA_HOST_INFLATE=1: inflated here by all threads instead (the way of rounds 2-3, kept for measurements and as the second implementation in the tests)
 		static const bool host_inflate = getenv("ARRIBA_HOST_INFLATE") != NULL && getenv("ARRIBA_HOST_INFLATE")[0] == '1';
-		if (!host_inflate) {
+		if (!host_inflate && !sam_) {
 			size_t n = take_pending(buffer, capacity);
 			if (n < capacity && !end_) { const size_t got = file_.read(buffer + n, capacity - n); if (got == 0) end_ = true; n += got; }
 			if (n == 0) return false;
@@ -1505,6 +1699,8 @@ public:
 	// Returns the offset of the first record of the part in the stream this feed delivers (the header size for part 0, else 0).
 	uint64_t take_part(uint32_t part, uint32_t parts) {
 		if (parts == 0 || part >= parts) throw std::runtime_error("part of the sample out of range");
+		if (sam_) throw std::runtime_error("a part of a sample can only be read from a BAM file: SAM text has no record sizes to find a record start by at an arbitrary offset of the file, "
+		                                   "so every rank would have to read all lines in front of its part -- convert the file with `samtools view -b`, or run it on one GPU");
 		if (!file_.seekable || mode_ == GZIP) throw std::runtime_error("a part of a sample can only be read from a BAM file on disk (BGZF or uncompressed): every rank opens the file at its own offset");
 		if (header_size_ == 0) throw std::runtime_error("the BAM header must be read first");
 		// told before any rank reads a byte of its part (the check of the read names behind the exchange of the parts would find it, too -- after every rank has ingested its part)
@@ -1734,6 +1930,10 @@ private:
 	z_stream gzip_;
 	bool gzip_open_, end_;
 	bool sorted_by_coordinate_ = false; // the header says SO:coordinate
+	bool sam_ = false, sam_end_ = false, file_ended_ = false; // the uncompressed stream is SAM text / has been delivered to its end / the file ended while the header was read
+	SamHeader sam_header_; SamTargetTable sam_targets_;
+	uint64_t sam_skip_ = 0, sam_lines_ = 0; // bytes of header lines still to drop from the stream; lines delivered so far (header lines included)
+	std::vector<uint8_t> sam_carry_;        // the incomplete line behind the last piece
 	uint32_t n_targets_;
 	uint64_t header_size_, header_raw_end_, header_inside_ = 0; // BGZF: file offset of the block that holds the first record, and the record's offset inside it
 	uint64_t consumed_raw_;                                    // file offset of the first byte the next piece starts with
@@ -1746,5 +1946,6 @@ uint64_t bam_feed_header(BamFeed* feed, std::vector<std::string>& target_names) 
 uint64_t bam_feed_size_hint(BamFeed* feed) { return feed->stream_size_hint(); }
 uint64_t bam_feed_take_part(BamFeed* feed, uint32_t part, uint32_t parts) { return feed->take_part(part, parts); }
 bool bam_feed_next(BamFeed* feed, uint8_t* buffer, size_t capacity, agpu_bgzf_block* blocks, uint32_t block_capacity, ahost_bam_piece& piece) { return feed->next(buffer, capacity, blocks, block_capacity, piece); }
+const SamTargetTable* bam_feed_sam_targets(BamFeed* feed) { return feed->is_sam_text() ? &feed->sam_targets() : NULL; }
 
 }

@@ -1,7 +1,8 @@
 // arriba_amd/csrc/workflow/main.cpp -- the command line of the reference (source/options.cpp:270-481: flags, defaults, checks and messages) in front of
 // arriba_workflow_run, so that run_arriba.sh can call this binary where it calls `arriba` (run_arriba.sh:42: STAR ... | arriba -x /dev/stdin -o ... -O ...).
-// Exit code 0 on success, 1 on any error ("ERROR: ..." on stderr, as crash() does in the reference).  Not supported and said so: -c (separate chimeric
-// SAM file of old STAR versions), SAM text and CRAM input, -@ (the threads of the BAM decompression are chosen by the ingest).
+// Exit code 0 on success, 1 on any error ("ERROR: ..." on stderr, as crash() does in the reference).  -x takes what sam_open takes but CRAM: BAM or SAM text (told by the
+// content, never by the name: a file, a pipe, /dev/stdin or -; plain, gzip or BGZF).  Not supported and said so: -c (separate chimeric SAM file of old STAR versions),
+// CRAM input (`samtools view -h x.cram | arriba_gpu_workflow -x /dev/stdin ...` reads one), -@ (the threads of the BAM decompression are chosen by the ingest).
 // The form `arriba_gpu_workflow assembly.fa annotation.gtf chimeric.bam fusions.tsv [discarded.tsv [...]]` of round 1 (no dash in front of the first
 // argument) is still understood.
 #include "../../../include/arriba_workflow.h"
@@ -50,7 +51,7 @@ void usage() {
 	std::cout << "arriba_gpu_workflow -- MI355X-native fusion caller with the command line and the output files of Arriba 2.5.1\n\n"
 	             "Usage: arriba_gpu_workflow -x Aligned.out.bam -g annotation.gtf -a assembly.fa -o fusions.tsv [-b blacklists.tsv] [-k known_fusions.tsv] [-t tags.tsv] [-p protein_domains.gff3]\n"
 	             "                           [-d structural_variants.tsv] [-O fusions.discarded.tsv] [OPTIONS]\n\n"
-	             " -x FILE  BAM file with the main alignments of STAR run with --chimOutType WithinBAM (BGZF, gzip or uncompressed; a file, a pipe, /dev/stdin or -)\n"
+	             " -x FILE  main alignments of STAR run with --chimOutType WithinBAM: BAM or SAM text, told by content (BGZF, gzip or uncompressed; a file, a pipe, /dev/stdin or -)\n"
 	             " -g FILE  gene annotation (GTF)        -a FILE  assembly (FastA)          -o FILE  output file             -O FILE  discarded fusions\n"
 	             " -b FILE  blacklist                    -k FILE  known fusions             -t FILE  tags                    -p FILE  protein domains (GFF3)\n"
 	             " -d FILE  structural variants from WGS -D INT   max. distance to them (100000)\n"
@@ -105,7 +106,7 @@ int main(int argc, char** argv) {
 			case 'c': crash("option -c (chimeric alignments in a separate SAM file, STAR < 2.5.3a) is not supported: run STAR with --chimOutType WithinBAM and pass the main BAM file with -x");
 			case 'x': {
 				const std::string path(optarg);
-				require(!(path.size() >= 5 && path.substr(path.size() - 5) == ".cram") && !(path.size() >= 4 && path.substr(path.size() - 4) == ".sam"), "only BAM input is supported (SAM text and CRAM are not): " + path);
+				require(!(path.size() >= 5 && path.substr(path.size() - 5) == ".cram"), "BAM and SAM text input are supported, CRAM is not (pipe it through `samtools view -h`): " + path);
 				options.chimeric_bam_file = optarg; readable(optarg); break;
 			}
 			case 'd': options.genomic_breakpoints_file = optarg; readable(optarg); break;

@@ -21,6 +21,11 @@
 #include <thread>
 #include <vector>
 
+// The two calls of the SAM text transcoder are weak references: the test-only build of this driver against the host stepping harness (tests/emu) has no twin of the
+// transcoder's kernels, links all the same, and says so if it is given SAM text.  The product links libarriba_gpu.so, which has them.
+extern "C" int agpu_ingest_sam_targets(agpu_ctx* ctx, const char* names, const uint32_t* name_offset, uint32_t n_targets) __attribute__((weak));
+extern "C" int agpu_ingest_push_sam(agpu_ctx* ctx, const void* text, size_t size, uint64_t first_line_number) __attribute__((weak));
+
 namespace {
 
 std::string g_error;
@@ -237,7 +242,16 @@ void feed_file(Run& run) {
 		ahost_bam_piece piece;
 		{ std::unique_lock<std::mutex> lock(feed.mutex); feed.changed.wait(lock, [&] { return feed.read > push || feed.at_end; }); if (feed.read <= push) break; piece = feed.pieces[push % buffers]; }
 		const double before = now_seconds();
-		if (piece.stored_bgzf) device_check(agpu_ingest_push_bgzf(run.device, run.pieces[push % buffers], piece.bytes, run.tables[push % buffers], piece.n_blocks, piece.stream_bytes));
+		if (piece.stored_bgzf == 3) { // lines of SAM text: transcoded to records on the device; the @SQ names they are looked up in go there once per ingest
+			if (push == 0) {
+				const char* names = nullptr; const uint32_t* name_offset = nullptr; uint32_t n_targets = 0;
+				if (ahost_bam_sam_targets(run.host, &names, &name_offset, &n_targets) != 1) throw Failure{ std::string("ERROR: ") + ahost_last_error() };
+				if (!agpu_ingest_sam_targets || !agpu_ingest_push_sam) throw Failure{ "ERROR: SAM text needs the transcoder of the device library (agpu_ingest_push_sam), which this build is not linked with" };
+				device_check(agpu_ingest_sam_targets(run.device, names, name_offset, n_targets));
+			}
+			device_check(agpu_ingest_push_sam(run.device, run.pieces[push % buffers], piece.bytes, piece.first_line));
+		}
+		else if (piece.stored_bgzf == 1 || piece.stored_bgzf == 2) device_check(agpu_ingest_push_bgzf(run.device, run.pieces[push % buffers], piece.bytes, run.tables[push % buffers], piece.n_blocks, piece.stream_bytes));
 		else device_check(agpu_ingest_push(run.device, run.pieces[push % buffers], piece.bytes));
 		pushing += now_seconds() - before;
 		{ std::lock_guard<std::mutex> lock(feed.mutex); feed.pushed = push + 1; }

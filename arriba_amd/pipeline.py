@@ -410,7 +410,16 @@ class DevicePipeline(object):
                     raise host_error()
                 if status == 0:
                     break
-                if piece.stored_bgzf:
+                if piece.stored_bgzf == _capi.PIECE_SAM_TEXT:
+                    if pushes == 0:  # the @SQ names the lines are looked up in: once per ingest
+                        names, offsets, n_targets = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_uint32()
+                        if lib.ahost_bam_sam_targets(handle, byref(names), byref(offsets), byref(n_targets)) != 1:
+                            raise host_error()
+                        if not hasattr(self.api, "ingest_push_sam"):
+                            raise ArribaError("ERROR: SAM text needs the transcoder of the device library (agpu_ingest_push_sam), which this library does not have")
+                        self._check(self.api.ingest_sam_targets(self.ctx, names, offsets, n_targets))
+                    self._check(self.api.ingest_push_sam(self.ctx, buffers[pushes & 1], piece.bytes, piece.first_line))
+                elif piece.stored_bgzf in (_capi.PIECE_STORED_BGZF, _capi.PIECE_DEFLATED_BGZF):
                     self._check(self.api.ingest_push_bgzf(self.ctx, buffers[pushes & 1], piece.bytes, tables[pushes & 1], piece.n_blocks, piece.stream_bytes))
                 else:
                     self._check(self.api.ingest_push(self.ctx, buffers[pushes & 1], piece.bytes))

@@ -242,6 +242,22 @@ int agpu_ingest_begin(agpu_ctx* ctx, const agpu_ingest_config* config);
 int agpu_ingest_push(agpu_ctx* ctx, const void* bytes, size_t size);
 int agpu_ingest_push_bgzf(agpu_ctx* ctx, const void* raw, size_t raw_size, const agpu_bgzf_block* blocks, uint32_t n_blocks, size_t stream_bytes);
 int agpu_ingest_finish(agpu_ctx* ctx, agpu_ingest_result* result);
+/* SAM text instead of BAM (sam_open reads both: source/read_chimeric_alignments.cpp:563): the lines are turned into the BAM records `samtools view -b` writes for them
+ * (SAMv1 section 4.2) on the device, in front of the ingest above (arriba_amd/csrc/device/agpu_sam.hip, sam_core.hpp), and appended to the stream; the stream holds records
+ * only (agpu_ingest_config.first_record_offset = 0; the host has read the header lines).
+ *   agpu_ingest_sam_targets   once, behind agpu_ingest_begin: the @SQ names in tid order -- names[name_offset[t] .. name_offset[t + 1]) -- which RNAME / RNEXT are looked up in
+ *   agpu_ingest_push_sam      the next piece of text: WHOLE lines only (the last line of the file may lack its "\n"; "\r\n" is taken as "\n"), less than 4 GiB;
+ *                             first_line_number: the 1-based number, in the file, of its first line.  Returns like the other pushes; it waits for two words from the device
+ *                             on the way (the number of lines, the size of their records), because the records of successive pieces must lie back to back.
+ * A malformed line (fewer than 11 fields, an empty line, an '@' line behind the first alignment, a bad number, an unknown reference name, a bad CIGAR, SEQ and QUAL of
+ * different length, a bad optional field) gives no record and does not stop the feed: the smallest line number and its reason are kept on the device, and
+ * agpu_ingest_finish fails with "failed to load alignments: SAM line N: <reason>".  The context is ready for the next agpu_ingest_begin.
+ *   agpu_sam_transcode        the same kernels over a caller's text (for tests and tools): '@' lines in front of the first alignment are skipped and counted; the records are
+ *                             copied to out[0 .. capacity).  AGPU_ERR_INVALID with *bad_line set if a line was malformed (the records of the others are still there), or if
+ *                             `out` is too small (*out_bytes then says what is needed).  Not while an ingest is under way on the context. */
+int agpu_ingest_sam_targets(agpu_ctx* ctx, const char* names, const uint32_t* name_offset, uint32_t n_targets);
+int agpu_ingest_push_sam(agpu_ctx* ctx, const void* text, size_t size, uint64_t first_line_number);
+int agpu_sam_transcode(agpu_ctx* ctx, const void* text, size_t size, const char* names, const uint32_t* name_offset, uint32_t n_targets, void* out, size_t capacity, uint64_t* out_bytes, uint64_t* n_records, uint64_t* bad_line);
 /* what the host's sequential stages and its output writer need from a batch that lives on the device:
  *   agpu_get_viral_read_counts   mapped_viral_reads_by_contig (source/read_chimeric_alignments.cpp:735-739)
  *   agpu_get_coverage            coverage_t as the reference holds it (16-bit saturating windows, start/end flags); sizes by coverage_window_offset

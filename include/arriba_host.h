@@ -25,7 +25,7 @@ const char* ahost_last_error(void);
 ahost_session* ahost_open(const char* fasta_path, const char* gtf_path, const char* interesting_contigs, const char* viral_contigs, const char* gtf_features);
 void ahost_close(ahost_session* session);
 
-/* read_chimeric_alignments for -x (source/read_chimeric_alignments.cpp:560-773); data = raw (inflated) BAM stream */
+/* read_chimeric_alignments for -x (source/read_chimeric_alignments.cpp:560-773); data = raw (inflated) BAM stream, or SAM text (told by content, as sam_open does) */
 int ahost_ingest_bam_file(ahost_session* session, const char* bam_path, int external_duplicate_marking, unsigned int max_itd_length);
 int ahost_ingest_bam_memory(ahost_session* session, const uint8_t* data, size_t size, int external_duplicate_marking, unsigned int max_itd_length);
 /* The result of an ingest (batch, counters, coverage) as a file, and back into a session opened on the same assembly and annotation: repeated
@@ -41,11 +41,15 @@ int ahost_load_ingest(ahost_session* session, const char* path);
  *   ahost_bam_next     the next piece into `buffer` (>= 1 MiB; pinned memory from agpu_host_alloc): stored_bgzf = 1: raw BGZF bytes whose blocks are
  *                      all stored, with the table of the blocks -> agpu_ingest_push_bgzf; 0: bytes of the uncompressed stream (deflated blocks inflated
  *                      by all cores, CRC-checked) -> agpu_ingest_push.  Returns 1, 0 at the end of the file, -1 on error.
+ *                      SAM text (the format is told by the content of the uncompressed head, never by the name of the file; plain, gzip or BGZF, inflated here):
+ *                      the header lines are read here -- @SQ SN/LN are the targets, @HD SO:coordinate the sort order -- config->first_record_offset is 0 and the pieces are
+ *                      of kind 3: whole lines only, first_line counting the header lines in -> agpu_ingest_push_sam, after ONE agpu_ingest_sam_targets with what
+ *                      ahost_bam_sam_targets returns.  ahost_bam_open_part refuses SAM text: text has no record sizes to find a record start by in the middle of the file.
  *   ahost_adopt_device_ingest   what the device found: the reference's checks and warnings behind its loop (:759-771: "no normal reads found", malformed
  *                      records, no chimeric reads, missing HI tags), the counters, and coverage_t (flat arrays in the order of config.coverage_window_offset)
  *   ahost_set_batch_rows   the rows of the batch the host itself works on (the output writer: names, CIGARs and sequences of the supporting reads), fetched
  *                      with agpu_gather_rows_*; fragment indices in an ahost_fusion_table then refer to these rows */
-typedef struct { int stored_bgzf; /* 0: the buffer holds bytes of the stream; 1: raw BGZF bytes whose blocks are stored, with their table; 2: raw BGZF bytes whose blocks are deflated, with their table (both: agpu_ingest_push_bgzf) */ size_t bytes; size_t stream_bytes; uint32_t n_blocks; } ahost_bam_piece;
+typedef struct { int stored_bgzf; /* the KIND of the piece (the name is from when there were two). 0: the buffer holds bytes of the stream; 1: raw BGZF bytes whose blocks are stored, with their table; 2: raw BGZF bytes whose blocks are deflated, with their table (both: agpu_ingest_push_bgzf); 3: whole lines of SAM text (agpu_ingest_push_sam; stream_bytes is 0: the size of their records is known on the device only) */ size_t bytes; size_t stream_bytes; uint32_t n_blocks; uint64_t first_line; /* kind 3: the 1-based number, in the file, of the first line of the piece */ } ahost_bam_piece;
 /* The processors this process may use at once (affinity, CPU quota of the cgroup), and a limit for every decision about a number of threads that is made on the calling thread
  * from now on (0: none): a session that feeds the next sample beside the stages of the current one and writes the last file beside both gives each of the three its share --
  * more busy threads than the quota has CPUs are all stopped together for the rest of the scheduler's period. */
@@ -59,6 +63,14 @@ int ahost_bam_open(ahost_session* session, const char* bam_path, int external_du
 int ahost_bam_open_part(ahost_session* session, const char* bam_path, int external_duplicate_marking, unsigned int max_itd_length, unsigned int part, unsigned int parts, agpu_ingest_config* config);
 int ahost_bam_next(ahost_session* session, void* buffer, size_t capacity, agpu_bgzf_block* blocks, uint32_t block_capacity, ahost_bam_piece* piece);
 void ahost_bam_close(ahost_session* session);
+/* 1: the file ahost_bam_open opened is SAM text -- names / name_offset [n_targets + 1] / n_targets are the @SQ names in tid order as agpu_ingest_sam_targets takes them (valid until
+ * ahost_bam_close); 0: it is BAM; -1: no file is open */
+int ahost_bam_sam_targets(ahost_session* session, const char** names, const uint32_t** name_offset, uint32_t* n_targets);
+/* Alignment lines of SAM text -> the BAM records `samtools view -b` writes for them (SAMv1 section 4.2), by arriba_amd/csrc/device/sam_core.hpp stepped on the host: the comparator of
+ * agpu_sam_transcode, and what the host ingest (ahost_ingest_bam_file / _memory, which take SAM text like BAM) runs.  text: whole lines, the last may lack its "\n"; '@' lines in front
+ * of the first alignment are skipped and counted.  names / name_offset [n_targets + 1]: the @SQ names in tid order.  Returns 0, or -1 with *bad_line = the 1-based number of the first
+ * malformed line (its record is left out; the others are still written) or when `out` is too small (*out_bytes then says how much is needed). */
+int ahost_sam_transcode(const void* text, size_t size, const char* names, const uint32_t* name_offset, uint32_t n_targets, void* out, size_t capacity, uint64_t* out_bytes, uint64_t* n_records, uint64_t* bad_line);
 int ahost_adopt_device_ingest(ahost_session* session, const agpu_ingest_result* result, const uint64_t* viral_read_counts, const uint16_t* coverage, const uint8_t* fragment_starts, const uint8_t* fragment_ends);
 int ahost_set_batch_rows(ahost_session* session, const agpu_batch_rows* rows, const uint32_t* fragments /* [rows->n] ascending: the fragment every row holds; NULL: row k holds the fragment
                          of entry k of the read lists of the table the next ahost_write_fusions writes (the reads of a candidate next to each other; the table then carries read_filter_of_rows) */);
