@@ -86,6 +86,17 @@ class IngestResult(ctypes.Structure):
                 ("names_were_sorted", c_uint8), ("windows", ctypes.c_uint16), ("reserved", c_uint8 * 4), ("stream_bytes", c_uint64)]
 
 
+class SortedBamInfo(ctypes.Structure):
+    """agpu_sorted_bam_info"""
+    _fields_ = [("records", c_uint64), ("uncompressed_bytes", c_uint64), ("file_bytes", c_uint64), ("windows", c_uint64), ("window_bytes", c_uint64)]
+
+
+class SortedBamIndex(ctypes.Structure):
+    """agpu_sorted_bam_index_arrays: the sizes, then the arrays of the BAI index"""
+    _fields_ = [("n_ref", c_uint32), ("n_chunks", c_uint64), ("n_intervals", c_uint64), ("n_no_coor", c_uint64)] + [
+        (name, c_void_p) for name in ("chunk_key", "chunk_begin", "chunk_end", "interval_offset", "intervals", "ref_begin", "ref_end", "ref_mapped", "ref_unmapped")]
+
+
 class BamPiece(ctypes.Structure):
     """ahost_bam_piece: stored_bgzf is the KIND of the piece -- 0 stream bytes, 1 stored BGZF, 2 deflated BGZF, 3 lines of SAM text (first_line: the number of its first line)"""
     _fields_ = [("stored_bgzf", c_int), ("bytes", c_size_t), ("stream_bytes", c_size_t), ("n_blocks", c_uint32), ("first_line", c_uint64)]
@@ -221,6 +232,10 @@ def bind_device_api(lib, prefix="agpu_"):
         "ingest_push_sam": (c_int, [ctx, c_void_p, c_size_t, c_uint64]),
         "sam_transcode": (c_int, [ctx, c_void_p, c_size_t, c_void_p, c_void_p, c_uint32, c_void_p, c_size_t, POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64)]),
         "ingest_finish": (c_int, [ctx, POINTER(IngestResult)]),
+        "sorted_bam_begin": (c_int, [ctx, POINTER(SortedBamInfo)]),
+        "sorted_bam_next": (c_int, [ctx, c_void_p, c_uint64, POINTER(c_uint64)]),
+        "sorted_bam_index": (c_int, [ctx, c_uint64, c_void_p, c_uint32, POINTER(SortedBamIndex)]),
+        "sorted_bam_end": (c_int, [ctx]),
         "shard_export_size": (c_int, [ctx, POINTER(c_uint64)]),
         "shard_export": (c_int, [ctx, c_void_p, c_uint64]),
         "shard_merge": (c_int, [ctx, c_void_p, c_uint64, c_uint32, POINTER(IngestResult)]),
@@ -295,6 +310,13 @@ def bind_host_api(lib):
         "ahost_bam_sam_targets": (c_int, [session, POINTER(c_void_p), POINTER(c_void_p), POINTER(c_uint32)]),
         "ahost_sam_transcode": (c_int, [c_void_p, c_size_t, c_void_p, c_void_p, c_uint32, c_void_p, c_size_t, POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64)]),
         "ahost_adopt_device_ingest": (c_int, [session, POINTER(IngestResult), c_void_p, c_void_p, c_void_p, c_void_p]),
+        "ahost_sorted_bam_header": (c_int, [session, POINTER(c_void_p), POINTER(c_uint64), POINTER(c_void_p), POINTER(c_uint32)]),
+        "ahost_sorted_bam_header_of": (c_int, [c_void_p, c_size_t, POINTER(c_void_p), POINTER(c_uint64), POINTER(c_void_p), POINTER(c_uint32)]),
+        "ahost_sorted_bam": (c_int, [c_void_p, c_size_t, c_uint64, c_void_p, c_uint32, POINTER(c_void_p), POINTER(SortedBamInfo), POINTER(SortedBamIndex)]),
+        "ahost_sorted_bam_write_index": (c_int, [POINTER(SortedBamIndex), c_char_p]),
+        "ahost_sorted_bam_eof": (None, [c_void_p]),
+        "ahost_sorted_bam_file": (c_int, [c_char_p, c_char_p, POINTER(SortedBamInfo)]),
+        "ahost_sorted_bam_write": (c_int, [c_void_p, c_size_t, c_void_p, c_size_t, c_char_p, POINTER(SortedBamInfo)]),
         "ahost_set_batch_rows": (c_int, [session, POINTER(BatchRows), c_void_p]),
         "ahost_fusion_table_reads": (c_int, [POINTER(FusionTable), c_int, c_void_p, c_uint64, POINTER(c_uint64)]),
         "ahost_read_length_sum_of": (c_float, [c_float, c_void_p, c_void_p, c_uint64]),
@@ -317,7 +339,7 @@ class WorkflowOptions(ctypes.Structure):
                                               "protein_domains_file", "genomic_breakpoints_file", "interesting_contigs", "viral_contigs", "gtf_features")] + [
         ("device", Params), ("min_itd_support", c_uint32), ("min_itd_allele_fraction", c_float), ("high_expression_quantile", c_float), ("min_spliced_events", c_uint32), ("min_anchor_length", c_uint32),
         ("max_homolog_identity", c_float), ("top_viral_contigs", c_uint32), ("viral_contig_min_covered_fraction", c_float), ("max_genomic_breakpoint_distance", c_int32),
-        ("print_extra_info_for_discarded_fusions", c_uint8), ("fill_sequence_gaps", c_uint8), ("device_index", c_int), ("log_to_stdout", c_uint8), ("host_ingest", c_uint8)]
+        ("print_extra_info_for_discarded_fusions", c_uint8), ("fill_sequence_gaps", c_uint8), ("device_index", c_int), ("log_to_stdout", c_uint8), ("host_ingest", c_uint8), ("sorted_bam_file", c_char_p)]
 
 
 class WorkflowStage(ctypes.Structure):
@@ -329,7 +351,7 @@ class WorkflowReport(ctypes.Structure):
 
 
 class WorkflowTiming(ctypes.Structure):
-    _fields_ = [(name, ctypes.c_double) for name in ("total", "feed", "ingest", "adopt", "stages", "filter_mismappers", "output", "output_results", "output_rows", "output_format", "feed_read", "feed_push", "feed_total", "exchange_parts", "exchange_verdicts", "exchange_rows", "shard_fragments", "exchanged_bytes")]
+    _fields_ = [(name, ctypes.c_double) for name in ("total", "feed", "ingest", "adopt", "stages", "filter_mismappers", "output", "output_results", "output_rows", "output_format", "feed_read", "feed_push", "feed_total", "exchange_parts", "exchange_verdicts", "exchange_rows", "shard_fragments", "exchanged_bytes", "sorted_bam")]
 
 
 WORKFLOW_MAX, WORKFLOW_MIN, WORKFLOW_SUM = 0, 1, 2
@@ -360,6 +382,7 @@ def workflow_library():
         lib.arriba_workflow_open.argtypes = [POINTER(WorkflowOptions)]; lib.arriba_workflow_open.restype = c_void_p
         lib.arriba_workflow_sample.argtypes = [c_void_p, c_char_p, c_char_p, c_char_p, POINTER(WorkflowReport), POINTER(WorkflowTiming)]; lib.arriba_workflow_sample.restype = c_int
         lib.arriba_workflow_submit.argtypes = [c_void_p, c_char_p]; lib.arriba_workflow_submit.restype = c_int
+        lib.arriba_workflow_sorted_bam.argtypes = [c_void_p, c_char_p]; lib.arriba_workflow_sorted_bam.restype = c_int
         lib.arriba_workflow_cancel.argtypes = [c_void_p]; lib.arriba_workflow_cancel.restype = c_int
         lib.arriba_workflow_defer_output.argtypes = [c_void_p, c_int]; lib.arriba_workflow_defer_output.restype = c_int
         lib.arriba_workflow_finish_ahead.argtypes = [c_void_p, c_int]; lib.arriba_workflow_finish_ahead.restype = c_int

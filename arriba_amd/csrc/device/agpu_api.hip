@@ -64,6 +64,7 @@ bool DeviceBuffer::release_idle_buffers() {
 		// (arriba_workflow_cancel) and runs the sample alone, where this function does help ("Memory").  The memo tables and task lists of filter_mismappers,
 		// the largest reservation, fall back to fewer workgroups by themselves (agpu_mismappers.hip)
 		if (ctx->pool.use_count() > 1) continue;
+		if (ctx->sorted_bam_active) continue; // (between agpu_sorted_bam_begin and _end the stream of the last ingest and the "sortedbam.*" buffers are in use)
 		(void) hipStreamSynchronize(ctx->stream);
 		if (!ctx->ingest_active && !ctx->ingest_finishing) { if (release_ingest_buffers(ctx)) released = true; }
 		else { // an ingest runs: nothing of the stages of the sample before is needed any more

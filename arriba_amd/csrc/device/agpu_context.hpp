@@ -179,6 +179,12 @@ struct agpu_ctx {
 	agpu::DeviceBuffer ingest_qname_keys; uint64_t ingest_qname_runs = 0; // a part of a sample: 128-bit keys of the runs of read names in its stream
 	agpu_ingest_result ingest_result; uint64_t ingest_pool_sizes[2] = { 0, 0 }; // what the last ingest (or merge of parts) reported; CIGAR words and sequence bytes of its pools
 	agpu::IngestProgress ingest_progress;
+	// --sorted-bam (agpu_sorted_bam.hip): the stream of the last ingest as agpu_ingest_finish left it (it zeroes ingest_stream_size) -- valid until the next agpu_ingest_begin on this
+	// context or its sibling; and where the output is between agpu_sorted_bam_begin and agpu_sorted_bam_end
+	uint64_t last_ingest_stream_size = 0, last_ingest_first_record = 0, last_ingest_records = 0;
+	bool last_ingest_kept = false, last_ingest_part_of_sample = false, sorted_bam_active = false, sorted_bam_index_ready = false;
+	uint64_t sorted_bam_records = 0, sorted_bam_bytes = 0, sorted_bam_blocks = 0, sorted_bam_window_blocks = 0, sorted_bam_next_block = 0, sorted_bam_gathered_block = ~0ull, sorted_bam_index_first = 0;
+	uint64_t sorted_bam_chunks = 0, sorted_bam_intervals = 0, sorted_bam_no_coor = 0; uint32_t sorted_bam_n_ref = 0;
 	// A pushed piece: copied on the context's stream (piece_copied: the caller's buffer is free), unwrapped and CRC-checked on a stream of its own (piece_stream; piece_ready: its
 	// bytes are in the stream, piece_done: the raw bytes are not needed any more), so that the copy of the next piece never waits for a kernel; AGPU_PIECE_SLOTS raw buffers in turn
 	hipStream_t piece_stream = nullptr, piece_stream2 = nullptr /* deflated pieces take the two in turn */; hipEvent_t piece_copied[AGPU_PIECE_SLOTS] = {}, piece_ready[AGPU_PIECE_SLOTS] = {}, piece_done[AGPU_PIECE_SLOTS] = {};

@@ -920,7 +920,10 @@ bool agpu::release_ingest_buffers(agpu_ctx* ctx) {
 	static const char* const temporary[] = { "ingest.record_offset", "ingest.keys", "ingest.keys_sorted", "ingest.record_bits", "ingest.sorted_records", "ingest.head", "ingest.group_start", "ingest.first_flags", "ingest.stream_rank", "ingest.group_first", "ingest.group_begin", "ingest.group_count", "ingest.plain_plans", "ingest.itd_plans",
 		"ingest.valid", "ingest.sizes", "ingest.refs", "ingest.order", "ingest.order_keys", "ingest.order_keys_sorted", "ingest.cigar_words", "ingest.sequence_bytes", "ingest.name_lengths", "ingest.new_group", "ingest.cigar_base",
 		"ingest.sequence_base", "ingest.name_base", "ingest.group_id", "ingest.qname_differs", "ingest.qname_run", "ingest.run_keys", "ingest.run_keys_sorted", "ingest.window_rocprim", "ingest.segment_first", "ingest.segment_end", "ingest.segment_end_before", "ingest.segment_count", "ingest.segment_base", "ingest.segment_mismatch", "ingest.rocprim", "ingest.coverage_summed", "ingest.hit_index",
-		"sam.wave_count", "sam.wave_base", "sam.line_start", "sam.record_size", "sam.record_offset", "sam.rocprim", "sam.tool_text", "sam.tool_records" };
+		"sam.wave_count", "sam.wave_base", "sam.line_start", "sam.record_size", "sam.record_offset", "sam.rocprim", "sam.tool_text", "sam.tool_records",
+		"sortedbam.keys", "sortedbam.keys_sorted", "sortedbam.order", "sortedbam.sizes", "sortedbam.sizes_sorted", "sortedbam.end_flag", "sortedbam.out_offset", "sortedbam.block_first", "sortedbam.staging", "sortedbam.rocprim", "sortedbam.crc_tables",
+		"sortedbam.ref_length", "sortedbam.interval_offset", "sortedbam.intervals", "sortedbam.ref_stats", "sortedbam.heads", "sortedbam.chunk_id", "sortedbam.chunk_key", "sortedbam.chunk_begin", "sortedbam.chunk_end", "sortedbam.chunk_key_sorted", "sortedbam.chunk_order", "sortedbam.chunk_out" };
+	ctx->last_ingest_kept = false; // (agpu_sorted_bam_begin says so instead of reading freed memory)
 	for (size_t k = 0; k < sizeof(temporary) / sizeof(temporary[0]); ++k) { DeviceBuffer& buffer = ctx->scratch(temporary[k]); if (buffer.ptr != nullptr) released = true; buffer.release(); }
 	return released;
 }
@@ -954,6 +957,7 @@ int agpu_ingest_begin(agpu_ctx* ctx, const agpu_ingest_config* config) {
 	}
 	if (config->host_buffers > AGPU_PIECE_SLOTS) { set_last_error("agpu_ingest_config.host_buffers: at most 4"); return AGPU_ERR_INVALID; }
 	ctx->ingest_host_buffers = config->host_buffers < 2 ? 2 : config->host_buffers;
+	ctx->last_ingest_kept = false; if (ctx->sibling) ctx->sibling->last_ingest_kept = false; // (the stream is written again from here on: no agpu_sorted_bam_begin of the sample before)
 	ctx->ingest_n_targets = config->n_targets; ctx->ingest_first_record = config->first_record_offset; ctx->ingest_stream_size = 0; ctx->ingest_pushes = 0; ctx->ingest_deflated_pieces = false; ctx->ingest_sam = false;
 	{ const char* knob = getenv("ARRIBA_VERIFY_CRC"); ctx->ingest_verify_crc = !(knob != nullptr && knob[0] == '0'); } // (the stored blocks are checked as htslib checks them; "0": a measurement without)
 	ALLOC(ctx->scratch("ingest.crc_mismatches"), 8); // [0] blocks whose payload does not give the CRC-32 of their trailer, [1] deflated blocks that did not decode (read whatever ARRIBA_VERIFY_CRC says)
@@ -1392,6 +1396,8 @@ int agpu_ingest_finish(agpu_ctx* ctx, agpu_ingest_result* result) {
 	// read lists and the batch behind them ~190 GB of the 288 GB are in use).  Only when an allocation fails are they given back (DeviceBuffer::release_idle_buffers); a part
 	// of a sample hands its windows on as they are (agpu_shard_export), everybody else is done with the 32-bit ones.
 	if (getenv("ARRIBA_RELEASE_INGEST_BUFFERS") != nullptr) agpu::release_ingest_buffers(ctx); // (for measurements: the behaviour of round 2 on samples that leave less than 160 GB free)
+	ctx->last_ingest_stream_size = size; ctx->last_ingest_first_record = base; ctx->last_ingest_records = n_records; ctx->last_ingest_part_of_sample = ctx->ingest_part_of_sample; // (for agpu_sorted_bam_begin)
+	ctx->last_ingest_kept = ctx->ingest_stream.ptr != nullptr && record_offset.ptr != nullptr;
 	ctx->ingest_stream_size = 0;
 	agpu_ingest_result& mine = ctx->ingest_result;
 	memset(&mine, 0, sizeof(mine));

@@ -232,6 +232,24 @@ uint64_t bam_feed_size_hint(BamFeed* feed);                                     
 const SamTargetTable* bam_feed_sam_targets(BamFeed* feed);                        // the @SQ names when the file is SAM text (its pieces are of kind 3), NULL for BAM
 bool bam_feed_next(BamFeed* feed, uint8_t* buffer, size_t capacity, agpu_bgzf_block* blocks, uint32_t block_capacity, ahost_bam_piece& piece);
 
+// --sorted-bam on the host (sorted_bam.cpp): the header of the output from the head of the input (a BAM header, or the '@' lines of SAM text), stored BGZF blocks, the records in
+// coordinate order with the arrays of the index (arriba_amd/csrc/device/sorted_bam_core.hpp stepped on the host), FILE.bai from those arrays, and the two files written
+struct SortedBam {
+	std::vector<uint8_t> blocks; // the record blocks
+	agpu_sorted_bam_info info;
+	bool indexed = false;
+	std::vector<uint64_t> chunk_key, chunk_begin, chunk_end, interval_offset, intervals, ref_begin, ref_end, ref_mapped, ref_unmapped;
+	uint64_t n_no_coor = 0;
+	agpu_sorted_bam_index_arrays view(uint32_t n_ref);
+};
+void sorted_bam_header(const uint8_t* input, size_t size, std::vector<uint8_t>& out, std::vector<uint32_t>& ref_length);
+void sorted_bam_frame(const uint8_t* bytes, uint64_t size, std::vector<uint8_t>& out);
+bool references_fit_bai(const uint32_t* ref_length, uint32_t n_ref);
+void sorted_bam_of(const uint8_t* records, uint64_t size, uint64_t first_block_file_offset, const uint32_t* ref_length /* NULL: no index */, uint32_t n_ref, SortedBam& result);
+void sorted_bam_bai(const agpu_sorted_bam_index_arrays& index, std::vector<uint8_t>& out);
+void sorted_bam_write(const uint8_t* input_header, size_t header_size, const uint8_t* records, uint64_t size, const std::string& path, agpu_sorted_bam_info* info);
+const std::vector<uint8_t>& bam_feed_header_bytes(BamFeed* feed); // the head of the uncompressed input as the feed read it: the BAM header, or the '@' lines of SAM text
+
 // reference: source/read_chimeric_alignments.cpp:560-773 with separate_chimeric_bam_file=false, is_rna_bam_file=true
 // gene_index must be the index over the GTF genes (before dummy genes are added).
 void read_chimeric_alignments(ByteSource& source, const Assembly& assembly, Contigs& contigs, const Annotation& annotation, const FlatIndex& gene_index, const IngestOptions& options, IngestResult& result);

@@ -23,6 +23,7 @@
 #include <tuple>
 #include <unordered_map>
 
+#include "../device/sorted_bam_core.hpp"
 using namespace arriba;
 
 namespace {
@@ -79,6 +80,7 @@ struct ahost_session {
 	bool rows_in_list_order = false;     // ... or row k holds the fragment of entry k of the read lists of the table written next (ahost_set_batch_rows without fragments)
 	std::vector<uint32_t> tid_to_contig;
 	std::vector<uint64_t> window_offset;
+	std::vector<uint8_t> input_header, sorted_bam_header_framed; std::vector<uint32_t> sorted_bam_ref_length; // --sorted-bam: the head of the file of the last ahost_bam_open; what ahost_sorted_bam_header made of it
 	~ahost_session() { if (feed) close_bam_feed(feed); }
 	std::map<std::pair<contig_t, contig_t>, bool> related_viruses;
 	std::string name_scratch;
@@ -518,6 +520,7 @@ int ahost_bam_open(ahost_session* session, const char* bam_path, int external_du
 		session->feed = open_bam_feed(bam_path);
 		std::vector<std::string> target_names;
 		const uint64_t header_size = bam_feed_header(session->feed, target_names);
+		session->input_header = bam_feed_header_bytes(session->feed);
 		// reference: source/read_chimeric_alignments.cpp:566-582 (contigs of the header join contigs_t; interesting contigs need a sequence)
 		session->tid_to_contig.resize(target_names.size());
 		for (size_t target = 0; target < target_names.size(); ++target) session->tid_to_contig[target] = session->contigs.add(target_names[target]);
@@ -579,6 +582,78 @@ int ahost_sam_transcode(const void* text, size_t size, const char* names, const 
 		if (records.size() > capacity) { g_error = "the buffer is too small for the records"; return -1; }
 		if (!records.empty()) memcpy(out, records.data(), records.size());
 		if (*bad_line != 0) { g_error = sam_line_error(*bad_line, reason); return -1; }
+		return 0;
+	} catch (const std::exception& e) { g_error = e.what(); return -1; }
+}
+
+// ---- --sorted-bam (include/arriba_host.h) ----
+namespace {
+inline uint32_t le32(const uint8_t* p) { return (uint32_t) p[0] | (uint32_t) p[1] << 8 | (uint32_t) p[2] << 16 | (uint32_t) p[3] << 24; }
+thread_local std::vector<uint8_t> g_sorted_header; thread_local std::vector<uint32_t> g_sorted_ref_length; thread_local SortedBam g_sorted_bam;
+void frame_header(const uint8_t* input, size_t size, std::vector<uint8_t>& framed, std::vector<uint32_t>& ref_length) {
+	std::vector<uint8_t> header;
+	sorted_bam_header(input, size, header, ref_length);
+	framed.clear();
+	sorted_bam_frame(header.data(), header.size(), framed);
+}
+}
+int ahost_sorted_bam_header(ahost_session* session, const uint8_t** framed, uint64_t* framed_bytes, const uint32_t** ref_length, uint32_t* n_ref) {
+	if (!session || !framed || !framed_bytes || !ref_length || !n_ref) { g_error = "null argument"; return -1; }
+	if (session->input_header.empty()) { g_error = "ahost_bam_open must run first"; return -1; }
+	try {
+		frame_header(session->input_header.data(), session->input_header.size(), session->sorted_bam_header_framed, session->sorted_bam_ref_length);
+		*framed = session->sorted_bam_header_framed.data(); *framed_bytes = session->sorted_bam_header_framed.size(); *ref_length = session->sorted_bam_ref_length.data(); *n_ref = (uint32_t) session->sorted_bam_ref_length.size();
+		return 0;
+	} catch (const std::exception& e) { g_error = e.what(); return -1; }
+}
+int ahost_sorted_bam_header_of(const void* input_header, size_t size, const uint8_t** framed, uint64_t* framed_bytes, const uint32_t** ref_length, uint32_t* n_ref) {
+	if (!input_header || !framed || !framed_bytes || !ref_length || !n_ref) { g_error = "null argument"; return -1; }
+	try {
+		frame_header((const uint8_t*) input_header, size, g_sorted_header, g_sorted_ref_length);
+		*framed = g_sorted_header.data(); *framed_bytes = g_sorted_header.size(); *ref_length = g_sorted_ref_length.data(); *n_ref = (uint32_t) g_sorted_ref_length.size();
+		return 0;
+	} catch (const std::exception& e) { g_error = e.what(); return -1; }
+}
+int ahost_sorted_bam(const void* records, size_t size, uint64_t first_block_file_offset, const uint32_t* ref_length, uint32_t n_ref, const uint8_t** blocks, agpu_sorted_bam_info* info, agpu_sorted_bam_index_arrays* index) {
+	if ((!records && size > 0) || !blocks || !info) { g_error = "null argument"; return -1; }
+	try {
+		sorted_bam_of((const uint8_t*) records, size, first_block_file_offset, index != NULL ? ref_length : NULL, n_ref, g_sorted_bam);
+		*blocks = g_sorted_bam.blocks.data(); *info = g_sorted_bam.info;
+		if (index != NULL) *index = g_sorted_bam.view(n_ref);
+		return 0;
+	} catch (const std::exception& e) { g_error = e.what(); return -1; }
+}
+int ahost_sorted_bam_write_index(const agpu_sorted_bam_index_arrays* index, const char* path) {
+	if (!index || !path) { g_error = "null argument"; return -1; }
+	try {
+		std::vector<uint8_t> bai;
+		sorted_bam_bai(*index, bai);
+		FILE* file = fopen(path, "wb");
+		if (file == NULL) throw std::runtime_error(std::string("failed to open '") + path + "' for writing");
+		const bool written = fwrite(bai.data(), 1, bai.size(), file) == bai.size();
+		if (fclose(file) != 0 || !written) { remove(path); throw std::runtime_error(std::string("failed to write '") + path + "'"); }
+		return 0;
+	} catch (const std::exception& e) { g_error = e.what(); return -1; }
+}
+void ahost_sorted_bam_eof(uint8_t* block) { for (uint32_t i = 0; i < agpu::SBAM_EOF_BYTES; ++i) block[i] = agpu::sbam_eof_byte(i); }
+int ahost_sorted_bam_write(const void* input_header, size_t header_size, const void* records, size_t size, const char* path, agpu_sorted_bam_info* info) {
+	if (!input_header || (!records && size > 0) || !path) { g_error = "null argument"; return -1; }
+	try { sorted_bam_write((const uint8_t*) input_header, header_size, (const uint8_t*) records, size, path, info); return 0; }
+	catch (const std::exception& e) { g_error = e.what(); return -1; }
+}
+int ahost_sorted_bam_file(const char* input_path, const char* path, agpu_sorted_bam_info* info) {
+	if (!input_path || !path) { g_error = "null argument"; return -1; }
+	try {
+		std::unique_ptr<ByteSource> source(text_or_bam_source(open_bam_file(input_path))); // (BGZF, gzip or raw; SAM text comes out as the BAM stream of its alignments)
+		std::vector<uint8_t> stream;
+		for (size_t got = 1; got > 0; ) { const size_t at = stream.size(); stream.resize(at + (16u << 20)); got = source->read(&stream[at], stream.size() - at); stream.resize(at + got); }
+		if (stream.size() < 12 || memcmp(stream.data(), "BAM\1", 4) != 0) throw std::runtime_error("failed to read SAM header");
+		uint64_t at = 8 + (uint64_t) le32(&stream[4]);
+		if (stream.size() < at + 4) throw std::runtime_error("failed to read SAM header");
+		const uint32_t n_ref = le32(&stream[at]);
+		at += 4;
+		for (uint32_t t = 0; t < n_ref; ++t) { if (stream.size() < at + 4) throw std::runtime_error("failed to read SAM header"); at += 8 + (uint64_t) le32(&stream[at]); if (stream.size() < at) throw std::runtime_error("failed to read SAM header"); }
+		sorted_bam_write(stream.data(), at, stream.data() + at, stream.size() - at, path, info);
 		return 0;
 	} catch (const std::exception& e) { g_error = e.what(); return -1; }
 }

@@ -1509,11 +1509,13 @@ public:
 					target_names = sam_header_.names; n_targets_ = (uint32_t) target_names.size(); sorted_by_coordinate_ = sam_header_.sorted_by_coordinate;
 					sam_targets_.build(target_names);
 					sam_skip_ = sam_header_.bytes; sam_lines_ = sam_header_.lines; header_size_ = 0;
+					header_bytes_.assign(head.begin(), head.begin() + sam_header_.bytes);
 					if (mode_ == BGZF_STORED) mode_ = BGZF_DEFLATED; // (compressed TEXT is inflated here, whatever its blocks are: the device takes text as it is)
 					return 0; // the stream the device gets holds records only
 				}
 			} else if (parse_header(head, target_names, size)) {
 				n_targets_ = (uint32_t) target_names.size(); header_size_ = size;
+				header_bytes_.assign(head.begin(), head.begin() + size);
 				// BGZF: the file offset of the block that holds the first record, and where that record starts inside it
 				if (mode_ == BGZF_STORED || mode_ == BGZF_DEFLATED) {
 					size_t raw_at = 0; uint64_t out_at = 0;
@@ -1538,6 +1540,7 @@ public:
 	}
 	bool is_sam_text() const { return sam_; }
 	const SamTargetTable& sam_targets() const { return sam_targets_; }
+	const std::vector<uint8_t>& header_bytes() const { return header_bytes_; }
 	uint64_t stream_size_hint() const { return (mode_ == RAW || (mode_ == BGZF_STORED && !sam_)) ? file_size_ + (1u << 20) : 0; } // (SAM text: the records of a line are rarely larger than the line)
 
 	// the next piece; false at the end of the file.  kind 1: `buffer` holds raw BGZF bytes whose blocks are all stored, `blocks` their table
@@ -1926,7 +1929,7 @@ private:
 	uint64_t file_size_;
 	unsigned int n_threads_;
 	Mode mode_;
-	std::vector<uint8_t> pending_, raw_;
+	std::vector<uint8_t> pending_, raw_, header_bytes_; // (header_bytes_: for the header of --sorted-bam)
 	z_stream gzip_;
 	bool gzip_open_, end_;
 	bool sorted_by_coordinate_ = false; // the header says SO:coordinate
@@ -1946,6 +1949,7 @@ uint64_t bam_feed_header(BamFeed* feed, std::vector<std::string>& target_names) 
 uint64_t bam_feed_size_hint(BamFeed* feed) { return feed->stream_size_hint(); }
 uint64_t bam_feed_take_part(BamFeed* feed, uint32_t part, uint32_t parts) { return feed->take_part(part, parts); }
 bool bam_feed_next(BamFeed* feed, uint8_t* buffer, size_t capacity, agpu_bgzf_block* blocks, uint32_t block_capacity, ahost_bam_piece& piece) { return feed->next(buffer, capacity, blocks, block_capacity, piece); }
+const std::vector<uint8_t>& bam_feed_header_bytes(BamFeed* feed) { return feed->header_bytes(); }
 const SamTargetTable* bam_feed_sam_targets(BamFeed* feed) { return feed->is_sam_text() ? &feed->sam_targets() : NULL; }
 
 }

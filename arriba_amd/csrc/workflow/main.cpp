@@ -63,7 +63,8 @@ void usage() {
 	             " -F INT fragment length for single-end data (200)   -U INT subsampling threshold (300)   -Q FLOAT high-expression quantile (0.998)   -e FLOAT exonic fraction (0.33)\n"
 	             " -T INT top viral contigs (5)   -C FLOAT min. covered fraction of a viral contig (0.05)   -l INT max. ITD length (100)   -z FLOAT min. ITD allele fraction (0.07)   -Z INT min. ITD support (10)\n"
 	             " -u duplicates are marked in the BAM file   -X extra columns for discarded fusions   -I fill gaps of the fusion transcript from the assembly   -h this text\n"
-	             " --device N  the GPU to use (0)            --host-ingest  read_chimeric_alignments on the host instead of on the GPU\n";
+	             " --device N  the GPU to use (0)            --host-ingest  read_chimeric_alignments on the host instead of on the GPU\n"
+	             " --sorted-bam FILE  the records of -x in coordinate order (BAM, stored BGZF blocks) and FILE.bai: what samtools sort + samtools index make of Aligned.out.bam\n";
 }
 
 }
@@ -85,10 +86,11 @@ int main(int argc, char** argv) {
 	std::cout << "[" << "arriba_gpu_workflow" << "] MI355X-native fusion caller (command line, progress lines and output files of Arriba 2.5.1)" << std::endl;
 	if (argc == 1) { usage(); crash("no arguments given"); }
 	require(argv[1][0] == '-' && argv[1][1] != '\0', std::string("cannot interpret the first argument: ") + argv[1]);
-	// the two long options of this implementation are taken out first; the rest is the reference's getopt string (source/options.cpp:282)
+	// the three long options of this implementation are taken out first; the rest is the reference's getopt string (source/options.cpp:282)
 	std::vector<char*> arguments(1, argv[0]);
 	for (int a = 1; a < argc; ++a) {
 		if (strcmp(argv[a], "--host-ingest") == 0) options.host_ingest = 1;
+		else if (strcmp(argv[a], "--sorted-bam") == 0 && a + 1 < argc) { options.sorted_bam_file = argv[++a]; parent_exists(options.sorted_bam_file); }
 		else if (strcmp(argv[a], "--device") == 0 && a + 1 < argc) { long device; require(parse_int(argv[++a], device) && device >= 0, "invalid argument to --device"); options.device_index = (int) device; }
 		else arguments.push_back(argv[a]);
 	}

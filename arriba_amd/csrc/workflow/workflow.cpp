@@ -25,6 +25,11 @@
 // transcoder's kernels, links all the same, and says so if it is given SAM text.  The product links libarriba_gpu.so, which has them.
 extern "C" int agpu_ingest_sam_targets(agpu_ctx* ctx, const char* names, const uint32_t* name_offset, uint32_t n_targets) __attribute__((weak));
 extern "C" int agpu_ingest_push_sam(agpu_ctx* ctx, const void* text, size_t size, uint64_t first_line_number) __attribute__((weak));
+// ... and so are the four calls of --sorted-bam
+extern "C" int agpu_sorted_bam_begin(agpu_ctx* ctx, agpu_sorted_bam_info* info) __attribute__((weak));
+extern "C" int agpu_sorted_bam_next(agpu_ctx* ctx, void* pinned, uint64_t capacity, uint64_t* bytes) __attribute__((weak));
+extern "C" int agpu_sorted_bam_index(agpu_ctx* ctx, uint64_t first_block_file_offset, const uint32_t* ref_length, uint32_t n_ref, agpu_sorted_bam_index_arrays* index) __attribute__((weak));
+extern "C" int agpu_sorted_bam_end(agpu_ctx* ctx) __attribute__((weak));
 
 namespace {
 
@@ -75,7 +80,8 @@ struct Run {
 	// read_chimeric_alignments in two halves (feed_file: the bytes of the file into HBM, on a thread of its own when the sample was submitted ahead; finish_device_ingest: what is
 	// left behind the last piece): what the first half leaves for the second
 	bool bam_open = false; uint64_t coverage_windows = 0; uint32_t bam_contigs = 0; double feed_started = 0, feed_finished = 0, feed_reading = 0, feed_pushing = 0;
-	std::string bam_path, output_path, discarded_path; // of the sample this lane works on (options.* point at them)
+	std::string bam_path, output_path, discarded_path, sorted_bam_path; // of the sample this lane works on (options.* point at them)
+	double sorted_bam_seconds = 0; // --sorted-bam of the sample at work
 	std::function<void()> after_ingest; // a session with two lanes: the stream and the tables of the ingest are free for the feed of the next sample
 	// arriba_workflow_finish_ahead: the second half ran on the feeder thread, before the caller asked for the sample; what it found is noted (report, timing) when the caller does
 	bool ingest_finished_ahead = false; uint64_t ingest_records = 0, ingest_stream_bytes = 0; double ingest_fed = 0, ingest_finished = 0, ingest_adopted = 0;
@@ -112,7 +118,7 @@ struct Run {
 	Run(const arriba_workflow_options& o): options(o), report(nullptr), timing(nullptr), host(nullptr), device(nullptr), dummy_genes(0), n_candidates(0), n_fragments(0), mapped_reads(0), device_ingest(false) {
 		for (int k = 0; k < FEED_BUFFERS; ++k) { pieces[k] = nullptr; tables[k] = nullptr; }
 		const char** texts[] = { &options.assembly_file, &options.gene_annotation_file, &options.chimeric_bam_file, &options.output_file, &options.discarded_output_file, &options.blacklist_file, &options.known_fusions_file,
-		                         &options.tags_file, &options.protein_domains_file, &options.genomic_breakpoints_file, &options.interesting_contigs, &options.viral_contigs, &options.gtf_features };
+		                         &options.tags_file, &options.protein_domains_file, &options.genomic_breakpoints_file, &options.interesting_contigs, &options.viral_contigs, &options.gtf_features, &options.sorted_bam_file };
 		strings.reserve(sizeof(texts) / sizeof(texts[0]));
 		for (size_t k = 0; k < sizeof(texts) / sizeof(texts[0]); ++k) if (*texts[k] != nullptr) { strings.push_back(*texts[k]); *texts[k] = strings.back().c_str(); }
 	}
@@ -191,6 +197,7 @@ void feed_file(Run& run) {
 	const arriba_workflow_options& o = run.options;
 	const double started = now_seconds();
 	run.feed_started = started;
+	if (run.ranks != nullptr && o.sorted_bam_file != nullptr) throw Failure{ "ERROR: a sorted BAM file of one sample over several GPUs is not supported" };
 	agpu_ingest_config config;
 	if (run.ranks != nullptr) host_check(ahost_bam_open_part(run.host, o.chimeric_bam_file, o.device.external_duplicate_marking, o.device.max_itd_length, run.ranks->rank, run.ranks->size, &config)); // this rank's part of the records
 	else host_check(ahost_bam_open(run.host, o.chimeric_bam_file, o.device.external_duplicate_marking, o.device.max_itd_length, &config));
@@ -412,6 +419,59 @@ bool shard_reads(Run& run, agpu_ingest_result& result, uint64_t windows, uint32_
 	return true;
 }
 
+// --sorted-bam: the records of the sample in coordinate order (BAM of stored BGZF blocks) and their BAI index, from the stream that is still in HBM behind agpu_ingest_finish
+// (include/arriba_gpu.h: agpu_sorted_bam_*; what run_arriba.sh:47-51 gets from samtools sort / index).  FILE.tmp and FILE.bai.tmp are renamed when both are complete; on a failure
+// they are removed and the sample fails with the message.  Windows come through two pinned buffers in turn: window k + 1 is gathered while window k is written.
+void write_sorted_bam(Run& run) {
+	const std::string path = run.options.sorted_bam_file, bam_tmp = path + ".tmp", bai_tmp = path + ".bai.tmp";
+	if (!agpu_sorted_bam_begin || !agpu_sorted_bam_next || !agpu_sorted_bam_index || !agpu_sorted_bam_end) throw Failure{ "ERROR: --sorted-bam needs the device library (agpu_sorted_bam_begin), which this build is not linked with" };
+	const double started = now_seconds();
+	agpu_sorted_bam_info info;
+	device_check(agpu_sorted_bam_begin(run.device, &info));
+	struct Ender { Run& run; ~Ender() { agpu_sorted_bam_end(run.device); } } ender = { run };
+	FILE* file = nullptr;
+	try {
+		const uint8_t* header = nullptr; uint64_t header_bytes = 0; const uint32_t* ref_length = nullptr; uint32_t n_ref = 0;
+		host_check(ahost_sorted_bam_header(run.host, &header, &header_bytes, &ref_length, &n_ref));
+		file = fopen(bam_tmp.c_str(), "wb");
+		if (file == nullptr) throw Failure{ "ERROR: failed to open '" + bam_tmp + "' for writing" };
+		auto put = [&](const void* bytes, size_t size) { if (size > 0 && fwrite(bytes, 1, size, file) != size) throw Failure{ "ERROR: failed to write '" + bam_tmp + "'" }; };
+		put(header, header_bytes);
+		uint8_t* windows[2] = { run.stage<uint8_t>("sorted_bam.window0", info.window_bytes), run.stage<uint8_t>("sorted_bam.window1", info.window_bytes) };
+		uint64_t written = 0;
+		for (unsigned int turn = 0; ; ++turn) {
+			uint64_t bytes = 0;
+			device_check(agpu_sorted_bam_next(run.device, windows[turn & 1], info.window_bytes, &bytes));
+			if (bytes == 0) break;
+			put(windows[turn & 1], bytes);
+			written += bytes;
+		}
+		if (written != info.file_bytes) throw Failure{ "ERROR: the record blocks of '" + path + "' do not have the size that was announced" };
+		uint8_t eof[28];
+		ahost_sorted_bam_eof(eof);
+		put(eof, sizeof(eof));
+		const int closed = fclose(file); file = nullptr;
+		if (closed != 0) throw Failure{ "ERROR: failed to write '" + bam_tmp + "'" };
+		bool indexed = true;
+		for (uint32_t t = 0; t < n_ref; ++t) if (ref_length[t] > (1u << 29)) indexed = false;
+		if (indexed) {
+			agpu_sorted_bam_index_arrays index; memset(&index, 0, sizeof(index));
+			device_check(agpu_sorted_bam_index(run.device, header_bytes, ref_length, n_ref, &index));
+			std::vector<uint64_t> chunks(3 * (size_t) index.n_chunks + 1), intervals((size_t) index.n_intervals + n_ref + 2), stats(4 * (size_t) n_ref + 1);
+			index.chunk_key = chunks.data(); index.chunk_begin = chunks.data() + index.n_chunks; index.chunk_end = chunks.data() + 2 * index.n_chunks;
+			index.interval_offset = intervals.data(); index.intervals = intervals.data() + n_ref + 1;
+			index.ref_begin = stats.data(); index.ref_end = stats.data() + n_ref; index.ref_mapped = stats.data() + 2 * (size_t) n_ref; index.ref_unmapped = stats.data() + 3 * (size_t) n_ref;
+			device_check(agpu_sorted_bam_index(run.device, header_bytes, ref_length, n_ref, &index));
+			host_check(ahost_sorted_bam_write_index(&index, bai_tmp.c_str()));
+		}
+		else std::cerr << "WARNING: a reference is longer than 2^29 bases, which a BAI index cannot address: '" << path << "' is written without '" << path << ".bai'" << std::endl;
+		if (rename(bam_tmp.c_str(), path.c_str()) != 0) throw Failure{ "ERROR: failed to write '" + path + "'" };
+		if (indexed && rename(bai_tmp.c_str(), (path + ".bai").c_str()) != 0) throw Failure{ "ERROR: failed to write '" + path + ".bai'" };
+	}
+	catch (...) { if (file) fclose(file); remove(bam_tmp.c_str()); remove(bai_tmp.c_str()); throw; }
+	run.sorted_bam_seconds = now_seconds() - started;
+}
+
 // ... and what is left of read_chimeric_alignments behind the last piece (agpu_ingest_finish), the counters, coverage_t and viral read counts back to the host session
 void finish_device_ingest(Run& run, double waited_since) {
 	struct Closer { Run& run; ~Closer() { if (run.bam_open) { ahost_bam_close(run.host); run.bam_open = false; } } } closer = { run };
@@ -419,6 +479,8 @@ void finish_device_ingest(Run& run, double waited_since) {
 	const double fed = now_seconds();
 	agpu_ingest_result result;
 	together(run.ranks, [&] { device_check(agpu_ingest_finish(run.device, &result)); });
+	run.sorted_bam_seconds = 0;
+	if (run.options.sorted_bam_file != nullptr) write_sorted_bam(run); // (before after_ingest: in a session of two lanes the stream belongs to the next feed after that)
 	run.sharded = false; run.first_rank = 0; run.exchanged_bytes = 0;
 	if (run.ranks != nullptr && !shard_reads(run, result, windows, n_contigs)) exchange_parts(run, result);
 	if (!run.sharded) run.local_fragments = result.fragments;
@@ -443,6 +505,7 @@ void note_device_ingest(Run& run, double waited_since) {
 		if (run.ingest_finished_ahead) { run.timing->feed = now_seconds() - waited_since; run.timing->ingest = 0; run.timing->adopt = 0; } // (all of it beside the sample in front: what is left is the wait for it)
 		else { run.timing->feed = run.ingest_fed - waited_since; run.timing->ingest = run.ingest_finished - run.ingest_fed; run.timing->adopt = run.ingest_adopted - run.ingest_finished; }
 	}
+	if (run.timing) run.timing->sorted_bam = run.sorted_bam_seconds; // (inside `ingest`, or beside the sample in front when the ingest was finished ahead)
 	run.note("bam_records", run.ingest_records); // (for the report only: no line of the reference's log)
 	run.note("bam_stream_bytes", run.ingest_stream_bytes);
 }
@@ -1005,6 +1068,7 @@ void run_sample(Run& run, bool already_fed, double sample_started) {
 	else {
 		if (run.ranks != nullptr) throw Failure{ "ERROR: one sample over several ranks needs read_chimeric_alignments on the device (host_ingest = 0): the parts of the batch are exchanged in device format" };
 		host_check(ahost_ingest_bam_file(run.host, o.chimeric_bam_file, o.device.external_duplicate_marking, o.device.max_itd_length));
+		if (o.sorted_bam_file != nullptr) { const double before = now_seconds(); host_check(ahost_sorted_bam_file(o.chimeric_bam_file, o.sorted_bam_file, nullptr)); if (run.timing) run.timing->sorted_bam = now_seconds() - before; } // (the host's stepping of the same code)
 		device_check(agpu_upload_genome(run.device, ahost_genome_view(run.host)));
 		device_check(agpu_upload_batch(run.device, ahost_batch_view(run.host)));
 		run.n_fragments = ahost_batch_view(run.host)->n;
@@ -1189,10 +1253,11 @@ int arriba_workflow_run(const arriba_workflow_options* options, arriba_workflow_
 struct arriba_workflow_session {
 	Run* lanes[2];
 	int processed_lane = 0; // of the sample arriba_workflow_sample worked on last
-	struct Submitted { std::string bam; int lane = 0; std::thread feeder; bool fed = false, ingest_finished = false, started = false; std::string error; int error_code = 0; };
+	struct Submitted { std::string bam, sorted_bam; int lane = 0; std::thread feeder; bool fed = false, ingest_finished = false, started = false; std::string error; int error_code = 0; };
 	std::deque<std::unique_ptr<Submitted>> queue; // oldest first; at most two
 	std::mutex mutex; std::condition_variable changed;
 	bool ingest_busy = false; // a lane is between agpu_ingest_begin and agpu_ingest_finish
+	std::string next_sorted_bam; // arriba_workflow_sorted_bam: of the sample that is submitted next
 	bool defer_output = false;
 	bool retrying = false; // arriba_workflow_sample runs a sample again after the device ran out of memory with two lanes (below)
 	bool finish_ahead = false; // arriba_workflow_finish_ahead: the feeder of a sample also finishes its ingest (the lanes keep their batch buffers)
@@ -1256,10 +1321,11 @@ struct arriba_workflow_session {
 		}
 		Run& run = *lanes[lane];
 		run.bam_path = bam; run.options.chimeric_bam_file = run.bam_path.c_str();
+		run.sorted_bam_path.swap(next_sorted_bam); next_sorted_bam.clear(); run.options.sorted_bam_file = run.sorted_bam_path.empty() ? nullptr : run.sorted_bam_path.c_str();
 		run.timing = nullptr; run.report = nullptr;
 		prepare_sample(run);
 		std::unique_ptr<Submitted> sample(new Submitted());
-		sample->bam = bam; sample->lane = lane;
+		sample->bam = bam; sample->sorted_bam = run.sorted_bam_path; sample->lane = lane;
 		Submitted* mine = sample.get();
 		{ std::lock_guard<std::mutex> lock(mutex); queue.push_back(std::move(sample)); }
 		if (!run.device_ingest) { join_writer_of(lane); std::lock_guard<std::mutex> lock(mutex); mine->fed = true; return; } // (the host ingest reads the file inside arriba_workflow_sample)
@@ -1293,6 +1359,12 @@ arriba_workflow_session* arriba_workflow_open(const arriba_workflow_options* opt
 	catch (const std::exception& e) { g_error = std::string("ERROR: ") + e.what(); }
 	delete session;
 	return nullptr;
+}
+
+int arriba_workflow_sorted_bam(arriba_workflow_session* session, const char* sorted_bam_file) {
+	if (!session) { g_error = "ERROR: null argument"; return -1; }
+	session->next_sorted_bam = sorted_bam_file ? sorted_bam_file : "";
+	return 0;
 }
 
 int arriba_workflow_submit(arriba_workflow_session* session, const char* chimeric_bam_file) {
@@ -1343,7 +1415,7 @@ int arriba_workflow_sample(arriba_workflow_session* session, const char* chimeri
 	}
 	catch (const Failure& failure) { g_error = failure.text; g_error_code = failure.code; status = -1; }
 	catch (const std::exception& e) { g_error = std::string("ERROR: ") + e.what(); g_error_code = 0; status = -1; }
-	if (lane) { lane->after_ingest = nullptr; lane->before_host_writer = nullptr; lane->options.chimeric_bam_file = nullptr; lane->options.output_file = nullptr; lane->options.discarded_output_file = nullptr; lane->report = nullptr; lane->timing = nullptr; session->processed_lane = (int) (lane == session->lanes[1]); }
+	if (lane) { lane->after_ingest = nullptr; lane->before_host_writer = nullptr; lane->options.chimeric_bam_file = nullptr; lane->options.sorted_bam_file = nullptr; lane->options.output_file = nullptr; lane->options.discarded_output_file = nullptr; lane->report = nullptr; lane->timing = nullptr; session->processed_lane = (int) (lane == session->lanes[1]); }
 	// The device ran out of memory while the session had two lanes (advisor, round 4): their contexts share one pool of scratch buffers, of which nothing is idle while one lane
 	// feeds and the other runs its stages, so the device library gives nothing back by itself (DeviceBuffer::release_idle_buffers).  The session does what INTEGRATION.md ("Memory")
 	// used to ask of the caller: what was fed ahead is thrown away, the second lane is closed -- the pool belongs to one context again, which gives back what it keeps for its next
@@ -1351,6 +1423,7 @@ int arriba_workflow_sample(arriba_workflow_session* session, const char* chimeri
 	if (status != 0 && lane != nullptr && !session->retrying && !session->over_ranks && session->lanes[1] != nullptr && g_error_code == AGPU_ERR_NO_MEMORY) { // (the status code of the device library, not a word of its message: review of round 5)
 		const std::string first_error = g_error;
 		const std::string behind = session->queue.empty() ? std::string() : session->queue.front()->bam;
+		const std::string behind_sorted_bam = session->queue.empty() ? std::string() : session->queue.front()->sorted_bam, again_sorted_bam = lane->sorted_bam_path;
 		session->drain();
 		session->join_writer_of(0); session->join_writer_of(1);
 		// (an I/O error on the deferred file of an EARLIER sample stays noted -- advisor, round 5: it was dropped here, and the caller never learnt that the file is incomplete -- and is
@@ -1359,10 +1432,11 @@ int arriba_workflow_sample(arriba_workflow_session* session, const char* chimeri
 		delete session->lanes[1]; session->lanes[1] = nullptr; session->processed_lane = 0;
 		fprintf(stderr, "arriba_workflow_sample: %s -- with two samples in flight; '%s' is run again with the device to itself\n", first_error.c_str(), chimeric_bam_file);
 		session->retrying = true;
+		session->next_sorted_bam = again_sorted_bam;
 		status = arriba_workflow_sample(session, chimeric_bam_file, output_file, discarded_output_file, report, timing);
 		session->retrying = false;
 		if (status == 0 && !behind.empty()) { // (as its caller submitted it: a failure to feed it is reported by the call that asks for it)
-			try { session->submit(behind.c_str()); }
+			try { session->next_sorted_bam = behind_sorted_bam; session->submit(behind.c_str()); }
 			catch (const Failure&) {} catch (const std::exception&) {}
 		}
 	}

@@ -153,8 +153,10 @@ class WorkflowSession(object):
         self.timings, self._profiling_on, self.ingest_result = {}, False, None  # (what bench.py reads from a DevicePipeline)
         self._profiled = set()
 
-    def submit(self, bam):
-        """the sample that comes after the one `sample` is called for next: its file is fed (PCIe, the front of read_chimeric_alignments) while the stages of that one run"""
+    def submit(self, bam, sorted_bam_file=None):
+        """the sample that comes after the one `sample` is called for next: its file is fed (PCIe, the front of read_chimeric_alignments) while the stages of that one run;
+        sorted_bam_file: its records in coordinate order with their index (--sorted-bam), written when its ingest is finished"""
+        self._lib.arriba_workflow_sorted_bam(self._session, sorted_bam_file.encode() if sorted_bam_file else None)
         if self._lib.arriba_workflow_submit(self._session, bam.encode()) != 0:
             raise ArribaError(self._lib.arriba_workflow_last_error().decode())
         if self._profiling_on:
@@ -249,9 +251,12 @@ class WorkflowSession(object):
     def _lane_contexts(self):
         return [ctx for ctx in (self._lib.arriba_workflow_lane_device(self._session, lane) for lane in (0, 1)) if ctx]
 
-    def sample(self, bam, output_file, discarded_output_file=None):
-        """one sample, BAM file -> fusions.tsv (and discarded.tsv); returns the stages with their "(remaining=N)" counts"""
+    def sample(self, bam, output_file, discarded_output_file=None, sorted_bam_file=None):
+        """one sample, BAM file -> fusions.tsv (and discarded.tsv); returns the stages with their "(remaining=N)" counts.  sorted_bam_file (--sorted-bam): for a sample that was
+        not submitted ahead; one that was says it to `submit`"""
         report, timing = _capi.WorkflowReport(), _capi.WorkflowTiming()
+        if sorted_bam_file:
+            self._lib.arriba_workflow_sorted_bam(self._session, sorted_bam_file.encode())
         if self._lib.arriba_workflow_sample(self._session, bam.encode(), output_file.encode(), discarded_output_file.encode() if discarded_output_file else None, byref(report), byref(timing)) != 0:
             raise ArribaError(self._lib.arriba_workflow_last_error().decode())
         self.ctx = self._lib.arriba_workflow_device(self._session)  # (the lane that worked on this sample)
@@ -356,6 +361,7 @@ class DevicePipeline(object):
     def close(self):
         if self.ctx:
             self._free_pieces()
+            self._free_sorted_windows()
             self.api.destroy(self.ctx)
             self.ctx = None
 
@@ -451,6 +457,91 @@ class DevicePipeline(object):
         self.n_dummy_genes = 0
         self.scalars = {}
         return self.n
+
+    MAX_BAI_REFERENCE = 1 << 29
+
+    def write_sorted_bam(self, path):
+        """The records of the file of the last read_chimeric_alignments in coordinate order as `path` (BAM of stored BGZF blocks) and `path`.bai -- what run_arriba.sh:47-51 gets
+        from `samtools sort` / `samtools index` -- from the record stream that is still in HBM (agpu_sorted_bam_*).  Valid after read_chimeric_alignments and before the next one.
+        Written through `path`.tmp / `path`.bai.tmp; returns {"records", "uncompressed_bytes", "file_bytes", "windows", "indexed"}; the seconds of its parts: self.sorted_bam_seconds."""
+        import os
+        import sys
+        import time
+        if not self.device_ingest or not hasattr(self.api, "sorted_bam_begin"):
+            raise ArribaError("ERROR: a sorted BAM file needs the record stream of an ingest on the device (DevicePipeline(bam=...))")
+        lib, handle = self.session._lib, self.session._session
+        started = time.perf_counter()
+        info = _capi.SortedBamInfo()
+        self._check(self.api.sorted_bam_begin(self.ctx, byref(info)))  # (refused before anything is written: the stream given back, another ingest begun, a part of a sample)
+        sorted_at = time.perf_counter()
+        seconds = {"sort": sorted_at - started, "gather_and_copy": 0.0, "write": 0.0, "index": 0.0}
+        temporaries = [path + ".tmp", path + ".bai.tmp"]
+        try:
+            framed, framed_bytes, lengths, n_ref = ctypes.c_void_p(), c_uint64(), ctypes.c_void_p(), ctypes.c_uint32()
+            if lib.ahost_sorted_bam_header(handle, byref(framed), byref(framed_bytes), byref(lengths), byref(n_ref)) != 0:
+                raise ArribaError("ERROR: " + lib.ahost_last_error().decode())
+            ref_length = np.ctypeslib.as_array(ctypes.cast(lengths, ctypes.POINTER(ctypes.c_uint32)), (n_ref.value,)).copy() if n_ref.value else np.zeros(0, np.uint32)
+            # two pinned buffers in turn: they stay with the pipeline, as the pieces of the feed do
+            if getattr(self, "_sorted_windows", None) is None or self._sorted_windows[0] < info.window_bytes:
+                self._free_sorted_windows()
+                buffers = [self.api.host_alloc(info.window_bytes) for _ in range(2)]
+                self._sorted_windows = (info.window_bytes, buffers)
+                if not all(buffers):
+                    self._free_sorted_windows()
+                    raise ArribaError("ERROR: " + self.api.last_error().decode())
+            capacity, buffers = self._sorted_windows
+            with open(temporaries[0], "wb") as out:
+                out.write(ctypes.string_at(framed, framed_bytes.value))
+                got, turn, written = c_uint64(), 0, 0
+                while True:
+                    before = time.perf_counter()
+                    self._check(self.api.sorted_bam_next(self.ctx, buffers[turn & 1], capacity, byref(got)))
+                    middle = time.perf_counter()
+                    seconds["gather_and_copy"] += middle - before
+                    if got.value == 0:
+                        break
+                    out.write((ctypes.c_char * got.value).from_address(buffers[turn & 1]))
+                    seconds["write"] += time.perf_counter() - middle
+                    written += got.value
+                    turn += 1
+                if written != info.file_bytes:
+                    raise ArribaError("ERROR: the record blocks of the sorted BAM file have %d bytes, %d were announced" % (written, info.file_bytes))
+                eof = ctypes.create_string_buffer(28)
+                lib.ahost_sorted_bam_eof(eof)
+                out.write(eof.raw)
+            indexed = bool((ref_length <= self.MAX_BAI_REFERENCE).all())
+            if indexed:
+                before = time.perf_counter()
+                index = _capi.SortedBamIndex()
+                self._check(self.api.sorted_bam_index(self.ctx, framed_bytes.value, ref_length.ctypes.data, n_ref.value, byref(index)))
+                arrays = {name: np.zeros(max(size, 1), np.uint64) for name, size in (("chunk_key", index.n_chunks), ("chunk_begin", index.n_chunks), ("chunk_end", index.n_chunks), ("interval_offset", n_ref.value + 1),
+                                                                                    ("intervals", index.n_intervals), ("ref_begin", n_ref.value), ("ref_end", n_ref.value), ("ref_mapped", n_ref.value), ("ref_unmapped", n_ref.value))}
+                for name, array in arrays.items():
+                    setattr(index, name, array.ctypes.data)
+                self._check(self.api.sorted_bam_index(self.ctx, framed_bytes.value, ref_length.ctypes.data, n_ref.value, byref(index)))
+                if lib.ahost_sorted_bam_write_index(byref(index), temporaries[1].encode()) != 0:
+                    raise ArribaError("ERROR: " + lib.ahost_last_error().decode())
+                seconds["index"] = time.perf_counter() - before
+            else:
+                sys.stderr.write("WARNING: a reference is longer than 2^29 bases, which a BAI index cannot address: '%s' is written without '%s.bai'\n" % (path, path))
+            os.replace(temporaries[0], path)
+            if indexed:
+                os.replace(temporaries[1], path + ".bai")
+        finally:
+            for temporary in temporaries:
+                if os.path.exists(temporary):
+                    os.remove(temporary)
+            self.api.sorted_bam_end(self.ctx)
+        seconds["total"] = time.perf_counter() - started
+        self.sorted_bam_seconds = seconds
+        return {"records": int(info.records), "uncompressed_bytes": int(info.uncompressed_bytes), "file_bytes": int(info.file_bytes), "windows": int(info.windows), "indexed": indexed}
+
+    def _free_sorted_windows(self):
+        if getattr(self, "_sorted_windows", None) is not None:
+            for pointer in self._sorted_windows[1]:
+                if pointer:
+                    self.api.host_free(pointer)
+            self._sorted_windows = None
 
     def batch_rows(self, fragments=None):
         """rows of the batch on the device as numpy arrays (fragments=None: all) -- what agpu_gather_rows_* hands to the host's writer; also the test's view of a batch built on the device"""
@@ -585,11 +676,13 @@ class DevicePipeline(object):
                      max_genomic_breakpoint_distance=100000, strandedness=None, evalue_cutoff=0.3,
                      min_itd_support=10, min_itd_allele_fraction=0.07, high_expression_quantile=0.998, min_spliced_events=4, min_anchor_length=23,
                      max_homolog_identity=0.3, max_itd_length=100, fill_sequence_gaps=False, top_viral_contigs=5, viral_contig_min_covered_fraction=0.05,
-                     print_extra_info_for_discarded_fusions=False, log=None):
+                     print_extra_info_for_discarded_fusions=False, log=None, sorted_bam_file=None):
         """The reference's main() behind read_chimeric_alignments (source/arriba.cpp:119-610) with its default parameters: the read-level cascade, find_fusions,
         every candidate-level filter in the reference's order, assign_confidence, and the two output files.  `log` receives (stage, remaining) pairs --
         the numbers the reference prints as "(remaining=N)".  Filters switched off with -f are skipped by the stages themselves (agpu_params.filter_enabled)."""
         note = log if log is not None else (lambda stage, remaining: None)
+        if sorted_bam_file:  # first: the record stream is still in HBM (it is given back when the stages need the memory)
+            self.write_sorted_bam(sorted_bam_file)
         self.run_read_level(strandedness, top_viral_contigs, viral_contig_min_covered_fraction)
         note("find_fusions", self.find_fusions())
         self.upload_coverage()

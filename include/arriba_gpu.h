@@ -258,6 +258,45 @@ int agpu_ingest_finish(agpu_ctx* ctx, agpu_ingest_result* result);
 int agpu_ingest_sam_targets(agpu_ctx* ctx, const char* names, const uint32_t* name_offset, uint32_t n_targets);
 int agpu_ingest_push_sam(agpu_ctx* ctx, const void* text, size_t size, uint64_t first_line_number);
 int agpu_sam_transcode(agpu_ctx* ctx, const void* text, size_t size, const char* names, const uint32_t* name_offset, uint32_t n_targets, void* out, size_t capacity, uint64_t* out_bytes, uint64_t* n_records, uint64_t* bad_line);
+/* ---- the records of the last ingest in coordinate order, as a BAM file of stored BGZF blocks with its BAI index (what run_arriba.sh:47-51 gets from `samtools sort` and
+ * `samtools index` behind the call of arriba; SAMv1 sections 4.1, 4.2, 5.2).  The stream and the offsets of its records stay in HBM behind agpu_ingest_finish; the sort key is
+ * samtools': refID as unsigned (-1 last), pos + 1, the reverse-strand flag, ties in input order; records are moved byte for byte (arriba_amd/csrc/device/agpu_sorted_bam.hip,
+ * sorted_bam_core.hpp).  The file is: the header in BGZF blocks of its own (the host's: ahost_sorted_bam_header), the record blocks -- 0xff00 payload bytes each, the last one
+ * shorter, payload + 31 bytes per block -- and the 28-byte end-of-file block.
+ *   agpu_sorted_bam_begin   behind agpu_ingest_finish, before the next agpu_ingest_begin on this context or its sibling: keys, stable sort, scan of the sizes; info: what follows.
+ *                           AGPU_ERR_INVALID if the stream or the record offsets have been given back to the device (memory pressure), or for a part of a sample.
+ *   agpu_sorted_bam_next    the next window of finished record blocks (a whole number of blocks, info.window_bytes at most) into pinned[0 .. capacity); *bytes == 0 at the end.  The
+ *                           window after it is gathered while the caller writes this one: take two pinned buffers in turn.
+ *   agpu_sorted_bam_index   the index arrays, for record blocks that begin at first_block_file_offset of the file; call with the pointers of `index` NULL for the sizes, then
+ *                           with arrays of those sizes (as agpu_get_candidate_read_lists_of does).  AGPU_ERR_INVALID if a reference is longer than 2^29 bases (BAI cannot address it).
+ *   agpu_sorted_bam_end     the context is where it was before agpu_sorted_bam_begin; the scratch buffers ("sortedbam.*") stay for the next sample, as the ingest's do
+ * ARRIBA_SORTED_BAM_WINDOW: bytes of the device staging buffer of a window (default 256 MiB, rounded down to whole blocks, at least one). */
+typedef struct {
+	uint64_t records;             /* records of the stream */
+	uint64_t uncompressed_bytes;  /* their bytes */
+	uint64_t file_bytes;          /* bytes of the record blocks in the file: uncompressed_bytes + 31 per block */
+	uint64_t windows;             /* calls of agpu_sorted_bam_next that return bytes */
+	uint64_t window_bytes;        /* capacity a window needs */
+} agpu_sorted_bam_info;
+typedef struct {
+	uint32_t n_ref;               /* as given */
+	uint64_t n_chunks;            /* runs of consecutive records of the file with one (reference, bin), grouped by (reference, bin) */
+	uint64_t n_intervals;         /* 16 kb windows of all references: sum of (length + 16383) >> 14 */
+	uint64_t n_no_coor;           /* records with refID < 0 */
+	uint64_t* chunk_key;          /* [n_chunks] reference << 32 | bin, ascending; chunks of one key in file order */
+	uint64_t* chunk_begin;        /* [n_chunks] virtual offsets */
+	uint64_t* chunk_end;
+	uint64_t* interval_offset;    /* [n_ref + 1] first window of every reference */
+	uint64_t* intervals;          /* [n_intervals] smallest virtual offset of a record that overlaps the window; empty windows: that of the next window of the reference that has one, else 0 */
+	uint64_t* ref_begin;          /* [n_ref] pseudo-bin 37450: virtual offsets of the first and behind the last record with this refID (0, 0 if none) ... */
+	uint64_t* ref_end;
+	uint64_t* ref_mapped;         /* ... and how many of them are mapped / unmapped (flag 0x4) */
+	uint64_t* ref_unmapped;
+} agpu_sorted_bam_index_arrays;
+int agpu_sorted_bam_begin(agpu_ctx* ctx, agpu_sorted_bam_info* info);
+int agpu_sorted_bam_next(agpu_ctx* ctx, void* pinned, uint64_t capacity, uint64_t* bytes);
+int agpu_sorted_bam_index(agpu_ctx* ctx, uint64_t first_block_file_offset, const uint32_t* ref_length, uint32_t n_ref, agpu_sorted_bam_index_arrays* index);
+int agpu_sorted_bam_end(agpu_ctx* ctx);
 /* what the host's sequential stages and its output writer need from a batch that lives on the device:
  *   agpu_get_viral_read_counts   mapped_viral_reads_by_contig (source/read_chimeric_alignments.cpp:735-739)
  *   agpu_get_coverage            coverage_t as the reference holds it (16-bit saturating windows, start/end flags); sizes by coverage_window_offset

@@ -71,6 +71,27 @@ int ahost_bam_sam_targets(ahost_session* session, const char** names, const uint
  * of the first alignment are skipped and counted.  names / name_offset [n_targets + 1]: the @SQ names in tid order.  Returns 0, or -1 with *bad_line = the 1-based number of the first
  * malformed line (its record is left out; the others are still written) or when `out` is too small (*out_bytes then says how much is needed). */
 int ahost_sam_transcode(const void* text, size_t size, const char* names, const uint32_t* name_offset, uint32_t n_targets, void* out, size_t capacity, uint64_t* out_bytes, uint64_t* n_records, uint64_t* bad_line);
+/* ---- --sorted-bam: the host side of agpu_sorted_bam_* (include/arriba_gpu.h) -- the records of -x in coordinate order as a BAM file of stored BGZF blocks, and its BAI index ----
+ *   ahost_sorted_bam_header     the header of the output, already in BGZF blocks of its own (the record blocks begin at *framed_bytes of the file): the header of the file the last
+ *                               ahost_bam_open opened, with "@HD ... SO:coordinate" -- an SO: already there is replaced, a header without @HD gets "@HD\tVN:1.6\tSO:coordinate" in
+ *                               front, every other line and the references stay.  SAM text: the BAM header is built from the '@' lines (l_text, the text, n_ref, SN / LN of every
+ *                               @SQ); an @SQ without LN is an error that names the line.  ref_length [n_ref]: for agpu_sorted_bam_index.  Valid until the next call on the session.
+ *   ahost_sorted_bam_header_of  the same from the head of an uncompressed input in memory (a BAM header, or the '@' lines of SAM text); valid until the next call on the thread
+ *   ahost_sorted_bam            arriba_amd/csrc/device/sorted_bam_core.hpp stepped on the host over BAM records in host memory: key, std::stable_sort, offsets, framing, index -- the same
+ *                               record blocks and the same index arrays as the device gives (its comparator; what --host-ingest and the CPU tier run).  index == NULL: no index.
+ *                               *blocks and the arrays of *index stay valid until the next call on the thread.
+ *   ahost_sorted_bam_write_index   FILE.bai (SAMv1 5.2) from the arrays
+ *   ahost_sorted_bam_eof        the 28 bytes that end a BGZF file
+ *   ahost_sorted_bam_write      all of it: path and path + ".bai" written through path + ".tmp" / ".bai.tmp" and renamed; a reference longer than 2^29 bases: the BAM file without
+ *                               an index, and a warning on stderr */
+int ahost_sorted_bam_header(ahost_session* session, const uint8_t** framed, uint64_t* framed_bytes, const uint32_t** ref_length, uint32_t* n_ref);
+int ahost_sorted_bam_header_of(const void* input_header, size_t size, const uint8_t** framed, uint64_t* framed_bytes, const uint32_t** ref_length, uint32_t* n_ref);
+int ahost_sorted_bam(const void* records, size_t size, uint64_t first_block_file_offset, const uint32_t* ref_length, uint32_t n_ref, const uint8_t** blocks, agpu_sorted_bam_info* info, agpu_sorted_bam_index_arrays* index);
+int ahost_sorted_bam_write_index(const agpu_sorted_bam_index_arrays* index, const char* path);
+void ahost_sorted_bam_eof(uint8_t* block /* [28] */);
+ /*  ahost_sorted_bam_file       the same for a file (BAM in BGZF, gzip or raw; SAM text): read whole into host memory -- what --host-ingest does for --sorted-bam */
+int ahost_sorted_bam_file(const char* input_path, const char* path, agpu_sorted_bam_info* info /* may be NULL */);
+int ahost_sorted_bam_write(const void* input_header, size_t header_size, const void* records, size_t size, const char* path, agpu_sorted_bam_info* info /* may be NULL */);
 int ahost_adopt_device_ingest(ahost_session* session, const agpu_ingest_result* result, const uint64_t* viral_read_counts, const uint16_t* coverage, const uint8_t* fragment_starts, const uint8_t* fragment_ends);
 int ahost_set_batch_rows(ahost_session* session, const agpu_batch_rows* rows, const uint32_t* fragments /* [rows->n] ascending: the fragment every row holds; NULL: row k holds the fragment
                          of entry k of the read lists of the table the next ahost_write_fusions writes (the reads of a candidate next to each other; the table then carries read_filter_of_rows) */);

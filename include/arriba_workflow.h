@@ -44,6 +44,9 @@ typedef struct {
 	uint8_t log_to_stdout;                /* 1: the progress lines of the reference's main() ("[time] Filtering duplicates (remaining=N)", source/arriba.cpp:96-610) go to stdout */
 	uint8_t host_ingest;                  /* 0 (default): read_chimeric_alignments runs on the device (agpu_ingest_*), the host feeds the bytes of the file;
 	                                         1: the multi-threaded host ingest builds the batch and uploads it */
+	const char* sorted_bam_file;          /* --sorted-bam; NULL = none.  The records of -x in coordinate order as a BAM file of stored BGZF blocks, and FILE.bai next to it (what run_arriba.sh:47-51
+	                                         gets from samtools sort / index), written behind read_chimeric_alignments from the record stream in HBM (include/arriba_gpu.h: agpu_sorted_bam_*).
+	                                         Of arriba_workflow_run's sample; the samples of a session say theirs with arriba_workflow_sorted_bam.  Not for one sample over several ranks. */
 } arriba_workflow_options;
 
 /* what the reference prints as "(remaining=N)" / "(total=N)" / "(marked=N)", in the order of the stages; stage names as in the reference's source */
@@ -81,6 +84,7 @@ typedef struct { /* seconds of one sample, by part (wall clock of the calling th
 	double shard_fragments;  /* one sample over several ranks, the reads sharded (below): the fragments THIS rank held through the sample (of the `read_chimeric_alignments` of the report); 0 = every
 	                            rank held the whole batch (one rank, or the split by an all-gather of the batch) */
 	double exchanged_bytes;  /*   ... and the bytes this rank received from the others in the exchanges of the sample (host collectives) */
+	double sorted_bam;       /* --sorted-bam: keys, sort, gather, copy back, the two files (inside `ingest`; beside the sample in front when the ingest was finished ahead) */
 } arriba_workflow_timing;
 /* options->chimeric_bam_file, output_file and discarded_output_file are not used by open (they belong to a sample); NULL + arriba_workflow_last_error() on failure */
 arriba_workflow_session* arriba_workflow_open(const arriba_workflow_options* options);
@@ -92,6 +96,10 @@ int arriba_workflow_sample(arriba_workflow_session* session, const char* chimeri
  * ahead of the one at work.  arriba_workflow_sample(bam) with nothing submitted submits bam itself (the behaviour without this call).  A sample that was submitted and never
  * asked for is thrown away by arriba_workflow_close.  Returns 0, or a negative number with the text in arriba_workflow_last_error(). */
 int arriba_workflow_submit(arriba_workflow_session* session, const char* chimeric_bam_file);
+/* --sorted-bam of the sample that is submitted NEXT (by arriba_workflow_submit, or by an arriba_workflow_sample with nothing submitted); NULL: none.  The file is written by the thread
+ * that finishes the ingest of that sample, before the stream in HBM goes to the feed of the sample behind it; if it cannot be written the sample fails with the message, FILE.tmp and
+ * FILE.bai.tmp are removed, and the session takes the next sample. */
+int arriba_workflow_sorted_bam(arriba_workflow_session* session, const char* sorted_bam_file);
 /* (If the device runs out of memory while two samples are in flight, arriba_workflow_sample throws away what was fed ahead, closes the second lane, runs its sample again with the device
  * to itself and submits the other sample again behind it -- once; a sample that does not fit the device alone fails the call.  INTEGRATION.md, "Memory".) */
 /* on: arriba_workflow_sample returns when the last output file of the sample (-O if given, else -o) has everything it needs off the device; the file is formatted and written
