@@ -97,6 +97,26 @@ class SortedBamIndex(ctypes.Structure):
         (name, c_void_p) for name in ("chunk_key", "chunk_begin", "chunk_end", "interval_offset", "intervals", "ref_begin", "ref_end", "ref_mapped", "ref_unmapped")]
 
 
+class SupportPoolInfo(ctypes.Structure):
+    """agpu_support_pool_info"""
+    _fields_ = [("names", c_uint64), ("stream_records", c_uint64), ("pooled_records", c_uint64), ("pool_bytes", c_uint64)]
+
+
+class SupportingRows(ctypes.Structure):
+    """agpu_supporting_rows: per row two (refID, 0-based breakpoint) pairs and the entries of the names that support it (CSR)"""
+    _fields_ = [("n_rows", c_uint32), ("ref", c_void_p), ("breakpoint", c_void_p), ("name_begin", c_void_p), ("names", c_void_p)]
+
+
+class SupportingInfo(ctypes.Structure):
+    """agpu_supporting_info"""
+    _fields_ = [(name, c_uint64) for name in ("rows", "records", "uncompressed_bytes", "file_bytes", "blocks", "windows", "window_bytes")]
+
+
+class SupportingIndex(ctypes.Structure):
+    """agpu_supporting_index_arrays: the sizes, then per record of the files its coordinates, bin and virtual offsets"""
+    _fields_ = [("n_rows", c_uint32), ("n_records", c_uint64)] + [(name, c_void_p) for name in ("row_first", "ref", "pos", "end_flag", "bin", "begin", "end")]
+
+
 class BamPiece(ctypes.Structure):
     """ahost_bam_piece: stored_bgzf is the KIND of the piece -- 0 stream bytes, 1 stored BGZF, 2 deflated BGZF, 3 lines of SAM text (first_line: the number of its first line)"""
     _fields_ = [("stored_bgzf", c_int), ("bytes", c_size_t), ("stream_bytes", c_size_t), ("n_blocks", c_uint32), ("first_line", c_uint64)]
@@ -236,6 +256,14 @@ def bind_device_api(lib, prefix="agpu_"):
         "sorted_bam_next": (c_int, [ctx, c_void_p, c_uint64, POINTER(c_uint64)]),
         "sorted_bam_index": (c_int, [ctx, c_uint64, c_void_p, c_uint32, POINTER(SortedBamIndex)]),
         "sorted_bam_end": (c_int, [ctx]),
+        "support_pool_build": (c_int, [ctx, c_void_p, c_void_p, c_uint64, POINTER(SupportPoolInfo)]),
+        "supporting_begin": (c_int, [ctx, POINTER(SupportingRows), ctypes.c_int64, POINTER(SupportingInfo)]),
+        "supporting_row_bytes": (c_int, [ctx, c_void_p]),
+        "supporting_next": (c_int, [ctx, c_void_p, c_uint64, POINTER(c_uint64)]),
+        "supporting_index": (c_int, [ctx, c_uint64, POINTER(SupportingIndex)]),
+        "supporting_end": (c_int, [ctx]),
+        "support_pool_release": (c_int, [ctx]),
+        "support_allocated_bytes": (c_int, [ctx, POINTER(c_uint64)]),
         "shard_export_size": (c_int, [ctx, POINTER(c_uint64)]),
         "shard_export": (c_int, [ctx, c_void_p, c_uint64]),
         "shard_merge": (c_int, [ctx, c_void_p, c_uint64, c_uint32, POINTER(IngestResult)]),
@@ -317,6 +345,13 @@ def bind_host_api(lib):
         "ahost_sorted_bam_eof": (None, [c_void_p]),
         "ahost_sorted_bam_file": (c_int, [c_char_p, c_char_p, POINTER(SortedBamInfo)]),
         "ahost_sorted_bam_write": (c_int, [c_void_p, c_size_t, c_void_p, c_size_t, c_char_p, POINTER(SortedBamInfo)]),
+        "ahost_written_fusion_rows": (c_int, [session, POINTER(c_uint32), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p)]),
+        "ahost_supporting_writer_open": (c_void_p, [c_char_p, c_void_p, c_uint64, c_uint32, c_void_p]),
+        "ahost_supporting_writer_push": (c_int, [c_void_p, c_void_p, c_uint64]),
+        "ahost_supporting_writer_index": (c_int, [c_void_p, POINTER(SupportingIndex), c_void_p, c_uint32]),
+        "ahost_supporting_writer_close": (c_int, [c_void_p, c_int]),
+        "ahost_supporting_alignments": (c_int, [c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p, c_uint64, POINTER(SupportingRows), ctypes.c_int64, c_char_p, POINTER(SupportingInfo)]),
+        "ahost_supporting_alignments_file": (c_int, [session, c_void_p, c_char_p, ctypes.c_int64, c_char_p, POINTER(SupportingInfo)]),
         "ahost_set_batch_rows": (c_int, [session, POINTER(BatchRows), c_void_p]),
         "ahost_fusion_table_reads": (c_int, [POINTER(FusionTable), c_int, c_void_p, c_uint64, POINTER(c_uint64)]),
         "ahost_read_length_sum_of": (c_float, [c_float, c_void_p, c_void_p, c_uint64]),
@@ -339,7 +374,7 @@ class WorkflowOptions(ctypes.Structure):
                                               "protein_domains_file", "genomic_breakpoints_file", "interesting_contigs", "viral_contigs", "gtf_features")] + [
         ("device", Params), ("min_itd_support", c_uint32), ("min_itd_allele_fraction", c_float), ("high_expression_quantile", c_float), ("min_spliced_events", c_uint32), ("min_anchor_length", c_uint32),
         ("max_homolog_identity", c_float), ("top_viral_contigs", c_uint32), ("viral_contig_min_covered_fraction", c_float), ("max_genomic_breakpoint_distance", c_int32),
-        ("print_extra_info_for_discarded_fusions", c_uint8), ("fill_sequence_gaps", c_uint8), ("device_index", c_int), ("log_to_stdout", c_uint8), ("host_ingest", c_uint8), ("sorted_bam_file", c_char_p)]
+        ("print_extra_info_for_discarded_fusions", c_uint8), ("fill_sequence_gaps", c_uint8), ("device_index", c_int), ("log_to_stdout", c_uint8), ("host_ingest", c_uint8), ("sorted_bam_file", c_char_p), ("supporting_alignments_prefix", c_char_p), ("supporting_alignments_window", ctypes.c_int64)]
 
 
 class WorkflowStage(ctypes.Structure):
@@ -351,7 +386,7 @@ class WorkflowReport(ctypes.Structure):
 
 
 class WorkflowTiming(ctypes.Structure):
-    _fields_ = [(name, ctypes.c_double) for name in ("total", "feed", "ingest", "adopt", "stages", "filter_mismappers", "output", "output_results", "output_rows", "output_format", "feed_read", "feed_push", "feed_total", "exchange_parts", "exchange_verdicts", "exchange_rows", "shard_fragments", "exchanged_bytes", "sorted_bam")]
+    _fields_ = [(name, ctypes.c_double) for name in ("total", "feed", "ingest", "adopt", "stages", "filter_mismappers", "output", "output_results", "output_rows", "output_format", "feed_read", "feed_push", "feed_total", "exchange_parts", "exchange_verdicts", "exchange_rows", "shard_fragments", "exchanged_bytes", "sorted_bam", "supporting_alignments")]
 
 
 WORKFLOW_MAX, WORKFLOW_MIN, WORKFLOW_SUM = 0, 1, 2
@@ -383,6 +418,7 @@ def workflow_library():
         lib.arriba_workflow_sample.argtypes = [c_void_p, c_char_p, c_char_p, c_char_p, POINTER(WorkflowReport), POINTER(WorkflowTiming)]; lib.arriba_workflow_sample.restype = c_int
         lib.arriba_workflow_submit.argtypes = [c_void_p, c_char_p]; lib.arriba_workflow_submit.restype = c_int
         lib.arriba_workflow_sorted_bam.argtypes = [c_void_p, c_char_p]; lib.arriba_workflow_sorted_bam.restype = c_int
+        lib.arriba_workflow_supporting_alignments.argtypes = [c_void_p, c_char_p]; lib.arriba_workflow_supporting_alignments.restype = c_int
         lib.arriba_workflow_cancel.argtypes = [c_void_p]; lib.arriba_workflow_cancel.restype = c_int
         lib.arriba_workflow_defer_output.argtypes = [c_void_p, c_int]; lib.arriba_workflow_defer_output.restype = c_int
         lib.arriba_workflow_finish_ahead.argtypes = [c_void_p, c_int]; lib.arriba_workflow_finish_ahead.restype = c_int

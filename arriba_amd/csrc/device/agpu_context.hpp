@@ -4,6 +4,7 @@
 
 #include <hip/hip_runtime.h>
 #include <cstdlib>
+#include <cstring>
 #include <deque>
 #include <functional>
 #include <map>
@@ -101,6 +102,21 @@ struct ScratchPool {
 	DeviceBuffer& get(const char* name) { std::lock_guard<std::mutex> lock(mutex); return buffers[name]; }
 };
 struct PoolSlots { DeviceBuffer* slot[AGPU_PIECE_SLOTS]; DeviceBuffer& operator[](size_t k) { return *slot[k]; } };
+// --supporting-alignments (agpu_supporting.hip): the records of the listed read names, copied out of the stream behind the ingest, until the rows of fusions.tsv are known.  The
+// "support.*" buffers are the context's own: not in the pool the lanes of a session share, not among the buffers that change hands between them (take_sample_buffers), not given
+// back under memory pressure (release_ingest_buffers) -- the pool of a sample lives until agpu_support_pool_release or the next build on the context.
+struct SupportState {
+	std::map<std::string, DeviceBuffer> buffers;
+	DeviceBuffer& buffer(const char* name) { return buffers[name]; }
+	void release_all() { for (std::map<std::string, DeviceBuffer>::iterator b = buffers.begin(); b != buffers.end(); ++b) b->second.release(); built = false; }
+	void release_prefix(const char* prefix) { for (std::map<std::string, DeviceBuffer>::iterator b = buffers.begin(); b != buffers.end(); ++b) if (b->first.compare(0, strlen(prefix), prefix) == 0) b->second.release(); }
+	uint64_t allocated() const { uint64_t sum = 0; for (std::map<std::string, DeviceBuffer>::const_iterator b = buffers.begin(); b != buffers.end(); ++b) sum += b->second.capacity; return sum; }
+	bool built = false, strip_hit_index = false, active = false, index_ready = false;
+	uint64_t n_names = 0, table_slots = 0, records = 0 /* of the pool */, bytes = 0; uint32_t hash_bits = 64;
+	// between agpu_supporting_begin and agpu_supporting_end
+	uint32_t n_rows = 0; uint64_t emissions = 0, blocks = 0, window_blocks = 0, next_block = 0, gathered_block = ~0ull, index_first = 0;
+	std::vector<uint64_t> row_first, row_bytes, row_block_begin, row_out_offset; // [n_rows + 1]: first record, payload bytes, first block, first byte of the framed blocks
+};
 }
 struct agpu_ctx {
 	explicit agpu_ctx(std::shared_ptr<agpu::ScratchPool> shared = std::shared_ptr<agpu::ScratchPool>()) : pool(shared ? shared : std::make_shared<agpu::ScratchPool>()),
@@ -185,6 +201,7 @@ struct agpu_ctx {
 	bool last_ingest_kept = false, last_ingest_part_of_sample = false, sorted_bam_active = false, sorted_bam_index_ready = false;
 	uint64_t sorted_bam_records = 0, sorted_bam_bytes = 0, sorted_bam_blocks = 0, sorted_bam_window_blocks = 0, sorted_bam_next_block = 0, sorted_bam_gathered_block = ~0ull, sorted_bam_index_first = 0;
 	uint64_t sorted_bam_chunks = 0, sorted_bam_intervals = 0, sorted_bam_no_coor = 0; uint32_t sorted_bam_n_ref = 0;
+	agpu::SupportState support; // --supporting-alignments (agpu_supporting.hip)
 	// A pushed piece: copied on the context's stream (piece_copied: the caller's buffer is free), unwrapped and CRC-checked on a stream of its own (piece_stream; piece_ready: its
 	// bytes are in the stream, piece_done: the raw bytes are not needed any more), so that the copy of the next piece never waits for a kernel; AGPU_PIECE_SLOTS raw buffers in turn
 	hipStream_t piece_stream = nullptr, piece_stream2 = nullptr /* deflated pieces take the two in turn */; hipEvent_t piece_copied[AGPU_PIECE_SLOTS] = {}, piece_ready[AGPU_PIECE_SLOTS] = {}, piece_done[AGPU_PIECE_SLOTS] = {};

@@ -17,19 +17,16 @@
 #include "agpu_context.hpp"
 #include "crc32_core.hpp"
 #include "sorted_bam_core.hpp"
+#include "sorted_bam_device.hpp"
 
 using namespace agpu;
 
 namespace {
 
 const int BLOCK = 256;
-const int GATHER_THREADS = 1024;          // 16 wavefronts: one record each at a time
+const int GATHER_THREADS = SBAM_GATHER_THREADS; // (the frame of a block and the copy of a record: sorted_bam_device.hpp, shared with agpu_supporting.hip)
 const uint32_t GATHER_BATCH = 512;        // records whose source and destination are looked up together
-const uint32_t IMAGE_BYTES = (SBAM_BLOCK + 15 + 15) / 16 * 16; // the block as it lies in memory, shifted by the alignment of its first byte (0 .. 15)
-const uint32_t CRC_LANE_BYTES = 64, CRC_VIRTUAL_BYTES = CRC_LANE_BYTES * GATHER_THREADS; // the payload is the END of a virtual block of 64 KiB whose front is zero bytes (crc32_core.hpp)
-const uint32_t CRC_SERIAL_BELOW = 64;     // a payload this short (the tail of a file) is done by one lane
 const uint64_t DEFAULT_WINDOW_BYTES = 256ull << 20;
-static_assert(CRC_VIRTUAL_BYTES >= SBAM_PAYLOAD, "the virtual block holds a payload");
 
 #define HIP_CHECK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { set_last_error(std::string(#call) + ": " + hipGetErrorString(e_)); return AGPU_ERR_DEVICE; } } while (0)
 #define ALLOC(buffer, bytes) do { if (!(buffer).allocate(bytes)) { set_last_error("hipMalloc failed (" #buffer ")"); return AGPU_ERR_NO_MEMORY; } } while (0)
@@ -65,9 +62,7 @@ __global__ void __launch_bounds__(BLOCK) sorted_bam_block_first_kernel(const uin
 }
 
 struct GatherShared {
-	uint4 image[IMAGE_BYTES / 16];
-	uint32_t crc_byte_table[256];
-	uint32_t advance[CRC32_ADVANCE_POWERS][32];
+	SbamFrameShared frame;
 	uint64_t source[GATHER_BATCH];           // where the record begins in the stream
 	uint64_t destination[GATHER_BATCH + 1];  // ... and in the uncompressed output; (the CRCs of the lanes lie over `source` later)
 };
@@ -85,13 +80,9 @@ __global__ void __launch_bounds__(GATHER_THREADS) sorted_bam_gather_kernel(const
 	const uint32_t length = (uint32_t) (total_bytes - begin < SBAM_PAYLOAD ? total_bytes - begin : SBAM_PAYLOAD);
 	uint8_t* const block_out = out + (uint64_t) blockIdx.x * SBAM_BLOCK;
 	const uint32_t pad = (uint32_t) ((uint64_t) block_out & 15u); // image byte pad + i is byte i of the block: 16-byte chunks of the image are 16-byte chunks of memory
-	uint8_t* const image = (uint8_t*) shared.image;
-	uint32_t* const image_words = (uint32_t*) shared.image;
+	uint8_t* const image = (uint8_t*) shared.frame.image;
 	const uint32_t payload_at = pad + SBAM_HEAD;
-
-	if (t < 256) shared.crc_byte_table[t] = tables->slice[0][t];
-	for (uint32_t k = t; k < CRC32_ADVANCE_POWERS * 32; k += GATHER_THREADS) shared.advance[k / 32][k % 32] = tables->advance[k / 32][k % 32];
-	if (t < SBAM_HEAD) image[pad + t] = sbam_head_byte(t, length);
+	sbam_frame_begin(shared.frame, tables, pad, length, t);
 
 	const uint64_t first_record = block_first[b], last_record = b + 1 < n_blocks ? block_first[b + 1] : n - 1;
 	for (uint64_t batch = first_record; batch <= last_record; batch += GATHER_BATCH) {
@@ -106,55 +97,11 @@ __global__ void __launch_bounds__(GATHER_THREADS) sorted_bam_gather_kernel(const
 			const uint64_t record_begin = shared.destination[j], record_end = shared.destination[j + 1];
 			const uint64_t from = record_begin > begin ? record_begin : begin, to = record_end < begin + length ? record_end : begin + length;
 			if (from >= to) continue;
-			const uint64_t source = shared.source[j] + (from - record_begin);
-			const uint32_t at = payload_at + (uint32_t) (from - begin), end = payload_at + (uint32_t) (to - begin); // image[at .. end)
-			uint32_t head = (4 - (at & 3u)) & 3u;
-			if (head > end - at) head = end - at;
-			if (lane < head) image[at + lane] = stream[source + lane];
-			const uint32_t words = (end - at - head) / 4, tail = (end - at - head) & 3u;
-			for (uint32_t k = lane; k < words; k += 64) image_words[(at + head) / 4 + k] = sbam_load32(stream, source + head + 4ull * k); // (aligned words of the stream and a shift: every word read holds a byte of the record)
-			if (lane < tail) image[end - tail + lane] = stream[source + (end - at) - tail + lane];
+			sbam_wave_copy<uint32_t>(image, payload_at + (uint32_t) (from - begin), payload_at + (uint32_t) (to - begin), stream, shared.source[j] + (from - record_begin), lane);
 		}
 	}
 	__syncthreads();
-
-	// the CRC-32 of image[payload_at .. payload_at + length)
-	uint32_t* const partial = (uint32_t*) shared.source;
-	if (length < CRC_SERIAL_BELOW) {
-		if (t == 0) partial[0] = ~crc32_of(shared.crc_byte_table, image + payload_at, length);
-	} else {
-		// raw CRCs (register started at 0) of the 64-byte chunks of the virtual block: zero bytes in front change nothing, and the standard start is the first four bytes inverted
-		const int32_t shift = (int32_t) (CRC_VIRTUAL_BYTES - length);
-		uint32_t c = 0;
-		const int32_t chunk = (int32_t) (t * CRC_LANE_BYTES) - shift; // where the chunk begins in the payload
-		if (chunk + (int32_t) CRC_LANE_BYTES > 0) {
-			for (int32_t i = chunk < 0 ? -chunk : 0; i < (int32_t) CRC_LANE_BYTES; ++i) {
-				const int32_t m = chunk + i;
-				uint32_t byte = image[payload_at + m];
-				if (m < 4) byte ^= 0xFFu;
-				c = shared.crc_byte_table[(c ^ byte) & 0xFFu] ^ (c >> 8);
-			}
-		}
-		partial[t] = c;
-		for (uint32_t level = 0, stride = 1; stride < GATHER_THREADS; ++level, stride *= 2) { // crc(A || B) = crc(A) advanced over |B| zero bytes, xor crc(B); |B| = 64 << level
-			__syncthreads();
-			if (t % (2 * stride) == 0) partial[t] = gf2_matrix_times(shared.advance[6 + level], partial[t]) ^ partial[t + stride];
-		}
-	}
-	__syncthreads();
-	const uint32_t crc = ~partial[0];
-	if (t < SBAM_TAIL) image[payload_at + length + t] = sbam_tail_byte(t, crc, length);
-	__syncthreads();
-
-	// image[pad .. pad + size) -> block_out[0 .. size): whole 16-byte chunks of memory with one store each, the ragged ends byte by byte (the neighbours' bytes of those chunks are theirs)
-	const uint32_t size = length + SBAM_HEAD + SBAM_TAIL, image_end = pad + size;
-	const uint32_t first_chunk = (pad + 15) / 16, end_chunk = image_end / 16;
-	uint4* const aligned_out = (uint4*) (block_out - pad);
-	for (uint32_t chunk = first_chunk + t; chunk < end_chunk; chunk += GATHER_THREADS) aligned_out[chunk] = shared.image[chunk];
-	const uint32_t head_end = first_chunk * 16 < image_end ? first_chunk * 16 : image_end;
-	if (pad + t < head_end) block_out[t] = image[pad + t];
-	const uint32_t tail_begin = end_chunk * 16 > head_end ? end_chunk * 16 : head_end;
-	if (tail_begin + t < image_end) block_out[tail_begin + t - pad] = image[tail_begin + t];
+	sbam_frame_finish(shared.frame, (uint32_t*) shared.source, pad, length, block_out, t);
 }
 
 // ---- the index ----

@@ -11,6 +11,8 @@
 #include <cstdint>
 #include "../../../include/arriba_host.h"
 #include "../device/sam_core.hpp"
+#include <cstdio>
+#include <functional>
 #include <map>
 #include <string>
 #include <unordered_map>
@@ -246,8 +248,30 @@ void sorted_bam_header(const uint8_t* input, size_t size, std::vector<uint8_t>& 
 void sorted_bam_frame(const uint8_t* bytes, uint64_t size, std::vector<uint8_t>& out);
 bool references_fit_bai(const uint32_t* ref_length, uint32_t n_ref);
 void sorted_bam_of(const uint8_t* records, uint64_t size, uint64_t first_block_file_offset, const uint32_t* ref_length /* NULL: no index */, uint32_t n_ref, SortedBam& result);
+struct SortedBamIndexed { int32_t ref, pos, end; bool unmapped; uint64_t begin_offset, end_offset; }; // a record of a file for its index: coordinates, and the virtual offsets of its first byte and behind its last
+void sorted_bam_index_of(uint64_t n, const std::function<SortedBamIndexed(uint64_t)>& record, const uint32_t* ref_length, uint32_t n_ref, SortedBam& result);
 void sorted_bam_bai(const agpu_sorted_bam_index_arrays& index, std::vector<uint8_t>& out);
+void write_file(const std::string& path, const std::vector<const std::vector<uint8_t>*>& parts);
 void sorted_bam_write(const uint8_t* input_header, size_t header_size, const uint8_t* records, uint64_t size, const std::string& path, agpu_sorted_bam_info* info);
+// --supporting-alignments on the host (supporting.cpp): the writer that cuts the framed record blocks of all rows -- one row's behind the other's, from the device or from the
+// stepping -- into PREFIX_ID.bam and makes PREFIX_ID.bam.bai from the arrays of their records; everything goes through *.tmp, and unless `commit` ran nothing of the prefix is
+// left behind.  supporting_alignments: arriba_amd/csrc/device/supporting_core.hpp stepped on the host over records in host memory.
+class SupportingWriter {
+public:
+	SupportingWriter(const std::string& prefix, const uint8_t* framed_header, uint64_t framed_bytes, uint32_t n_rows, const uint64_t* row_file_bytes);
+	~SupportingWriter();
+	void push(const uint8_t* bytes, uint64_t size);
+	void index(const agpu_supporting_index_arrays& arrays, const uint32_t* ref_length, uint32_t n_ref);
+	void commit();
+	void abandon();
+private:
+	std::string path_of(uint32_t row) const;
+	void open_row(); void close_row(); void skip_finished_rows();
+	std::string prefix_; std::vector<uint8_t> header_; std::vector<uint64_t> row_bytes_; size_t row_; uint64_t written_; FILE* file_; bool indexed_;
+	std::vector<std::string> temporaries_, finals_;
+};
+void supporting_alignments(const uint8_t* input_header, size_t header_size, const uint8_t* records, uint64_t size, const char* names, const uint64_t* name_offset, uint64_t n_names, bool strip_hit_index,
+                           const agpu_supporting_rows& rows, int64_t window, const std::string& prefix, agpu_supporting_info* info);
 const std::vector<uint8_t>& bam_feed_header_bytes(BamFeed* feed); // the head of the uncompressed input as the feed read it: the BAM header, or the '@' lines of SAM text
 
 // reference: source/read_chimeric_alignments.cpp:560-773 with separate_chimeric_bam_file=false, is_rna_bam_file=true

@@ -80,6 +80,7 @@ struct ahost_session {
 	bool rows_in_list_order = false;     // ... or row k holds the fragment of entry k of the read lists of the table written next (ahost_set_batch_rows without fragments)
 	std::vector<uint32_t> tid_to_contig;
 	std::vector<uint64_t> window_offset;
+	std::vector<WrittenRow> written_rows; std::vector<uint32_t> written_candidate; std::vector<int32_t> written_ref, written_breakpoint; // --supporting-alignments: the data rows of the last fusions file (not the discarded one) in their order
 	std::vector<uint8_t> input_header, sorted_bam_header_framed; std::vector<uint32_t> sorted_bam_ref_length; // --sorted-bam: the head of the file of the last ahost_bam_open; what ahost_sorted_bam_header made of it
 	~ahost_session() { if (feed) close_bam_feed(feed); }
 	std::map<std::pair<contig_t, contig_t>, bool> related_viruses;
@@ -320,6 +321,7 @@ static int write_or_format_fusions(ahost_session* session, const SampleView& sam
 		t.read_filter = table->read_filter; t.closest_genomic_breakpoint1 = table->closest_genomic_breakpoint1; t.closest_genomic_breakpoint2 = table->closest_genomic_breakpoint2; t.n_genes = table->n_genes; t.gene_contig = table->gene_contig; t.gene_start = table->gene_start; t.gene_end = table->gene_end;
 		OutputExtras extras = { &session->tags, &session->protein_domains, &session->protein_domain_index, max_mate_gap, fill_sequence_gaps != 0 };
 		extras.part = part; extras.parts = parts; extras.text_of_part = text_of_part;
+		if (!write_discarded && text_of_part == NULL) extras.rows_written = &session->written_rows;
 		// device ingest: the batch of the session holds only the rows fetched for this table (ahost_set_batch_rows); the read lists of the candidates
 		// that get written and the filter column are translated from fragments to rows
 		std::vector<uint32_t> lists_as_rows; std::vector<uint8_t> filter_of_rows;
@@ -641,19 +643,112 @@ int ahost_sorted_bam_write(const void* input_header, size_t header_size, const v
 	try { sorted_bam_write((const uint8_t*) input_header, header_size, (const uint8_t*) records, size, path, info); return 0; }
 	catch (const std::exception& e) { g_error = e.what(); return -1; }
 }
+namespace {
+// a file (BAM in BGZF, gzip or raw; SAM text) read whole into host memory as the uncompressed BAM stream; returns where its records begin
+uint64_t read_whole_bam(const char* input_path, std::vector<uint8_t>& stream) {
+	std::unique_ptr<ByteSource> source(text_or_bam_source(open_bam_file(input_path))); // (BGZF, gzip or raw; SAM text comes out as the BAM stream of its alignments)
+	stream.clear();
+	for (size_t got = 1; got > 0; ) { const size_t at = stream.size(); stream.resize(at + (16u << 20)); got = source->read(&stream[at], stream.size() - at); stream.resize(at + got); }
+	if (stream.size() < 12 || memcmp(stream.data(), "BAM\1", 4) != 0) throw std::runtime_error("failed to read SAM header");
+	uint64_t at = 8 + (uint64_t) le32(&stream[4]);
+	if (stream.size() < at + 4) throw std::runtime_error("failed to read SAM header");
+	const uint32_t n_ref = le32(&stream[at]);
+	at += 4;
+	for (uint32_t t = 0; t < n_ref; ++t) { if (stream.size() < at + 4) throw std::runtime_error("failed to read SAM header"); at += 8 + (uint64_t) le32(&stream[at]); if (stream.size() < at) throw std::runtime_error("failed to read SAM header"); }
+	return at;
+}
+}
 int ahost_sorted_bam_file(const char* input_path, const char* path, agpu_sorted_bam_info* info) {
 	if (!input_path || !path) { g_error = "null argument"; return -1; }
 	try {
-		std::unique_ptr<ByteSource> source(text_or_bam_source(open_bam_file(input_path))); // (BGZF, gzip or raw; SAM text comes out as the BAM stream of its alignments)
 		std::vector<uint8_t> stream;
-		for (size_t got = 1; got > 0; ) { const size_t at = stream.size(); stream.resize(at + (16u << 20)); got = source->read(&stream[at], stream.size() - at); stream.resize(at + got); }
-		if (stream.size() < 12 || memcmp(stream.data(), "BAM\1", 4) != 0) throw std::runtime_error("failed to read SAM header");
-		uint64_t at = 8 + (uint64_t) le32(&stream[4]);
-		if (stream.size() < at + 4) throw std::runtime_error("failed to read SAM header");
-		const uint32_t n_ref = le32(&stream[at]);
-		at += 4;
-		for (uint32_t t = 0; t < n_ref; ++t) { if (stream.size() < at + 4) throw std::runtime_error("failed to read SAM header"); at += 8 + (uint64_t) le32(&stream[at]); if (stream.size() < at) throw std::runtime_error("failed to read SAM header"); }
+		const uint64_t at = read_whole_bam(input_path, stream);
 		sorted_bam_write(stream.data(), at, stream.data() + at, stream.size() - at, path, info);
+		return 0;
+	} catch (const std::exception& e) { g_error = e.what(); return -1; }
+}
+
+// ---- --supporting-alignments (include/arriba_host.h) ----
+struct ahost_supporting_writer { SupportingWriter writer; ahost_supporting_writer(const char* prefix, const uint8_t* header, uint64_t bytes, uint32_t n_rows, const uint64_t* row_file_bytes) : writer(prefix, header, bytes, n_rows, row_file_bytes) {} };
+ahost_supporting_writer* ahost_supporting_writer_open(const char* prefix, const void* framed_header, uint64_t framed_bytes, uint32_t n_rows, const uint64_t* row_file_bytes) {
+	if (!prefix || (!framed_header && framed_bytes > 0) || (!row_file_bytes && n_rows > 0)) { g_error = "null argument"; return NULL; }
+	try { return new ahost_supporting_writer(prefix, (const uint8_t*) framed_header, framed_bytes, n_rows, row_file_bytes); }
+	catch (const std::exception& e) { g_error = e.what(); return NULL; }
+}
+int ahost_supporting_writer_push(ahost_supporting_writer* writer, const void* bytes, uint64_t size) {
+	if (!writer || (!bytes && size > 0)) { g_error = "null argument"; return -1; }
+	try { writer->writer.push((const uint8_t*) bytes, size); return 0; }
+	catch (const std::exception& e) { g_error = e.what(); return -1; }
+}
+int ahost_supporting_writer_index(ahost_supporting_writer* writer, const agpu_supporting_index_arrays* index, const uint32_t* ref_length, uint32_t n_ref) {
+	if (!writer || !index || (!ref_length && n_ref > 0)) { g_error = "null argument"; return -1; }
+	try { writer->writer.index(*index, ref_length, n_ref); return 0; }
+	catch (const std::exception& e) { g_error = e.what(); return -1; }
+}
+int ahost_supporting_writer_close(ahost_supporting_writer* writer, int commit) {
+	if (!writer) return 0;
+	int status = 0;
+	try { if (commit) writer->writer.commit(); else writer->writer.abandon(); }
+	catch (const std::exception& e) { g_error = e.what(); status = -1; writer->writer.abandon(); }
+	delete writer;
+	return status;
+}
+int ahost_supporting_alignments(const void* input_header, size_t header_size, const void* records, size_t size, const char* names, const uint64_t* name_offset, uint64_t n_names,
+                                const agpu_supporting_rows* rows, int64_t window, const char* prefix, agpu_supporting_info* info) {
+	if (!input_header || (!records && size > 0) || (n_names > 0 && (!names || !name_offset)) || !rows || !prefix) { g_error = "null argument"; return -1; }
+	try { supporting_alignments((const uint8_t*) input_header, header_size, (const uint8_t*) records, size, names, name_offset, n_names, false, *rows, window, prefix, info); return 0; }
+	catch (const std::exception& e) { g_error = e.what(); return -1; }
+}
+namespace {
+// the contig of a breakpoint is the reference sequence of the BAM file of that name: the first tid of the header that joined contigs_t under it (-1: none)
+void written_rows_of(ahost_session* session, const std::vector<uint32_t>& tid_to_contig) {
+	std::vector<int32_t> contig_to_tid(session->contigs.size() + 1, -1);
+	for (size_t tid = tid_to_contig.size(); tid-- > 0; ) if (tid_to_contig[tid] < contig_to_tid.size()) contig_to_tid[tid_to_contig[tid]] = (int32_t) tid;
+	const size_t n = session->written_rows.size();
+	session->written_candidate.resize(n); session->written_ref.resize(2 * n); session->written_breakpoint.resize(2 * n);
+	for (size_t r = 0; r < n; ++r) {
+		const WrittenRow& row = session->written_rows[r];
+		session->written_candidate[r] = row.candidate;
+		for (int k = 0; k < 2; ++k) { session->written_ref[2 * r + k] = row.contig[k] < contig_to_tid.size() ? contig_to_tid[row.contig[k]] : -1; session->written_breakpoint[2 * r + k] = row.breakpoint[k]; }
+	}
+}
+}
+int ahost_written_fusion_rows(ahost_session* session, uint32_t* n_rows, const uint32_t** candidate, const int32_t** ref, const int32_t** breakpoint) {
+	if (!session || !n_rows || !candidate || !ref || !breakpoint) { g_error = "null argument"; return -1; }
+	try {
+		written_rows_of(session, session->tid_to_contig); // (of the file the last ahost_bam_open opened)
+		*n_rows = (uint32_t) session->written_rows.size(); *candidate = session->written_candidate.data(); *ref = session->written_ref.data(); *breakpoint = session->written_breakpoint.data();
+		return 0;
+	} catch (const std::exception& e) { g_error = e.what(); return -1; }
+}
+// --host-ingest: the rows of the fusions file the session wrote last, the names of their supporting fragments from the batch of the session ("QNAME,HI"), the records of the file
+int ahost_supporting_alignments_file(ahost_session* session, const ahost_fusion_table* table, const char* input_path, int64_t window, const char* prefix, agpu_supporting_info* info) {
+	if (!session || !table || !input_path || !prefix) { g_error = "null argument"; return -1; }
+	try {
+		if (!session->have_batch || session->device_batch) throw std::runtime_error("the supporting alignments of a file need the batch of a host ingest");
+		std::vector<uint8_t> stream;
+		const uint64_t at = read_whole_bam(input_path, stream);
+		// (the host ingest read the file by itself: the references of its header are looked up in contigs_t, which they joined then)
+		std::vector<uint8_t> framed; std::vector<uint32_t> ref_length; std::vector<uint32_t> tid_to_contig;
+		{ uint64_t name_at = 12 + (uint64_t) le32(&stream[4]); const uint32_t n_ref = le32(&stream[name_at - 4]);
+		  for (uint32_t t = 0; t < n_ref; ++t) { const uint32_t l_name = le32(&stream[name_at]); tid_to_contig.push_back(session->contigs.add(std::string((const char*) &stream[name_at + 4], l_name > 0 ? l_name - 1 : 0))); name_at += 8 + (uint64_t) l_name; } }
+		written_rows_of(session, tid_to_contig);
+		const uint32_t n_rows = (uint32_t) session->written_rows.size(); const uint32_t* candidate = session->written_candidate.data(); const int32_t* ref = session->written_ref.data(); const int32_t* breakpoint = session->written_breakpoint.data();
+		const Batch& batch = session->ingest.batch;
+		std::vector<uint64_t> name_begin(1, 0), name_offset(1, 0); std::vector<uint32_t> entries; std::string names;
+		for (uint32_t r = 0; r < n_rows; ++r) {
+			if (candidate[r] >= table->n_candidates) throw std::runtime_error("the table is not the one the fusions file was written from");
+			for (uint64_t k = table->list_offset[3 * (size_t) candidate[r]]; k < table->list_offset[3 * (size_t) candidate[r] + 3]; ++k) {
+				const uint32_t read = table->read_lists[k];
+				if (read >= batch.n) throw std::runtime_error("the table is not the one the fusions file was written from");
+				entries.push_back((uint32_t) (name_offset.size() - 1));
+				names.append(batch.names, batch.name_offset[read], batch.name_offset[read + 1] - batch.name_offset[read]);
+				name_offset.push_back(names.size());
+			}
+			name_begin.push_back(entries.size());
+		}
+		const agpu_supporting_rows rows = { n_rows, ref, breakpoint, name_begin.data(), entries.data() };
+		supporting_alignments(stream.data(), at, stream.data() + at, stream.size() - at, names.data(), name_offset.data(), name_offset.size() - 1, true, rows, window, prefix, info);
 		return 0;
 	} catch (const std::exception& e) { g_error = e.what(); return -1; }
 }

@@ -329,6 +329,15 @@ void write_fusions_to_file(const Annotation& annotation, const FlatIndex& exon_i
 	}
 
 	profile_mark("genes indexed, rows sorted");
+	if (extras.rows_written != NULL) {
+		extras.rows_written->clear();
+		for (size_t r = 0; r < rows.size(); ++r) {
+			const Fusion& f = rows[r];
+			WrittenRow row = { f.candidate, { f.contig1, f.contig2 }, { f.breakpoint1, f.breakpoint2 } };
+			if (!f.transcript_start_gene1) { std::swap(row.contig[0], row.contig[1]); std::swap(row.breakpoint[0], row.breakpoint[1]); } // (the 5' gene comes first)
+			extras.rows_written->push_back(row);
+		}
+	}
 	const bool to_text = extras.text_of_part != NULL;
 	if (to_text && extras.parts > 1) { // this rank's share of the rows, in their order
 		std::vector<Fusion> mine;

@@ -4,6 +4,7 @@
 #include <algorithm>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <iostream>
 #include <stdexcept>
 #include <string>
@@ -146,6 +147,17 @@ void sorted_bam_of(const uint8_t* records, uint64_t size, uint64_t first_block_f
 	// the index
 	result.indexed = ref_length != NULL;
 	if (!result.indexed) return;
+	sorted_bam_index_of(n, [&](uint64_t i) {
+		const SbamRecord& r = parsed[order[i]];
+		const SortedBamIndexed record = { r.ref, r.pos, r.end, (r.flag & 4u) != 0, sbam_voffset(first_block_file_offset, out_offset[i]), sbam_voffset(first_block_file_offset, out_offset[i + 1]) };
+		return record;
+	}, ref_length, n_ref, result);
+}
+
+// the arrays of the index from the records of a file in file order (what the kernels of agpu_sorted_bam.hip compute; --supporting-alignments makes the indexes of its small files here)
+void sorted_bam_index_of(uint64_t n, const std::function<SortedBamIndexed(uint64_t)>& record, const uint32_t* ref_length, uint32_t n_ref, SortedBam& result) {
+	using namespace agpu;
+	result.indexed = true;
 	if (!references_fit_bai(ref_length, n_ref)) throw std::runtime_error("a reference is longer than 2^29 bases: a BAI index cannot address it");
 	result.interval_offset.assign((size_t) n_ref + 1, 0);
 	for (uint32_t t = 0; t < n_ref; ++t) result.interval_offset[t + 1] = result.interval_offset[t] + sbam_windows_of(ref_length[t]);
@@ -155,12 +167,12 @@ void sorted_bam_of(const uint8_t* records, uint64_t size, uint64_t first_block_f
 	std::vector<uint64_t> run_key, run_begin, run_end;
 	bool open = false;
 	for (uint64_t i = 0; i < n; ++i) {
-		const SbamRecord& r = parsed[order[i]];
-		const uint64_t begin = sbam_voffset(first_block_file_offset, out_offset[i]), end = sbam_voffset(first_block_file_offset, out_offset[i + 1]);
+		const SortedBamIndexed r = record(i);
+		const uint64_t begin = r.begin_offset, end = r.end_offset;
 		if (r.ref < 0) ++result.n_no_coor;
 		else if ((uint32_t) r.ref < n_ref) {
 			result.ref_begin[r.ref] = std::min(result.ref_begin[r.ref], begin); result.ref_end[r.ref] = std::max(result.ref_end[r.ref], end);
-			++((r.flag & 4u) ? result.ref_unmapped : result.ref_mapped)[r.ref];
+			++(r.unmapped ? result.ref_unmapped : result.ref_mapped)[r.ref];
 		}
 		if (!sbam_indexed(r.ref, r.pos, n_ref)) { open = false; continue; }
 		const uint64_t key = sbam_chunk_key(r.ref, sbam_reg2bin(r.pos, r.end));

@@ -64,7 +64,9 @@ void usage() {
 	             " -T INT top viral contigs (5)   -C FLOAT min. covered fraction of a viral contig (0.05)   -l INT max. ITD length (100)   -z FLOAT min. ITD allele fraction (0.07)   -Z INT min. ITD support (10)\n"
 	             " -u duplicates are marked in the BAM file   -X extra columns for discarded fusions   -I fill gaps of the fusion transcript from the assembly   -h this text\n"
 	             " --device N  the GPU to use (0)            --host-ingest  read_chimeric_alignments on the host instead of on the GPU\n"
-	             " --sorted-bam FILE  the records of -x in coordinate order (BAM, stored BGZF blocks) and FILE.bai: what samtools sort + samtools index make of Aligned.out.bam\n";
+	             " --sorted-bam FILE  the records of -x in coordinate order (BAM, stored BGZF blocks) and FILE.bai: what samtools sort + samtools index make of Aligned.out.bam\n"
+	             " --supporting-alignments PREFIX  PREFIX_ID.bam and .bam.bai per row of -o: the alignments of its read_identifiers near its breakpoints (extract_fusion-supporting_alignments.sh)\n"
+	             " --supporting-window INT  how far from a breakpoint they may lie (1000000)\n";
 }
 
 }
@@ -86,11 +88,13 @@ int main(int argc, char** argv) {
 	std::cout << "[" << "arriba_gpu_workflow" << "] MI355X-native fusion caller (command line, progress lines and output files of Arriba 2.5.1)" << std::endl;
 	if (argc == 1) { usage(); crash("no arguments given"); }
 	require(argv[1][0] == '-' && argv[1][1] != '\0', std::string("cannot interpret the first argument: ") + argv[1]);
-	// the three long options of this implementation are taken out first; the rest is the reference's getopt string (source/options.cpp:282)
+	// the long options of this implementation are taken out first; the rest is the reference's getopt string (source/options.cpp:282)
 	std::vector<char*> arguments(1, argv[0]);
 	for (int a = 1; a < argc; ++a) {
 		if (strcmp(argv[a], "--host-ingest") == 0) options.host_ingest = 1;
 		else if (strcmp(argv[a], "--sorted-bam") == 0 && a + 1 < argc) { options.sorted_bam_file = argv[++a]; parent_exists(options.sorted_bam_file); }
+		else if (strcmp(argv[a], "--supporting-alignments") == 0 && a + 1 < argc) { options.supporting_alignments_prefix = argv[++a]; parent_exists(options.supporting_alignments_prefix); }
+		else if (strcmp(argv[a], "--supporting-window") == 0 && a + 1 < argc) { long window; require(parse_int(argv[++a], window) && window > 0 && window <= 0x7FFFFFFFl, "invalid argument to --supporting-window"); options.supporting_alignments_window = window; }
 		else if (strcmp(argv[a], "--device") == 0 && a + 1 < argc) { long device; require(parse_int(argv[++a], device) && device >= 0, "invalid argument to --device"); options.device_index = (int) device; }
 		else arguments.push_back(argv[a]);
 	}

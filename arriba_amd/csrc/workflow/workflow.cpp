@@ -30,6 +30,14 @@ extern "C" int agpu_sorted_bam_begin(agpu_ctx* ctx, agpu_sorted_bam_info* info) 
 extern "C" int agpu_sorted_bam_next(agpu_ctx* ctx, void* pinned, uint64_t capacity, uint64_t* bytes) __attribute__((weak));
 extern "C" int agpu_sorted_bam_index(agpu_ctx* ctx, uint64_t first_block_file_offset, const uint32_t* ref_length, uint32_t n_ref, agpu_sorted_bam_index_arrays* index) __attribute__((weak));
 extern "C" int agpu_sorted_bam_end(agpu_ctx* ctx) __attribute__((weak));
+// ... and those of --supporting-alignments
+extern "C" int agpu_support_pool_build(agpu_ctx* ctx, const char* names, const uint64_t* name_offset, uint64_t n_names, agpu_support_pool_info* info) __attribute__((weak));
+extern "C" int agpu_supporting_begin(agpu_ctx* ctx, const agpu_supporting_rows* rows, int64_t window, agpu_supporting_info* info) __attribute__((weak));
+extern "C" int agpu_supporting_row_bytes(agpu_ctx* ctx, uint64_t* row_file_bytes) __attribute__((weak));
+extern "C" int agpu_supporting_next(agpu_ctx* ctx, void* pinned, uint64_t capacity, uint64_t* bytes) __attribute__((weak));
+extern "C" int agpu_supporting_index(agpu_ctx* ctx, uint64_t first_block_file_offset, agpu_supporting_index_arrays* index) __attribute__((weak));
+extern "C" int agpu_supporting_end(agpu_ctx* ctx) __attribute__((weak));
+extern "C" int agpu_support_pool_release(agpu_ctx* ctx) __attribute__((weak));
 
 namespace {
 
@@ -80,8 +88,9 @@ struct Run {
 	// read_chimeric_alignments in two halves (feed_file: the bytes of the file into HBM, on a thread of its own when the sample was submitted ahead; finish_device_ingest: what is
 	// left behind the last piece): what the first half leaves for the second
 	bool bam_open = false; uint64_t coverage_windows = 0; uint32_t bam_contigs = 0; double feed_started = 0, feed_finished = 0, feed_reading = 0, feed_pushing = 0;
-	std::string bam_path, output_path, discarded_path, sorted_bam_path; // of the sample this lane works on (options.* point at them)
+	std::string bam_path, output_path, discarded_path, sorted_bam_path, supporting_prefix; // of the sample this lane works on (options.* point at them)
 	double sorted_bam_seconds = 0; // --sorted-bam of the sample at work
+	double supporting_seconds = 0; bool support_pool_built = false; // --supporting-alignments of the sample at work: the pool behind the ingest and the files behind fusions.tsv
 	std::function<void()> after_ingest; // a session with two lanes: the stream and the tables of the ingest are free for the feed of the next sample
 	// arriba_workflow_finish_ahead: the second half ran on the feeder thread, before the caller asked for the sample; what it found is noted (report, timing) when the caller does
 	bool ingest_finished_ahead = false; uint64_t ingest_records = 0, ingest_stream_bytes = 0; double ingest_fed = 0, ingest_finished = 0, ingest_adopted = 0;
@@ -118,7 +127,7 @@ struct Run {
 	Run(const arriba_workflow_options& o): options(o), report(nullptr), timing(nullptr), host(nullptr), device(nullptr), dummy_genes(0), n_candidates(0), n_fragments(0), mapped_reads(0), device_ingest(false) {
 		for (int k = 0; k < FEED_BUFFERS; ++k) { pieces[k] = nullptr; tables[k] = nullptr; }
 		const char** texts[] = { &options.assembly_file, &options.gene_annotation_file, &options.chimeric_bam_file, &options.output_file, &options.discarded_output_file, &options.blacklist_file, &options.known_fusions_file,
-		                         &options.tags_file, &options.protein_domains_file, &options.genomic_breakpoints_file, &options.interesting_contigs, &options.viral_contigs, &options.gtf_features, &options.sorted_bam_file };
+		                         &options.tags_file, &options.protein_domains_file, &options.genomic_breakpoints_file, &options.interesting_contigs, &options.viral_contigs, &options.gtf_features, &options.sorted_bam_file, &options.supporting_alignments_prefix };
 		strings.reserve(sizeof(texts) / sizeof(texts[0]));
 		for (size_t k = 0; k < sizeof(texts) / sizeof(texts[0]); ++k) if (*texts[k] != nullptr) { strings.push_back(*texts[k]); *texts[k] = strings.back().c_str(); }
 	}
@@ -198,6 +207,7 @@ void feed_file(Run& run) {
 	const double started = now_seconds();
 	run.feed_started = started;
 	if (run.ranks != nullptr && o.sorted_bam_file != nullptr) throw Failure{ "ERROR: a sorted BAM file of one sample over several GPUs is not supported" };
+	if (run.ranks != nullptr && o.supporting_alignments_prefix != nullptr) throw Failure{ "ERROR: supporting alignments of one sample over several GPUs are not supported" };
 	agpu_ingest_config config;
 	if (run.ranks != nullptr) host_check(ahost_bam_open_part(run.host, o.chimeric_bam_file, o.device.external_duplicate_marking, o.device.max_itd_length, run.ranks->rank, run.ranks->size, &config)); // this rank's part of the records
 	else host_check(ahost_bam_open(run.host, o.chimeric_bam_file, o.device.external_duplicate_marking, o.device.max_itd_length, &config));
@@ -472,6 +482,73 @@ void write_sorted_bam(Run& run) {
 	run.sorted_bam_seconds = now_seconds() - started;
 }
 
+// --supporting-alignments, phase 1: behind the ingest, while the stream is in HBM, the records of the read names of the batch go into a pool of this lane's context
+// (include/arriba_gpu.h: agpu_support_pool_build).  Phase 2 follows when the rows of fusions.tsv are fixed (write_supporting_alignments).
+void build_support_pool(Run& run) {
+	if (!agpu_support_pool_build || !agpu_supporting_begin || !agpu_supporting_row_bytes || !agpu_supporting_next || !agpu_supporting_index || !agpu_supporting_end || !agpu_support_pool_release)
+		throw Failure{ "ERROR: --supporting-alignments needs the device library (agpu_support_pool_build), which this build is not linked with" };
+	const double started = now_seconds();
+	agpu_support_pool_info info;
+	const int status = agpu_support_pool_build(run.device, nullptr, nullptr, 0, &info);
+	if (status == AGPU_ERR_NO_MEMORY) throw Failure{ std::string("ERROR: --supporting-alignments: ") + agpu_last_error(), status };
+	device_check(status);
+	run.support_pool_built = true;
+	run.supporting_seconds = now_seconds() - started;
+}
+
+// Phase 2: PREFIX_ID.bam and PREFIX_ID.bam.bai for the data rows of the fusions file that was just written (the rows of the host's writer, the read lists of `table`, which hold
+// fragments of the batch): the framed blocks of all rows come through two pinned buffers in turn and are cut into the files by the host library, which also makes the indexes.
+void write_supporting_alignments(Run& run, const ahost_fusion_table& table) {
+	const double started = now_seconds();
+	const std::string prefix = run.options.supporting_alignments_prefix;
+	const int64_t window = run.options.supporting_alignments_window > 0 ? run.options.supporting_alignments_window : 1000000;
+	if (!run.device_ingest) { // (the host's stepping of the same code)
+		host_check(ahost_supporting_alignments_file(run.host, &table, run.options.chimeric_bam_file, window, prefix.c_str(), nullptr));
+		run.supporting_seconds += now_seconds() - started;
+		return;
+	}
+	if (!run.support_pool_built) throw Failure{ "ERROR: --supporting-alignments: the pool of supporting alignments was not built behind the ingest of this sample" };
+	uint32_t n_rows = 0; const uint32_t* candidate = nullptr; const int32_t* ref = nullptr; const int32_t* breakpoint = nullptr;
+	host_check(ahost_written_fusion_rows(run.host, &n_rows, &candidate, &ref, &breakpoint));
+	std::vector<uint64_t> name_begin((size_t) n_rows + 1, 0);
+	for (uint32_t r = 0; r < n_rows; ++r) name_begin[r + 1] = name_begin[r] + (table.list_offset[3 * (size_t) candidate[r] + 3] - table.list_offset[3 * (size_t) candidate[r]]);
+	std::vector<uint32_t> names((size_t) name_begin[n_rows]);
+	for (uint32_t r = 0; r < n_rows; ++r) if (name_begin[r + 1] > name_begin[r]) memcpy(&names[(size_t) name_begin[r]], table.read_lists + table.list_offset[3 * (size_t) candidate[r]], (size_t) (name_begin[r + 1] - name_begin[r]) * 4);
+	const agpu_supporting_rows rows = { n_rows, ref, breakpoint, name_begin.data(), names.data() };
+	agpu_supporting_info info;
+	device_check(agpu_supporting_begin(run.device, &rows, window, &info));
+	struct Ender { Run& run; ~Ender() { agpu_supporting_end(run.device); agpu_support_pool_release(run.device); run.support_pool_built = false; } } ender = { run };
+	const uint8_t* header = nullptr; uint64_t header_bytes = 0; const uint32_t* ref_length = nullptr; uint32_t n_ref = 0;
+	host_check(ahost_sorted_bam_header(run.host, &header, &header_bytes, &ref_length, &n_ref));
+	std::vector<uint64_t> row_bytes((size_t) n_rows + 1, 0);
+	device_check(agpu_supporting_row_bytes(run.device, row_bytes.data()));
+	ahost_supporting_writer* writer = ahost_supporting_writer_open(prefix.c_str(), header, header_bytes, n_rows, row_bytes.data());
+	if (writer == nullptr) throw Failure{ std::string("ERROR: ") + ahost_last_error() };
+	try {
+		uint8_t* windows[2] = { run.stage<uint8_t>("sorted_bam.window0", info.window_bytes), run.stage<uint8_t>("sorted_bam.window1", info.window_bytes) };
+		uint64_t written = 0;
+		for (unsigned int turn = 0; ; ++turn) {
+			uint64_t bytes = 0;
+			device_check(agpu_supporting_next(run.device, windows[turn & 1], info.window_bytes, &bytes));
+			if (bytes == 0) break;
+			host_check(ahost_supporting_writer_push(writer, windows[turn & 1], bytes));
+			written += bytes;
+		}
+		if (written != info.file_bytes) throw Failure{ "ERROR: the record blocks of '" + prefix + "' do not have the size that was announced" };
+		agpu_supporting_index_arrays index; memset(&index, 0, sizeof(index));
+		device_check(agpu_supporting_index(run.device, header_bytes, &index));
+		const size_t n = (size_t) index.n_records;
+		std::vector<uint64_t> wide(2 * n + n_rows + 2); std::vector<uint32_t> narrow(4 * n + 1);
+		index.row_first = wide.data(); index.begin = wide.data() + n_rows + 1; index.end = wide.data() + n_rows + 1 + n;
+		index.ref = (int32_t*) narrow.data(); index.pos = (int32_t*) narrow.data() + n; index.end_flag = narrow.data() + 2 * n; index.bin = narrow.data() + 3 * n;
+		device_check(agpu_supporting_index(run.device, header_bytes, &index));
+		host_check(ahost_supporting_writer_index(writer, &index, ref_length, n_ref));
+	}
+	catch (...) { ahost_supporting_writer_close(writer, 0); throw; }
+	host_check(ahost_supporting_writer_close(writer, 1));
+	run.supporting_seconds += now_seconds() - started;
+}
+
 // ... and what is left of read_chimeric_alignments behind the last piece (agpu_ingest_finish), the counters, coverage_t and viral read counts back to the host session
 void finish_device_ingest(Run& run, double waited_since) {
 	struct Closer { Run& run; ~Closer() { if (run.bam_open) { ahost_bam_close(run.host); run.bam_open = false; } } } closer = { run };
@@ -481,6 +558,8 @@ void finish_device_ingest(Run& run, double waited_since) {
 	together(run.ranks, [&] { device_check(agpu_ingest_finish(run.device, &result)); });
 	run.sorted_bam_seconds = 0;
 	if (run.options.sorted_bam_file != nullptr) write_sorted_bam(run); // (before after_ingest: in a session of two lanes the stream belongs to the next feed after that)
+	run.supporting_seconds = 0; run.support_pool_built = false;
+	if (run.options.supporting_alignments_prefix != nullptr) build_support_pool(run); // (before after_ingest as well; the pool is this lane's own and outlives the hand-over of the stream)
 	run.sharded = false; run.first_rank = 0; run.exchanged_bytes = 0;
 	if (run.ranks != nullptr && !shard_reads(run, result, windows, n_contigs)) exchange_parts(run, result);
 	if (!run.sharded) run.local_fragments = result.fragments;
@@ -754,7 +833,8 @@ void write_output_files(Run& run, int32_t max_mate_gap) {
 			continue;
 		}
 		const bool last_file = write_discarded == (run.options.discarded_output_file ? 1 : 0);
-		if (run.defer_output && last_file) { // nothing of this file is on the device any more: formatted and written beside the next sample
+		const bool with_supporting_alignments = write_discarded == 0 && run.options.supporting_alignments_prefix != nullptr;
+		if (run.defer_output && last_file && !with_supporting_alignments) { // nothing of this file is on the device any more: formatted and written beside the next sample
 			const std::string path = write_discarded ? run.options.discarded_output_file : run.options.output_file;
 			const unsigned int max_itd_length = run.options.device.max_itd_length; const int fill_gaps = run.options.fill_sequence_gaps;
 			run.writer_error.clear();
@@ -782,6 +862,11 @@ void write_output_files(Run& run, int32_t max_mate_gap) {
 		}
 		host_check(ahost_write_fusions(run.host, &table, write_discarded ? run.options.discarded_output_file : run.options.output_file, write_discarded, print_extra_info, run.options.device.max_itd_length, max_mate_gap, run.options.fill_sequence_gaps));
 		lap(&arriba_workflow_timing::output_format);
+		if (with_supporting_alignments) { // (the rows of fusions.tsv are fixed: --supporting-alignments, phase 2; its seconds are not the writer's)
+			write_supporting_alignments(run, table);
+			if (run.timing) run.timing->supporting_alignments = run.supporting_seconds;
+			mark = now_seconds();
+		}
 	}
 }
 
@@ -1253,11 +1338,12 @@ int arriba_workflow_run(const arriba_workflow_options* options, arriba_workflow_
 struct arriba_workflow_session {
 	Run* lanes[2];
 	int processed_lane = 0; // of the sample arriba_workflow_sample worked on last
-	struct Submitted { std::string bam, sorted_bam; int lane = 0; std::thread feeder; bool fed = false, ingest_finished = false, started = false; std::string error; int error_code = 0; };
+	struct Submitted { std::string bam, sorted_bam, supporting; int lane = 0; std::thread feeder; bool fed = false, ingest_finished = false, started = false; std::string error; int error_code = 0; };
 	std::deque<std::unique_ptr<Submitted>> queue; // oldest first; at most two
 	std::mutex mutex; std::condition_variable changed;
 	bool ingest_busy = false; // a lane is between agpu_ingest_begin and agpu_ingest_finish
 	std::string next_sorted_bam; // arriba_workflow_sorted_bam: of the sample that is submitted next
+	std::string next_supporting; // arriba_workflow_supporting_alignments: likewise
 	bool defer_output = false;
 	bool retrying = false; // arriba_workflow_sample runs a sample again after the device ran out of memory with two lanes (below)
 	bool finish_ahead = false; // arriba_workflow_finish_ahead: the feeder of a sample also finishes its ingest (the lanes keep their batch buffers)
@@ -1322,10 +1408,11 @@ struct arriba_workflow_session {
 		Run& run = *lanes[lane];
 		run.bam_path = bam; run.options.chimeric_bam_file = run.bam_path.c_str();
 		run.sorted_bam_path.swap(next_sorted_bam); next_sorted_bam.clear(); run.options.sorted_bam_file = run.sorted_bam_path.empty() ? nullptr : run.sorted_bam_path.c_str();
+		run.supporting_prefix.swap(next_supporting); next_supporting.clear(); run.options.supporting_alignments_prefix = run.supporting_prefix.empty() ? nullptr : run.supporting_prefix.c_str();
 		run.timing = nullptr; run.report = nullptr;
 		prepare_sample(run);
 		std::unique_ptr<Submitted> sample(new Submitted());
-		sample->bam = bam; sample->sorted_bam = run.sorted_bam_path; sample->lane = lane;
+		sample->bam = bam; sample->sorted_bam = run.sorted_bam_path; sample->supporting = run.supporting_prefix; sample->lane = lane;
 		Submitted* mine = sample.get();
 		{ std::lock_guard<std::mutex> lock(mutex); queue.push_back(std::move(sample)); }
 		if (!run.device_ingest) { join_writer_of(lane); std::lock_guard<std::mutex> lock(mutex); mine->fed = true; return; } // (the host ingest reads the file inside arriba_workflow_sample)
@@ -1364,6 +1451,12 @@ arriba_workflow_session* arriba_workflow_open(const arriba_workflow_options* opt
 int arriba_workflow_sorted_bam(arriba_workflow_session* session, const char* sorted_bam_file) {
 	if (!session) { g_error = "ERROR: null argument"; return -1; }
 	session->next_sorted_bam = sorted_bam_file ? sorted_bam_file : "";
+	return 0;
+}
+
+int arriba_workflow_supporting_alignments(arriba_workflow_session* session, const char* prefix) {
+	if (!session) { g_error = "ERROR: null argument"; return -1; }
+	session->next_supporting = prefix ? prefix : "";
 	return 0;
 }
 
@@ -1415,7 +1508,7 @@ int arriba_workflow_sample(arriba_workflow_session* session, const char* chimeri
 	}
 	catch (const Failure& failure) { g_error = failure.text; g_error_code = failure.code; status = -1; }
 	catch (const std::exception& e) { g_error = std::string("ERROR: ") + e.what(); g_error_code = 0; status = -1; }
-	if (lane) { lane->after_ingest = nullptr; lane->before_host_writer = nullptr; lane->options.chimeric_bam_file = nullptr; lane->options.sorted_bam_file = nullptr; lane->options.output_file = nullptr; lane->options.discarded_output_file = nullptr; lane->report = nullptr; lane->timing = nullptr; session->processed_lane = (int) (lane == session->lanes[1]); }
+	if (lane) { lane->after_ingest = nullptr; lane->before_host_writer = nullptr; lane->options.chimeric_bam_file = nullptr; lane->options.sorted_bam_file = nullptr; lane->options.supporting_alignments_prefix = nullptr; lane->options.output_file = nullptr; lane->options.discarded_output_file = nullptr; lane->report = nullptr; lane->timing = nullptr; session->processed_lane = (int) (lane == session->lanes[1]); }
 	// The device ran out of memory while the session had two lanes (advisor, round 4): their contexts share one pool of scratch buffers, of which nothing is idle while one lane
 	// feeds and the other runs its stages, so the device library gives nothing back by itself (DeviceBuffer::release_idle_buffers).  The session does what INTEGRATION.md ("Memory")
 	// used to ask of the caller: what was fed ahead is thrown away, the second lane is closed -- the pool belongs to one context again, which gives back what it keeps for its next
@@ -1424,6 +1517,7 @@ int arriba_workflow_sample(arriba_workflow_session* session, const char* chimeri
 		const std::string first_error = g_error;
 		const std::string behind = session->queue.empty() ? std::string() : session->queue.front()->bam;
 		const std::string behind_sorted_bam = session->queue.empty() ? std::string() : session->queue.front()->sorted_bam, again_sorted_bam = lane->sorted_bam_path;
+		const std::string behind_supporting = session->queue.empty() ? std::string() : session->queue.front()->supporting, again_supporting = lane->supporting_prefix;
 		session->drain();
 		session->join_writer_of(0); session->join_writer_of(1);
 		// (an I/O error on the deferred file of an EARLIER sample stays noted -- advisor, round 5: it was dropped here, and the caller never learnt that the file is incomplete -- and is
@@ -1432,11 +1526,11 @@ int arriba_workflow_sample(arriba_workflow_session* session, const char* chimeri
 		delete session->lanes[1]; session->lanes[1] = nullptr; session->processed_lane = 0;
 		fprintf(stderr, "arriba_workflow_sample: %s -- with two samples in flight; '%s' is run again with the device to itself\n", first_error.c_str(), chimeric_bam_file);
 		session->retrying = true;
-		session->next_sorted_bam = again_sorted_bam;
+		session->next_sorted_bam = again_sorted_bam; session->next_supporting = again_supporting;
 		status = arriba_workflow_sample(session, chimeric_bam_file, output_file, discarded_output_file, report, timing);
 		session->retrying = false;
 		if (status == 0 && !behind.empty()) { // (as its caller submitted it: a failure to feed it is reported by the call that asks for it)
-			try { session->next_sorted_bam = behind_sorted_bam; session->submit(behind.c_str()); }
+			try { session->next_sorted_bam = behind_sorted_bam; session->next_supporting = behind_supporting; session->submit(behind.c_str()); }
 			catch (const Failure&) {} catch (const std::exception&) {}
 		}
 	}

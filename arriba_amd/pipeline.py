@@ -153,10 +153,11 @@ class WorkflowSession(object):
         self.timings, self._profiling_on, self.ingest_result = {}, False, None  # (what bench.py reads from a DevicePipeline)
         self._profiled = set()
 
-    def submit(self, bam, sorted_bam_file=None):
+    def submit(self, bam, sorted_bam_file=None, supporting_alignments_prefix=None):
         """the sample that comes after the one `sample` is called for next: its file is fed (PCIe, the front of read_chimeric_alignments) while the stages of that one run;
         sorted_bam_file: its records in coordinate order with their index (--sorted-bam), written when its ingest is finished"""
         self._lib.arriba_workflow_sorted_bam(self._session, sorted_bam_file.encode() if sorted_bam_file else None)
+        self._lib.arriba_workflow_supporting_alignments(self._session, supporting_alignments_prefix.encode() if supporting_alignments_prefix else None)  # (--supporting-alignments: PREFIX_ID.bam per row of its fusions file)
         if self._lib.arriba_workflow_submit(self._session, bam.encode()) != 0:
             raise ArribaError(self._lib.arriba_workflow_last_error().decode())
         if self._profiling_on:
@@ -251,12 +252,14 @@ class WorkflowSession(object):
     def _lane_contexts(self):
         return [ctx for ctx in (self._lib.arriba_workflow_lane_device(self._session, lane) for lane in (0, 1)) if ctx]
 
-    def sample(self, bam, output_file, discarded_output_file=None, sorted_bam_file=None):
+    def sample(self, bam, output_file, discarded_output_file=None, sorted_bam_file=None, supporting_alignments_prefix=None):
         """one sample, BAM file -> fusions.tsv (and discarded.tsv); returns the stages with their "(remaining=N)" counts.  sorted_bam_file (--sorted-bam): for a sample that was
         not submitted ahead; one that was says it to `submit`"""
         report, timing = _capi.WorkflowReport(), _capi.WorkflowTiming()
         if sorted_bam_file:
             self._lib.arriba_workflow_sorted_bam(self._session, sorted_bam_file.encode())
+        if supporting_alignments_prefix:  # (as sorted_bam_file: for a sample that was not submitted ahead)
+            self._lib.arriba_workflow_supporting_alignments(self._session, supporting_alignments_prefix.encode())
         if self._lib.arriba_workflow_sample(self._session, bam.encode(), output_file.encode(), discarded_output_file.encode() if discarded_output_file else None, byref(report), byref(timing)) != 0:
             raise ArribaError(self._lib.arriba_workflow_last_error().decode())
         self.ctx = self._lib.arriba_workflow_device(self._session)  # (the lane that worked on this sample)
@@ -536,6 +539,130 @@ class DevicePipeline(object):
         self.sorted_bam_seconds = seconds
         return {"records": int(info.records), "uncompressed_bytes": int(info.uncompressed_bytes), "file_bytes": int(info.file_bytes), "windows": int(info.windows), "indexed": indexed}
 
+    def build_support_pool(self, names=None):
+        """Phase 1 of --supporting-alignments: the records of the listed read names copied out of the record stream of the last read_chimeric_alignments into a pool that stays with
+        this pipeline (agpu_support_pool_build).  names=None: the QNAMEs of the fragments of the batch (entry i is fragment i); else a list of names (bytes or str), entry i is names[i].
+        Valid after read_chimeric_alignments and before the next one.  Returns {"names", "stream_records", "pooled_records", "pool_bytes"}."""
+        if not self.device_ingest or not hasattr(self.api, "support_pool_build"):
+            raise ArribaError("ERROR: the supporting alignments need the record stream of an ingest on the device (DevicePipeline(bam=...))")
+        info = _capi.SupportPoolInfo()
+        if names is None:
+            self._check(self.api.support_pool_build(self.ctx, None, None, 0, byref(info)))
+        else:
+            encoded = [name.encode() if isinstance(name, str) else bytes(name) for name in names]
+            offsets = np.zeros(len(encoded) + 1, np.uint64)
+            offsets[1:] = np.cumsum([len(name) for name in encoded], dtype=np.uint64) if encoded else 0
+            text = ctypes.create_string_buffer(b"".join(encoded), max(int(offsets[-1]), 1))
+            self._check(self.api.support_pool_build(self.ctx, ctypes.cast(text, ctypes.c_void_p), offsets.ctypes.data, len(encoded), byref(info)))
+        return {name: int(getattr(info, name)) for name in ("names", "stream_records", "pooled_records", "pool_bytes")}
+
+    def release_support_pool(self):
+        self._check(self.api.support_pool_release(self.ctx))
+
+    def support_allocated_bytes(self):
+        count = c_uint64()
+        self._check(self.api.support_allocated_bytes(self.ctx, byref(count)))
+        return int(count.value)
+
+    def written_fusion_rows(self):
+        """the data rows of the fusions file written last (not the discarded one) as the rows of write_supporting_alignments: {"ref" [n, 2], "breakpoint" [n, 2], "name_begin" [n + 1],
+        "names"}: per row the references and 0-based positions of columns 5 and 6, and the fragments of its read_identifiers (the host writer's rows and the read lists of their candidates)"""
+        lib, handle = self.session._lib, self.session._session
+        n_rows, candidate, ref, breakpoint = c_uint32(), ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
+        if lib.ahost_written_fusion_rows(handle, byref(n_rows), byref(candidate), byref(ref), byref(breakpoint)) != 0:
+            raise ArribaError("ERROR: " + lib.ahost_last_error().decode())
+        n = n_rows.value
+        if getattr(self, "_written_lists", None) is None:
+            raise ArribaError("ERROR: no fusions file has been written by this pipeline")
+        list_offset, read_lists = self._written_lists
+        take = lambda pointer, count, dtype: np.ctypeslib.as_array(ctypes.cast(pointer, ctypes.POINTER(dtype)), (count,)).copy() if count else np.zeros(0, dtype)
+        candidates = take(candidate, n, ctypes.c_uint32)
+        begins, ends = list_offset[3 * candidates.astype(np.int64)], list_offset[3 * candidates.astype(np.int64) + 3]
+        name_begin = np.zeros(n + 1, np.uint64)
+        name_begin[1:] = np.cumsum(ends - begins, dtype=np.uint64)
+        names = np.concatenate([read_lists[int(b):int(e)] for b, e in zip(begins, ends)] + [np.zeros(0, np.uint32)]).astype(np.uint32)
+        return {"ref": take(ref, 2 * n, ctypes.c_int32).reshape(n, 2), "breakpoint": take(breakpoint, 2 * n, ctypes.c_int32).reshape(n, 2), "name_begin": name_begin, "names": names}
+
+    def write_supporting_alignments(self, prefix, rows=None, window=1000000):
+        """Phase 2 of --supporting-alignments: `prefix`_ID.bam and `prefix`_ID.bam.bai for every row (ID = 1-based rank), with the records of the pool whose QNAME the row lists and that
+        overlap one of its two windows -- what scripts/extract_fusion-supporting_alignments.sh of the reference gets from samtools (agpu_supporting_*).  rows: {"ref" [n, 2],
+        "breakpoint" [n, 2] 0-based, "name_begin" [n + 1], "names": entries of the names the pool was built from}; None: the rows of the fusions file written last.  Written
+        through *.tmp; on a failure nothing of the prefix is left behind.  Returns {"rows", "records", "uncompressed_bytes", "file_bytes", "blocks", "windows", "indexed"}."""
+        import time
+        if not hasattr(self.api, "supporting_begin"):
+            raise ArribaError("ERROR: the device library has no agpu_supporting_begin")
+        if rows is None:
+            rows = self.written_fusion_rows()
+        lib, handle = self.session._lib, self.session._session
+        ref = np.ascontiguousarray(rows["ref"], dtype=np.int32).reshape(-1)
+        breakpoint = np.ascontiguousarray(rows["breakpoint"], dtype=np.int32).reshape(-1)
+        name_begin = np.ascontiguousarray(rows["name_begin"], dtype=np.uint64)
+        names = np.ascontiguousarray(rows["names"], dtype=np.uint32)
+        n_rows = ref.size // 2
+        if breakpoint.size != ref.size or name_begin.size != n_rows + 1 or (n_rows and int(name_begin[-1]) != names.size):
+            raise ArribaError("ERROR: the rows of the supporting alignments do not fit together")
+        view = _capi.SupportingRows(n_rows, ref.ctypes.data, breakpoint.ctypes.data, name_begin.ctypes.data, names.ctypes.data if names.size else None)
+        started = time.perf_counter()
+        info = _capi.SupportingInfo()
+        self._check(self.api.supporting_begin(self.ctx, byref(view), int(window), byref(info)))  # (refused before anything is written: no pool)
+        seconds = {"join": time.perf_counter() - started, "gather_and_copy": 0.0, "write": 0.0, "index": 0.0}
+        writer = None
+        try:
+            framed, framed_bytes, lengths, n_ref = ctypes.c_void_p(), c_uint64(), ctypes.c_void_p(), ctypes.c_uint32()
+            if lib.ahost_sorted_bam_header(handle, byref(framed), byref(framed_bytes), byref(lengths), byref(n_ref)) != 0:
+                raise ArribaError("ERROR: " + lib.ahost_last_error().decode())
+            ref_length = np.ctypeslib.as_array(ctypes.cast(lengths, ctypes.POINTER(ctypes.c_uint32)), (n_ref.value,)).copy() if n_ref.value else np.zeros(0, np.uint32)
+            row_bytes = np.zeros(max(n_rows, 1), np.uint64)
+            self._check(self.api.supporting_row_bytes(self.ctx, row_bytes.ctypes.data))
+            writer = lib.ahost_supporting_writer_open(prefix.encode(), framed, framed_bytes.value, n_rows, row_bytes.ctypes.data)
+            if not writer:
+                raise ArribaError("ERROR: " + lib.ahost_last_error().decode())
+            if getattr(self, "_sorted_windows", None) is None or self._sorted_windows[0] < info.window_bytes:  # (the two pinned buffers of --sorted-bam serve here as well)
+                self._free_sorted_windows()
+                buffers = [self.api.host_alloc(info.window_bytes) for _ in range(2)]
+                self._sorted_windows = (info.window_bytes, buffers)
+                if not all(buffers):
+                    self._free_sorted_windows()
+                    raise ArribaError("ERROR: " + self.api.last_error().decode())
+            capacity, buffers = self._sorted_windows
+            got, turn, written = c_uint64(), 0, 0
+            while True:
+                before = time.perf_counter()
+                self._check(self.api.supporting_next(self.ctx, buffers[turn & 1], capacity, byref(got)))
+                middle = time.perf_counter()
+                seconds["gather_and_copy"] += middle - before
+                if got.value == 0:
+                    break
+                if lib.ahost_supporting_writer_push(writer, buffers[turn & 1], got.value) != 0:
+                    raise ArribaError("ERROR: " + lib.ahost_last_error().decode())
+                seconds["write"] += time.perf_counter() - middle
+                written += got.value
+                turn += 1
+            if written != info.file_bytes:
+                raise ArribaError("ERROR: the record blocks of the supporting alignments have %d bytes, %d were announced" % (written, info.file_bytes))
+            indexed = bool((ref_length <= self.MAX_BAI_REFERENCE).all())
+            before = time.perf_counter()
+            index = _capi.SupportingIndex()
+            self._check(self.api.supporting_index(self.ctx, framed_bytes.value, byref(index)))
+            arrays = {name: np.zeros(max(size, 1), dtype) for name, size, dtype in (("row_first", n_rows + 1, np.uint64), ("ref", index.n_records, np.int32), ("pos", index.n_records, np.int32),
+                      ("end_flag", index.n_records, np.uint32), ("bin", index.n_records, np.uint32), ("begin", index.n_records, np.uint64), ("end", index.n_records, np.uint64))}
+            for name, array in arrays.items():
+                setattr(index, name, array.ctypes.data)
+            self._check(self.api.supporting_index(self.ctx, framed_bytes.value, byref(index)))
+            if lib.ahost_supporting_writer_index(writer, byref(index), ref_length.ctypes.data if n_ref.value else None, n_ref.value) != 0:
+                raise ArribaError("ERROR: " + lib.ahost_last_error().decode())
+            seconds["index"] = time.perf_counter() - before
+            status, writer = lib.ahost_supporting_writer_close(writer, 1), None
+            if status != 0:
+                raise ArribaError("ERROR: " + lib.ahost_last_error().decode())
+        finally:
+            if writer:
+                lib.ahost_supporting_writer_close(writer, 0)
+            self.api.supporting_end(self.ctx)
+        seconds["total"] = time.perf_counter() - started
+        self.supporting_seconds = seconds
+        return {"rows": int(info.rows), "records": int(info.records), "uncompressed_bytes": int(info.uncompressed_bytes), "file_bytes": int(info.file_bytes), "blocks": int(info.blocks), "windows": int(info.windows), "indexed": indexed}
+
     def _free_sorted_windows(self):
         if getattr(self, "_sorted_windows", None) is not None:
             for pointer in self._sorted_windows[1]:
@@ -676,13 +803,15 @@ class DevicePipeline(object):
                      max_genomic_breakpoint_distance=100000, strandedness=None, evalue_cutoff=0.3,
                      min_itd_support=10, min_itd_allele_fraction=0.07, high_expression_quantile=0.998, min_spliced_events=4, min_anchor_length=23,
                      max_homolog_identity=0.3, max_itd_length=100, fill_sequence_gaps=False, top_viral_contigs=5, viral_contig_min_covered_fraction=0.05,
-                     print_extra_info_for_discarded_fusions=False, log=None, sorted_bam_file=None):
+                     print_extra_info_for_discarded_fusions=False, log=None, sorted_bam_file=None, supporting_alignments_prefix=None, supporting_alignments_window=1000000):
         """The reference's main() behind read_chimeric_alignments (source/arriba.cpp:119-610) with its default parameters: the read-level cascade, find_fusions,
         every candidate-level filter in the reference's order, assign_confidence, and the two output files.  `log` receives (stage, remaining) pairs --
         the numbers the reference prints as "(remaining=N)".  Filters switched off with -f are skipped by the stages themselves (agpu_params.filter_enabled)."""
         note = log if log is not None else (lambda stage, remaining: None)
         if sorted_bam_file:  # first: the record stream is still in HBM (it is given back when the stages need the memory)
             self.write_sorted_bam(sorted_bam_file)
+        if supporting_alignments_prefix:  # (--supporting-alignments, phase 1: the records of the names of the batch leave the stream while it is there)
+            self.build_support_pool()
         self.run_read_level(strandedness, top_viral_contigs, viral_contig_min_covered_fraction)
         note("find_fusions", self.find_fusions())
         self.upload_coverage()
@@ -722,6 +851,9 @@ class DevicePipeline(object):
         if protein_domains_file:
             self.session.load_protein_domains(protein_domains_file)
         self.write_fusions(output_file, discarded=False, max_itd_length=max_itd_length, fill_sequence_gaps=fill_sequence_gaps)
+        if supporting_alignments_prefix:  # (phase 2: the rows of the file are fixed)
+            self.write_supporting_alignments(supporting_alignments_prefix, None, supporting_alignments_window)
+            self.release_support_pool()
         if discarded_output_file:
             self.write_fusions(discarded_output_file, discarded=True, print_extra_info=print_extra_info_for_discarded_fusions, max_itd_length=max_itd_length, fill_sequence_gaps=fill_sequence_gaps)
 
@@ -921,6 +1053,8 @@ class DevicePipeline(object):
                 raise ArribaError("ERROR: " + lib.ahost_last_error().decode())
             mark("rows into the session")
         self._emit_fusions(view, path, discarded, print_extra_info, max_itd_length, fill_sequence_gaps, detached)
+        if not discarded:
+            self._written_lists = (np.asarray(list_offset), np.asarray(read_lists))  # (for written_fusion_rows: the fragments of the rows' read_identifiers)
         mark("ahost_write_fusions")
         self.writer_seconds = {name: round(at - marks[k][1], 4) for k, (name, at) in enumerate(marks[1:])}  # where the time of the output side went (bench.py reports it)
 

@@ -297,6 +297,67 @@ int agpu_sorted_bam_begin(agpu_ctx* ctx, agpu_sorted_bam_info* info);
 int agpu_sorted_bam_next(agpu_ctx* ctx, void* pinned, uint64_t capacity, uint64_t* bytes);
 int agpu_sorted_bam_index(agpu_ctx* ctx, uint64_t first_block_file_offset, const uint32_t* ref_length, uint32_t n_ref, agpu_sorted_bam_index_arrays* index);
 int agpu_sorted_bam_end(agpu_ctx* ctx);
+/* ---- one small sorted, indexed BAM file per row of fusions.tsv, with the alignments of the row's read_identifiers that lie near its breakpoints: what the reference's
+ * scripts/extract_fusion-supporting_alignments.sh gets from samtools view / sort / index, from the record stream in HBM (arriba_amd/csrc/device/agpu_supporting.hip,
+ * supporting_core.hpp).  Two phases, because the stream goes to the next feed right behind the ingest and the rows exist only at the end of the sample:
+ *   agpu_support_pool_build   behind agpu_ingest_finish, before the next agpu_ingest_begin on this context or its sibling (the refusals of agpu_sorted_bam_begin): every record
+ *                             of the stream whose QNAME is one of the names and that has a reference is copied into a pool of the context, in coordinate order (the key of
+ *                             --sorted-bam, ties in input order).  names == NULL: the QNAMEs of the fragments of the batch the ingest built ("QNAME,HI": the name ends in front of its
+ *                             last ','), entry i is fragment i.  Otherwise names[name_offset[i] .. name_offset[i + 1]) is entry i of an explicit list.  The pool and its tables belong to
+ *                             the context until agpu_support_pool_release or the next build; they are not given back under memory pressure and do not change hands between the lanes
+ *                             of a session.  AGPU_ERR_NO_MEMORY if they do not fit.
+ *   agpu_supporting_begin     the rows: two (refID, 0-based breakpoint) pairs each and the entries of the names that support them (CSR).  A record goes into the file of a row when
+ *                             its QNAME equals a name of the row byte for byte and it overlaps one of the two windows [max(P,W)-W, max(P,W)+W] (1-based, closed, P = breakpoint + 1);
+ *                             once, in pool order.  info: what follows.
+ *   agpu_supporting_row_bytes the bytes of the record blocks of every row's file (payload + 31 per block; 0 for a row without records)
+ *   agpu_supporting_next      the next window of finished record blocks of ALL rows, one row's behind the other's (a whole number of blocks; the last block of a row is short) into
+ *                             pinned[0 .. capacity); *bytes == 0 at the end.  The window behind it is gathered meanwhile: take two pinned buffers in turn.
+ *   agpu_supporting_index     per record of the files, in file order: row_first [n_rows + 1], reference, position, end | unmapped << 31, bin, and the virtual offsets of its first byte and of
+ *                             the byte behind it for record blocks that begin at first_block_file_offset of their file.  Pointers NULL: the sizes.  The host makes the BAI files of them.
+ *   agpu_supporting_end       the context is where it was before agpu_supporting_begin; the pool stays
+ * ARRIBA_SUPPORTING_WINDOW: bytes of the device staging buffer of a window (default 64 MiB, at least one block).  ARRIBA_SUPPORT_HASH_BITS (a test knob, default 64): bits of the hash
+ * of a name that are used. */
+typedef struct {
+	uint64_t names;               /* entries of the list of names */
+	uint64_t stream_records;      /* records of the stream that were looked at */
+	uint64_t pooled_records;      /* ... of them in the pool */
+	uint64_t pool_bytes;          /* their bytes */
+} agpu_support_pool_info;
+typedef struct {
+	uint32_t n_rows;
+	const int32_t* ref;           /* [2 * n_rows] reference of the two breakpoints of a row (-1: a contig the BAM header does not have) */
+	const int32_t* breakpoint;    /* [2 * n_rows] 0-based */
+	const uint64_t* name_begin;   /* [n_rows + 1] */
+	const uint32_t* names;        /* [name_begin[n_rows]] entries of the names the pool was built from */
+} agpu_supporting_rows;
+typedef struct {
+	uint64_t rows;
+	uint64_t records;             /* records of all files */
+	uint64_t uncompressed_bytes;  /* their bytes */
+	uint64_t file_bytes;          /* bytes of the record blocks of all files */
+	uint64_t blocks;
+	uint64_t windows;             /* calls of agpu_supporting_next that return bytes */
+	uint64_t window_bytes;        /* capacity a window needs */
+} agpu_supporting_info;
+typedef struct {
+	uint32_t n_rows;
+	uint64_t n_records;
+	uint64_t* row_first;          /* [n_rows + 1] the first record of every row */
+	int32_t* ref;                 /* [n_records] */
+	int32_t* pos;
+	uint32_t* end_flag;           /* end coordinate, bit 31: unmapped (flag 0x4) */
+	uint32_t* bin;                /* 0xFFFFFFFF: not indexed */
+	uint64_t* begin;              /* virtual offsets */
+	uint64_t* end;
+} agpu_supporting_index_arrays;
+int agpu_support_pool_build(agpu_ctx* ctx, const char* names, const uint64_t* name_offset, uint64_t n_names, agpu_support_pool_info* info);
+int agpu_supporting_begin(agpu_ctx* ctx, const agpu_supporting_rows* rows, int64_t window, agpu_supporting_info* info);
+int agpu_supporting_row_bytes(agpu_ctx* ctx, uint64_t* row_file_bytes /* [n_rows] */);
+int agpu_supporting_next(agpu_ctx* ctx, void* pinned, uint64_t capacity, uint64_t* bytes);
+int agpu_supporting_index(agpu_ctx* ctx, uint64_t first_block_file_offset, agpu_supporting_index_arrays* index);
+int agpu_supporting_end(agpu_ctx* ctx);
+int agpu_support_pool_release(agpu_ctx* ctx);
+int agpu_support_allocated_bytes(agpu_ctx* ctx, uint64_t* bytes); /* of the "support.*" buffers of the context: 0 as long as the option was never used on it, and behind agpu_support_pool_release */
 /* what the host's sequential stages and its output writer need from a batch that lives on the device:
  *   agpu_get_viral_read_counts   mapped_viral_reads_by_contig (source/read_chimeric_alignments.cpp:735-739)
  *   agpu_get_coverage            coverage_t as the reference holds it (16-bit saturating windows, start/end flags); sizes by coverage_window_offset

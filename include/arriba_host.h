@@ -92,6 +92,27 @@ void ahost_sorted_bam_eof(uint8_t* block /* [28] */);
  /*  ahost_sorted_bam_file       the same for a file (BAM in BGZF, gzip or raw; SAM text): read whole into host memory -- what --host-ingest does for --sorted-bam */
 int ahost_sorted_bam_file(const char* input_path, const char* path, agpu_sorted_bam_info* info /* may be NULL */);
 int ahost_sorted_bam_write(const void* input_header, size_t header_size, const void* records, size_t size, const char* path, agpu_sorted_bam_info* info /* may be NULL */);
+/* ---- --supporting-alignments: the host side of agpu_support_pool_build / agpu_supporting_* (include/arriba_gpu.h) -- one sorted, indexed BAM file per row of fusions.tsv with
+ * the alignments of the row's read_identifiers near its breakpoints (the reference's scripts/extract_fusion-supporting_alignments.sh), PREFIX_ID.bam and PREFIX_ID.bam.bai, ID = 1-based
+ * rank of the row ----
+ *   ahost_written_fusion_rows        the data rows of the fusions file (-o, not -O) the session wrote last, in their order: the candidate of the table each was made from, and per
+ *                                    row two (refID of the BAM header, 0-based breakpoint) pairs as columns 5 and 6 print them (-1: a contig the BAM header does not have).  The
+ *                                    supporting fragments of row r are entries list_offset[3 c] .. list_offset[3 c + 3] of read_lists of that table, c = candidate[r].
+ *                                    Valid until the next call on the session.
+ *   ahost_supporting_writer_*        cuts the framed record blocks of all rows (agpu_supporting_next) into the files, each with the header of --sorted-bam (ahost_sorted_bam_header)
+ *                                    and the end-of-file block; _index makes the BAI files from the arrays of agpu_supporting_index (a reference longer than 2^29 bases: none, and the
+ *                                    warning of --sorted-bam); _close(commit = 1) renames the *.tmp files; _close(0), or any failure: nothing of the prefix is left behind
+ *   ahost_supporting_alignments      arriba_amd/csrc/device/supporting_core.hpp stepped on the host over BAM records in host memory, with an explicit list of names: the same files
+ *                                    as the device gives (its comparator; the CPU tier)
+ *   ahost_supporting_alignments_file the same for a file and the rows ahost_written_fusion_rows gives, with the names of the batch of a host ingest: what --host-ingest runs */
+typedef struct ahost_supporting_writer ahost_supporting_writer;
+int ahost_written_fusion_rows(ahost_session* session, uint32_t* n_rows, const uint32_t** candidate, const int32_t** ref /* [2 * n_rows] */, const int32_t** breakpoint /* [2 * n_rows] */);
+ahost_supporting_writer* ahost_supporting_writer_open(const char* prefix, const void* framed_header, uint64_t framed_bytes, uint32_t n_rows, const uint64_t* row_file_bytes);
+int ahost_supporting_writer_push(ahost_supporting_writer* writer, const void* bytes, uint64_t size);
+int ahost_supporting_writer_index(ahost_supporting_writer* writer, const agpu_supporting_index_arrays* index, const uint32_t* ref_length, uint32_t n_ref);
+int ahost_supporting_writer_close(ahost_supporting_writer* writer, int commit);
+int ahost_supporting_alignments(const void* input_header, size_t header_size, const void* records, size_t size, const char* names, const uint64_t* name_offset, uint64_t n_names,
+                                const agpu_supporting_rows* rows, int64_t window, const char* prefix, agpu_supporting_info* info /* may be NULL */);
 int ahost_adopt_device_ingest(ahost_session* session, const agpu_ingest_result* result, const uint64_t* viral_read_counts, const uint16_t* coverage, const uint8_t* fragment_starts, const uint8_t* fragment_ends);
 int ahost_set_batch_rows(ahost_session* session, const agpu_batch_rows* rows, const uint32_t* fragments /* [rows->n] ascending: the fragment every row holds; NULL: row k holds the fragment
                          of entry k of the read lists of the table the next ahost_write_fusions writes (the reads of a candidate next to each other; the table then carries read_filter_of_rows) */);
@@ -121,6 +142,8 @@ typedef struct {
 } ahost_fusion_table;
 int ahost_write_fusions(ahost_session* session, const ahost_fusion_table* table, const char* path, int write_discarded, int print_extra_info, unsigned int max_itd_length, int max_mate_gap,
                         int fill_sequence_gaps /* -I: complete the fusion transcript from the assembly along the chosen transcripts */);
+/* --supporting-alignments under --host-ingest (described with ahost_supporting_alignments above) */
+int ahost_supporting_alignments_file(ahost_session* session, const ahost_fusion_table* table, const char* input_path, int64_t window, const char* prefix, agpu_supporting_info* info /* may be NULL */);
 /* The last output file of a sample written while the session reads the next one (arriba_workflow_defer_output): ahost_detach_sample moves what the writer reads of the SAMPLE --
  * coverage_t, the rows of ahost_set_batch_rows, the contig names as its header left them -- out of the session (which then holds no sample until its next ingest);
  * ahost_write_fusions_of writes from there on any thread, beside ahost_bam_open / ahost_bam_next / ahost_adopt_device_ingest of the next sample on the same session, with the

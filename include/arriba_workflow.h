@@ -47,6 +47,12 @@ typedef struct {
 	const char* sorted_bam_file;          /* --sorted-bam; NULL = none.  The records of -x in coordinate order as a BAM file of stored BGZF blocks, and FILE.bai next to it (what run_arriba.sh:47-51
 	                                         gets from samtools sort / index), written behind read_chimeric_alignments from the record stream in HBM (include/arriba_gpu.h: agpu_sorted_bam_*).
 	                                         Of arriba_workflow_run's sample; the samples of a session say theirs with arriba_workflow_sorted_bam.  Not for one sample over several ranks. */
+	const char* supporting_alignments_prefix; /* --supporting-alignments; NULL = none.  PREFIX_ID.bam and PREFIX_ID.bam.bai for every data row of output_file (ID = 1-based rank of the row): the
+	                                         alignments of the row's read_identifiers that lie within supporting_alignments_window of one of its breakpoints, sorted and indexed (what the reference's
+	                                         scripts/extract_fusion-supporting_alignments.sh gets from samtools), from the record stream in HBM (include/arriba_gpu.h: agpu_support_pool_build,
+	                                         agpu_supporting_*).  Of arriba_workflow_run's sample; the samples of a session say theirs with arriba_workflow_supporting_alignments.
+	                                         Not for one sample over several ranks. */
+	int64_t supporting_alignments_window; /* --supporting-window: SEARCH_WINDOW of the script; 0 = its default, 1000000 */
 } arriba_workflow_options;
 
 /* what the reference prints as "(remaining=N)" / "(total=N)" / "(marked=N)", in the order of the stages; stage names as in the reference's source */
@@ -85,6 +91,7 @@ typedef struct { /* seconds of one sample, by part (wall clock of the calling th
 	                            rank held the whole batch (one rank, or the split by an all-gather of the batch) */
 	double exchanged_bytes;  /*   ... and the bytes this rank received from the others in the exchanges of the sample (host collectives) */
 	double sorted_bam;       /* --sorted-bam: keys, sort, gather, copy back, the two files (inside `ingest`; beside the sample in front when the ingest was finished ahead) */
+	double supporting_alignments; /* --supporting-alignments: the pool behind the ingest (name table, marks, compaction) and the files behind fusions.tsv (join, gather, copy back, files, indexes) */
 } arriba_workflow_timing;
 /* options->chimeric_bam_file, output_file and discarded_output_file are not used by open (they belong to a sample); NULL + arriba_workflow_last_error() on failure */
 arriba_workflow_session* arriba_workflow_open(const arriba_workflow_options* options);
@@ -100,6 +107,9 @@ int arriba_workflow_submit(arriba_workflow_session* session, const char* chimeri
  * that finishes the ingest of that sample, before the stream in HBM goes to the feed of the sample behind it; if it cannot be written the sample fails with the message, FILE.tmp and
  * FILE.bai.tmp are removed, and the session takes the next sample. */
 int arriba_workflow_sorted_bam(arriba_workflow_session* session, const char* sorted_bam_file);
+/* --supporting-alignments of the sample that is submitted NEXT, in the same way; NULL: none.  The pool of its supporting alignments is built by the thread that finishes its ingest and
+ * belongs to its lane until its fusions file is written; the window is options.supporting_alignments_window of arriba_workflow_open. */
+int arriba_workflow_supporting_alignments(arriba_workflow_session* session, const char* prefix);
 /* (If the device runs out of memory while two samples are in flight, arriba_workflow_sample throws away what was fed ahead, closes the second lane, runs its sample again with the device
  * to itself and submits the other sample again behind it -- once; a sample that does not fit the device alone fails the call.  INTEGRATION.md, "Memory".) */
 /* on: arriba_workflow_sample returns when the last output file of the sample (-O if given, else -o) has everything it needs off the device; the file is formatted and written
