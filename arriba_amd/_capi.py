@@ -256,6 +256,9 @@ def bind_device_api(lib, prefix="agpu_"):
         "sorted_bam_next": (c_int, [ctx, c_void_p, c_uint64, POINTER(c_uint64)]),
         "sorted_bam_index": (c_int, [ctx, c_uint64, c_void_p, c_uint32, POINTER(SortedBamIndex)]),
         "sorted_bam_end": (c_int, [ctx]),
+        "sorted_bam_set_compression": (c_int, [ctx, c_int]),
+        "sorted_bam_compressed_bytes": (c_int, [ctx, POINTER(c_uint64)]),
+        "sorted_bam_compression_allocated_bytes": (c_int, [ctx, POINTER(c_uint64)]),
         "support_pool_build": (c_int, [ctx, c_void_p, c_void_p, c_uint64, POINTER(SupportPoolInfo)]),
         "supporting_begin": (c_int, [ctx, POINTER(SupportingRows), ctypes.c_int64, POINTER(SupportingInfo)]),
         "supporting_row_bytes": (c_int, [ctx, c_void_p]),
@@ -345,6 +348,9 @@ def bind_host_api(lib):
         "ahost_sorted_bam_eof": (None, [c_void_p]),
         "ahost_sorted_bam_file": (c_int, [c_char_p, c_char_p, POINTER(SortedBamInfo)]),
         "ahost_sorted_bam_write": (c_int, [c_void_p, c_size_t, c_void_p, c_size_t, c_char_p, POINTER(SortedBamInfo)]),
+        "ahost_sorted_bam_level": (c_int, [c_void_p, c_size_t, c_uint64, c_void_p, c_uint32, c_int, POINTER(c_void_p), POINTER(SortedBamInfo), POINTER(SortedBamIndex)]),
+        "ahost_sorted_bam_file_level": (c_int, [c_char_p, c_char_p, c_int, POINTER(SortedBamInfo)]),
+        "ahost_sorted_bam_write_level": (c_int, [c_void_p, c_size_t, c_void_p, c_size_t, c_char_p, c_int, POINTER(SortedBamInfo)]),
         "ahost_written_fusion_rows": (c_int, [session, POINTER(c_uint32), POINTER(c_void_p), POINTER(c_void_p), POINTER(c_void_p)]),
         "ahost_supporting_writer_open": (c_void_p, [c_char_p, c_void_p, c_uint64, c_uint32, c_void_p]),
         "ahost_supporting_writer_push": (c_int, [c_void_p, c_void_p, c_uint64]),
@@ -374,7 +380,7 @@ class WorkflowOptions(ctypes.Structure):
                                               "protein_domains_file", "genomic_breakpoints_file", "interesting_contigs", "viral_contigs", "gtf_features")] + [
         ("device", Params), ("min_itd_support", c_uint32), ("min_itd_allele_fraction", c_float), ("high_expression_quantile", c_float), ("min_spliced_events", c_uint32), ("min_anchor_length", c_uint32),
         ("max_homolog_identity", c_float), ("top_viral_contigs", c_uint32), ("viral_contig_min_covered_fraction", c_float), ("max_genomic_breakpoint_distance", c_int32),
-        ("print_extra_info_for_discarded_fusions", c_uint8), ("fill_sequence_gaps", c_uint8), ("device_index", c_int), ("log_to_stdout", c_uint8), ("host_ingest", c_uint8), ("sorted_bam_file", c_char_p), ("supporting_alignments_prefix", c_char_p), ("supporting_alignments_window", ctypes.c_int64)]
+        ("print_extra_info_for_discarded_fusions", c_uint8), ("fill_sequence_gaps", c_uint8), ("device_index", c_int), ("log_to_stdout", c_uint8), ("host_ingest", c_uint8), ("sorted_bam_file", c_char_p), ("supporting_alignments_prefix", c_char_p), ("supporting_alignments_window", ctypes.c_int64), ("sorted_bam_compression", c_int)]
 
 
 class WorkflowStage(ctypes.Structure):
@@ -419,6 +425,7 @@ def workflow_library():
         lib.arriba_workflow_submit.argtypes = [c_void_p, c_char_p]; lib.arriba_workflow_submit.restype = c_int
         lib.arriba_workflow_sorted_bam.argtypes = [c_void_p, c_char_p]; lib.arriba_workflow_sorted_bam.restype = c_int
         lib.arriba_workflow_supporting_alignments.argtypes = [c_void_p, c_char_p]; lib.arriba_workflow_supporting_alignments.restype = c_int
+        lib.arriba_workflow_sorted_bam_compression.argtypes = [c_void_p, c_int]; lib.arriba_workflow_sorted_bam_compression.restype = c_int
         lib.arriba_workflow_cancel.argtypes = [c_void_p]; lib.arriba_workflow_cancel.restype = c_int
         lib.arriba_workflow_defer_output.argtypes = [c_void_p, c_int]; lib.arriba_workflow_defer_output.restype = c_int
         lib.arriba_workflow_finish_ahead.argtypes = [c_void_p, c_int]; lib.arriba_workflow_finish_ahead.restype = c_int

@@ -201,6 +201,8 @@ struct agpu_ctx {
 	bool last_ingest_kept = false, last_ingest_part_of_sample = false, sorted_bam_active = false, sorted_bam_index_ready = false;
 	uint64_t sorted_bam_records = 0, sorted_bam_bytes = 0, sorted_bam_blocks = 0, sorted_bam_window_blocks = 0, sorted_bam_next_block = 0, sorted_bam_gathered_block = ~0ull, sorted_bam_index_first = 0;
 	uint64_t sorted_bam_chunks = 0, sorted_bam_intervals = 0, sorted_bam_no_coor = 0; uint32_t sorted_bam_n_ref = 0;
+	int sorted_bam_level_next = 0, sorted_bam_level = 0; // agpu_sorted_bam_set_compression: of the next agpu_sorted_bam_begin; of the begin ... end under way
+	uint64_t sorted_bam_compressed_bytes = 0;            // of the windows fetched so far
 	agpu::SupportState support; // --supporting-alignments (agpu_supporting.hip)
 	// A pushed piece: copied on the context's stream (piece_copied: the caller's buffer is free), unwrapped and CRC-checked on a stream of its own (piece_stream; piece_ready: its
 	// bytes are in the stream, piece_done: the raw bytes are not needed any more), so that the copy of the next piece never waits for a kernel; AGPU_PIECE_SLOTS raw buffers in turn

@@ -2,7 +2,8 @@
 // reference's workflow script gets from `samtools sort` + `samtools index` behind the call of arriba (run_arriba.sh:47-51).  Everything that decides a byte of the two files
 // is here and is shared by the kernels of agpu_sorted_bam.hip and the host stepping of arriba_amd/csrc/host/sorted_bam.cpp:
 //   sbam_parse        the sort key of a record (refID as unsigned, pos + 1, the reverse-strand flag), its size, and its end coordinate from the CIGAR of the record
-//   sbam_voffset      the virtual offset of a byte of the sorted uncompressed stream: blocks of exactly SBAM_PAYLOAD bytes, so block positions are arithmetic
+//   sbam_voffset      the virtual offset of a byte of the sorted uncompressed stream: blocks of exactly SBAM_PAYLOAD bytes, so block positions are arithmetic (stored
+//                     blocks) or come from a table of block file offsets (compressed blocks: deflate_out_core.hpp)
 //   sbam_head_byte / sbam_tail_byte   the 23 bytes in front of the payload of a stored block and the 8 behind it
 //   sbam_reg2bin, sbam_indexed, sbam_window_range   the bin and the 16 kb windows of a record
 // Records are moved byte for byte; the `bin` field of a record is never read (generators write constants there).
@@ -100,6 +101,11 @@ AGPU_HD bool sbam_window_range(int32_t pos, int32_t end, uint64_t windows, uint6
 AGPU_HD uint64_t sbam_block_count(uint64_t uncompressed) { return (uncompressed + SBAM_PAYLOAD - 1) / SBAM_PAYLOAD; }
 AGPU_HD uint64_t sbam_voffset(uint64_t first_block_file_offset, uint64_t uncompressed_offset) {
 	return (first_block_file_offset + uncompressed_offset / SBAM_PAYLOAD * SBAM_BLOCK) << 16 | uncompressed_offset % SBAM_PAYLOAD;
+}
+
+// ... of a file whose blocks have sizes of their own (--sorted-bam-compression): block_file_offset[b] is where block b begins in the file, one entry more for the end
+AGPU_HD uint64_t sbam_voffset(const uint64_t* block_file_offset, uint64_t uncompressed_offset) {
+	return block_file_offset[uncompressed_offset / SBAM_PAYLOAD] << 16 | uncompressed_offset % SBAM_PAYLOAD;
 }
 
 // byte i < SBAM_HEAD in front of a payload of n bytes

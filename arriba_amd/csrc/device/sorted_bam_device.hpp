@@ -1,6 +1,7 @@
 // sorted_bam_device.hpp -- what the kernels that write stored BGZF blocks share (agpu_sorted_bam.hip: sorted_bam_gather_kernel; agpu_supporting.hip: support_pool_copy_kernel,
 // supporting_gather_kernel): the copy of a run of bytes by one wavefront (destination-aligned words, the source read with aligned words and shifts, ragged ends by bytes), and
-// the frame of a block around a payload that lies in LDS (tables and header bytes in front, CRC-32 from LDS, trailer, 16-byte stores behind).  Device code only.
+// the frame of a block around a payload that lies in LDS (tables and header bytes in front, CRC-32 from LDS, trailer, 16-byte stores behind; the compressing gather of
+// agpu_sorted_bam.hip takes the CRC and the stores by themselves).  Device code only.
 #ifndef AGPU_SORTED_BAM_DEVICE_HPP
 #define AGPU_SORTED_BAM_DEVICE_HPP 1
 
@@ -42,12 +43,10 @@ __device__ __forceinline__ void sbam_frame_begin(SbamFrameShared& shared, const 
 	if (t < SBAM_HEAD) image[pad + t] = sbam_head_byte(t, length);
 }
 
-// Behind a barrier that follows the last write of the payload: the CRC-32 of image[pad + SBAM_HEAD ..) taken from LDS (64 bytes per lane, joined pairwise), the trailer, and the
-// block stored to block_out (pad = block_out & 15): whole 16-byte chunks of memory with one store each, the ragged ends byte by byte (the neighbours' bytes of those chunks are
-// theirs).  `partial`: SBAM_GATHER_THREADS words of LDS.  All SBAM_GATHER_THREADS lanes of the workgroup call it.
-__device__ __forceinline__ void sbam_frame_finish(SbamFrameShared& shared, uint32_t* partial, uint32_t pad, uint32_t length, uint8_t* block_out, uint32_t t) {
+// Behind a barrier that follows the last write of the payload: the CRC-32 of image[payload_at .. payload_at + length) taken from LDS (64 bytes per lane, joined pairwise);
+// every lane gets it, behind a barrier.  `partial`: SBAM_GATHER_THREADS words of LDS.  All SBAM_GATHER_THREADS lanes of the workgroup call it.
+__device__ __forceinline__ uint32_t sbam_frame_crc(SbamFrameShared& shared, uint32_t* partial, uint32_t payload_at, uint32_t length, uint32_t t) {
 	uint8_t* const image = (uint8_t*) shared.image;
-	const uint32_t payload_at = pad + SBAM_HEAD;
 	if (length < SBAM_CRC_SERIAL_BELOW) {
 		if (t == 0) partial[0] = ~crc32_of(shared.crc_byte_table, image + payload_at, length);
 	} else {
@@ -70,11 +69,14 @@ __device__ __forceinline__ void sbam_frame_finish(SbamFrameShared& shared, uint3
 		}
 	}
 	__syncthreads();
-	const uint32_t crc = ~partial[0];
-	if (t < SBAM_TAIL) image[payload_at + length + t] = sbam_tail_byte(t, crc, length);
-	__syncthreads();
+	return ~partial[0];
+}
 
-	const uint32_t size = length + SBAM_HEAD + SBAM_TAIL, image_end = pad + size;
+// image[pad .. pad + size) stored to block_out (pad = block_out & 15): whole 16-byte chunks of memory with one store each, the ragged ends byte by byte (the neighbours' bytes of
+// those chunks are theirs).  Behind a barrier that follows the last write of the image.
+__device__ __forceinline__ void sbam_frame_store(SbamFrameShared& shared, uint32_t pad, uint32_t size, uint8_t* block_out, uint32_t t) {
+	uint8_t* const image = (uint8_t*) shared.image;
+	const uint32_t image_end = pad + size;
 	const uint32_t first_chunk = (pad + 15) / 16, end_chunk = image_end / 16;
 	uint4* const aligned_out = (uint4*) (block_out - pad);
 	for (uint32_t chunk = first_chunk + t; chunk < end_chunk; chunk += SBAM_GATHER_THREADS) aligned_out[chunk] = shared.image[chunk];
@@ -82,6 +84,16 @@ __device__ __forceinline__ void sbam_frame_finish(SbamFrameShared& shared, uint3
 	if (pad + t < head_end) block_out[t] = image[pad + t];
 	const uint32_t tail_begin = end_chunk * 16 > head_end ? end_chunk * 16 : head_end;
 	if (tail_begin + t < image_end) block_out[tail_begin + t - pad] = image[tail_begin + t];
+}
+
+// Behind a barrier that follows the last write of the payload: the CRC-32 of the payload, the trailer, and the stored block to block_out
+__device__ __forceinline__ void sbam_frame_finish(SbamFrameShared& shared, uint32_t* partial, uint32_t pad, uint32_t length, uint8_t* block_out, uint32_t t) {
+	uint8_t* const image = (uint8_t*) shared.image;
+	const uint32_t payload_at = pad + SBAM_HEAD;
+	const uint32_t crc = sbam_frame_crc(shared, partial, payload_at, length, t);
+	if (t < SBAM_TAIL) image[payload_at + length + t] = sbam_tail_byte(t, crc, length);
+	__syncthreads();
+	sbam_frame_store(shared, pad, length + SBAM_HEAD + SBAM_TAIL, block_out, t);
 }
 
 }

@@ -617,9 +617,12 @@ int ahost_sorted_bam_header_of(const void* input_header, size_t size, const uint
 	} catch (const std::exception& e) { g_error = e.what(); return -1; }
 }
 int ahost_sorted_bam(const void* records, size_t size, uint64_t first_block_file_offset, const uint32_t* ref_length, uint32_t n_ref, const uint8_t** blocks, agpu_sorted_bam_info* info, agpu_sorted_bam_index_arrays* index) {
+	return ahost_sorted_bam_level(records, size, first_block_file_offset, ref_length, n_ref, 0, blocks, info, index);
+}
+int ahost_sorted_bam_level(const void* records, size_t size, uint64_t first_block_file_offset, const uint32_t* ref_length, uint32_t n_ref, int level, const uint8_t** blocks, agpu_sorted_bam_info* info, agpu_sorted_bam_index_arrays* index) {
 	if ((!records && size > 0) || !blocks || !info) { g_error = "null argument"; return -1; }
 	try {
-		sorted_bam_of((const uint8_t*) records, size, first_block_file_offset, index != NULL ? ref_length : NULL, n_ref, g_sorted_bam);
+		sorted_bam_of((const uint8_t*) records, size, first_block_file_offset, index != NULL ? ref_length : NULL, n_ref, g_sorted_bam, level);
 		*blocks = g_sorted_bam.blocks.data(); *info = g_sorted_bam.info;
 		if (index != NULL) *index = g_sorted_bam.view(n_ref);
 		return 0;
@@ -639,8 +642,11 @@ int ahost_sorted_bam_write_index(const agpu_sorted_bam_index_arrays* index, cons
 }
 void ahost_sorted_bam_eof(uint8_t* block) { for (uint32_t i = 0; i < agpu::SBAM_EOF_BYTES; ++i) block[i] = agpu::sbam_eof_byte(i); }
 int ahost_sorted_bam_write(const void* input_header, size_t header_size, const void* records, size_t size, const char* path, agpu_sorted_bam_info* info) {
+	return ahost_sorted_bam_write_level(input_header, header_size, records, size, path, 0, info);
+}
+int ahost_sorted_bam_write_level(const void* input_header, size_t header_size, const void* records, size_t size, const char* path, int level, agpu_sorted_bam_info* info) {
 	if (!input_header || (!records && size > 0) || !path) { g_error = "null argument"; return -1; }
-	try { sorted_bam_write((const uint8_t*) input_header, header_size, (const uint8_t*) records, size, path, info); return 0; }
+	try { sorted_bam_write((const uint8_t*) input_header, header_size, (const uint8_t*) records, size, path, info, level); return 0; }
 	catch (const std::exception& e) { g_error = e.what(); return -1; }
 }
 namespace {
@@ -658,12 +664,14 @@ uint64_t read_whole_bam(const char* input_path, std::vector<uint8_t>& stream) {
 	return at;
 }
 }
-int ahost_sorted_bam_file(const char* input_path, const char* path, agpu_sorted_bam_info* info) {
+int ahost_sorted_bam_file(const char* input_path, const char* path, agpu_sorted_bam_info* info) { return ahost_sorted_bam_file_level(input_path, path, 0, info); }
+int ahost_sorted_bam_file_level(const char* input_path, const char* path, int level, agpu_sorted_bam_info* info) {
 	if (!input_path || !path) { g_error = "null argument"; return -1; }
+	if (level != 0 && level != 1) { g_error = "the compression level of a sorted BAM file is 0 (stored) or 1"; return -1; }
 	try {
 		std::vector<uint8_t> stream;
 		const uint64_t at = read_whole_bam(input_path, stream);
-		sorted_bam_write(stream.data(), at, stream.data() + at, stream.size() - at, path, info);
+		sorted_bam_write(stream.data(), at, stream.data() + at, stream.size() - at, path, info, level);
 		return 0;
 	} catch (const std::exception& e) { g_error = e.what(); return -1; }
 }

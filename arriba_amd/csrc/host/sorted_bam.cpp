@@ -12,6 +12,7 @@
 #include "arriba_host.h"
 #include "../device/crc32_core.hpp"
 #include "../device/sorted_bam_core.hpp"
+#include "../device/deflate_out_core.hpp"
 
 namespace arriba {
 
@@ -108,6 +109,83 @@ void sorted_bam_frame(const uint8_t* bytes, uint64_t size, std::vector<uint8_t>&
 	}
 }
 
+namespace {
+
+// deflate_out_core.hpp stepped on the host over one payload: the rounds of the device (64 lanes whose loads of a round all come before its stores, a table per segment), the
+// histograms, the codes, the bits.  The BGZF block is appended to `out`; a payload that no encoding makes smaller comes out as the stored block of sorted_bam_frame.
+void deflated_block(const uint8_t* payload, uint32_t n, std::vector<uint8_t>& out) {
+	using namespace agpu;
+	std::vector<uint32_t> token(n, 0);
+	for (uint32_t segment_begin = 0; segment_begin < n; segment_begin += DFO_SEGMENT) {
+		const uint32_t segment_end = dfo_segment_end(segment_begin, n);
+		uint32_t table[DFO_HASH_SLOTS] = { 0 };
+		uint32_t next = segment_begin; // the first position that no token covers yet
+		for (uint32_t base = segment_begin; base < segment_end; base += DFO_ROUND) {
+			const uint32_t count = std::min(DFO_ROUND, segment_end - base);
+			const bool covered = next >= base + count; // (a match reaches over the whole round: nothing is looked up, the positions are entered all the same)
+			uint32_t found[DFO_ROUND];
+			if (!covered) for (uint32_t lane = 0; lane < count; ++lane) {
+				const uint32_t p = base + lane;
+				const bool hashable = dfo_hashable(p, segment_end);
+				const uint32_t value = hashable ? dfo_load32(payload, p) : 0;
+				found[lane] = dfo_find(payload, p, segment_end, hashable ? table[dfo_hash(value)] : 0, value);
+			}
+			for (uint32_t lane = 0; lane < count; ++lane) {
+				const uint32_t p = base + lane;
+				if (dfo_hashable(p, segment_end)) { uint32_t& slot = table[dfo_hash(dfo_load32(payload, p))]; slot = std::max(slot, p + 1); }
+			}
+			if (!covered) {
+				uint32_t at = std::max(next, base);
+				while (at < base + count) { token[at] = found[at - base]; at += dfo_token_span(found[at - base]); }
+				next = at;
+			}
+		}
+	}
+	DfoState s; memset(&s, 0, sizeof(s));
+	s.ll_count[DFO_END] = 1;
+	for (uint32_t p = 0; p < n; ++p) if (token[p] != 0) {
+		uint32_t ll, d, extra;
+		dfo_token_symbols(token[p], ll, d, extra);
+		++s.ll_count[ll]; if (d < DFO_D) ++s.d_count[d]; s.extra_bits += extra;
+	}
+	for (uint32_t t = 0; t < DFO_LL; ++t) if (s.ll_count[t] != 0) { s.ll_sorted[dfo_rank(s.ll_count, DFO_LL, t)] = (uint16_t) t; ++s.ll_used; }
+	for (uint32_t t = 0; t < DFO_D; ++t) if (s.d_count[t] != 0) { s.d_sorted[dfo_rank(s.d_count, DFO_D, t)] = (uint16_t) t; ++s.d_used; }
+	dfo_plan_lengths(s);
+	for (uint32_t t = 0; t < DFO_CL; ++t) if (s.cl_count[t] != 0) { s.cl_sorted[dfo_rank(s.cl_count, DFO_CL, t)] = (uint16_t) t; ++s.cl_used; }
+	dfo_plan(s, n);
+	if (s.btype == DFO_STORED) { sorted_bam_frame(payload, n, out); return; }
+	for (uint32_t t = 0; t < DFO_LL; ++t) s.ll_code[t] = (uint16_t) dfo_code_of(s.ll_length, s.ll_first, t);
+	for (uint32_t t = 0; t < DFO_D; ++t) s.d_code[t] = (uint16_t) dfo_code_of(s.d_length, s.d_first, t);
+	for (uint32_t t = 0; t < DFO_CL; ++t) s.cl_code[t] = (uint16_t) dfo_code_of(s.cl_length, s.cl_first, t);
+	std::vector<uint32_t> words((s.total_bits + 31) / 32 + 2, 0);
+	const auto or_word = [&words](uint32_t word, uint32_t bits) { words[word] |= bits; };
+	dfo_put_header(s, 0, or_word);
+	uint64_t at = s.header_bits;
+	for (uint32_t p = 0; p < n; ++p) if (token[p] != 0) { dfo_put_token(s, at, token[p], or_word); at += dfo_token_bits(s, token[p]); }
+	dfo_put(at, dfo_end_value(s), dfo_end_bits(s), or_word); at += dfo_end_bits(s);
+	if (at != s.total_bits) throw std::runtime_error("deflate: the bits of a block do not add up to their count");
+	const uint32_t data_bytes = (s.total_bits + 7) / 8, bsize = dfo_block_bytes(s.total_bits) - 1;
+	for (uint32_t i = 0; i < 16; ++i) out.push_back(sbam_head_byte(i, n));
+	out.push_back((uint8_t) bsize); out.push_back((uint8_t) (bsize >> 8));
+	for (uint32_t i = 0; i < data_bytes; ++i) out.push_back((uint8_t) (words[i / 4] >> (8 * (i % 4))));
+	const uint32_t crc = crc32_of_sliced(crc_tables().slice, payload, n);
+	for (uint32_t i = 0; i < SBAM_TAIL; ++i) out.push_back(sbam_tail_byte(i, crc, n));
+}
+
+}
+
+// the same at a compression level (0: stored, 1: deflate_out_core.hpp); block_offset: where every block begins in `out`, counted from first_offset, one entry more for the end
+void sorted_bam_frame_level(const uint8_t* bytes, uint64_t size, int level, std::vector<uint8_t>& out, uint64_t first_offset, std::vector<uint64_t>& block_offset) {
+	const size_t base = out.size();
+	block_offset.clear();
+	for (uint64_t at = 0; at < size; at += agpu::SBAM_PAYLOAD) {
+		const uint32_t n = (uint32_t) std::min<uint64_t>(agpu::SBAM_PAYLOAD, size - at);
+		block_offset.push_back(first_offset + (out.size() - base));
+		if (level == 0) sorted_bam_frame(bytes + at, n, out); else deflated_block(bytes + at, n, out);
+	}
+	block_offset.push_back(first_offset + (out.size() - base));
+}
+
 agpu_sorted_bam_index_arrays SortedBam::view(uint32_t n_ref) {
 	agpu_sorted_bam_index_arrays v; memset(&v, 0, sizeof(v));
 	v.n_ref = n_ref; v.n_chunks = chunk_key.size(); v.n_intervals = intervals.size(); v.n_no_coor = n_no_coor;
@@ -119,8 +197,9 @@ agpu_sorted_bam_index_arrays SortedBam::view(uint32_t n_ref) {
 bool references_fit_bai(const uint32_t* ref_length, uint32_t n_ref) { for (uint32_t t = 0; t < n_ref; ++t) if (ref_length[t] > (uint32_t) agpu::SBAM_MAX_REFERENCE) return false; return true; }
 
 // ref_length == NULL: no index
-void sorted_bam_of(const uint8_t* records, uint64_t size, uint64_t first_block_file_offset, const uint32_t* ref_length, uint32_t n_ref, SortedBam& result) {
+void sorted_bam_of(const uint8_t* records, uint64_t size, uint64_t first_block_file_offset, const uint32_t* ref_length, uint32_t n_ref, SortedBam& result, int level) {
 	using namespace agpu;
+	if (level != 0 && level != 1) throw std::runtime_error("the compression level of a sorted BAM file is 0 (stored) or 1");
 	// the record chain
 	std::vector<uint64_t> offset;
 	for (uint64_t at = 0; at < size; ) {
@@ -141,7 +220,8 @@ void sorted_bam_of(const uint8_t* records, uint64_t size, uint64_t first_block_f
 	std::vector<uint8_t> sorted(size);
 	for (uint64_t i = 0; i < n; ++i) memcpy(sorted.data() + out_offset[i], records + offset[order[i]], parsed[order[i]].size);
 	result.blocks.clear(); result.blocks.reserve(size + sbam_block_count(size) * (SBAM_HEAD + SBAM_TAIL));
-	sorted_bam_frame(sorted.data(), size, result.blocks);
+	std::vector<uint64_t> block_offset;
+	sorted_bam_frame_level(sorted.data(), size, level, result.blocks, first_block_file_offset, block_offset);
 	memset(&result.info, 0, sizeof(result.info));
 	result.info.records = n; result.info.uncompressed_bytes = size; result.info.file_bytes = result.blocks.size(); result.info.windows = size > 0 ? 1 : 0; result.info.window_bytes = result.blocks.size();
 	// the index
@@ -149,6 +229,7 @@ void sorted_bam_of(const uint8_t* records, uint64_t size, uint64_t first_block_f
 	if (!result.indexed) return;
 	sorted_bam_index_of(n, [&](uint64_t i) {
 		const SbamRecord& r = parsed[order[i]];
+		if (level != 0) { const SortedBamIndexed record = { r.ref, r.pos, r.end, (r.flag & 4u) != 0, sbam_voffset(block_offset.data(), out_offset[i]), sbam_voffset(block_offset.data(), out_offset[i + 1]) }; return record; }
 		const SortedBamIndexed record = { r.ref, r.pos, r.end, (r.flag & 4u) != 0, sbam_voffset(first_block_file_offset, out_offset[i]), sbam_voffset(first_block_file_offset, out_offset[i + 1]) };
 		return record;
 	}, ref_length, n_ref, result);
@@ -231,7 +312,8 @@ void write_file(const std::string& path, const std::vector<const std::vector<uin
 }
 
 // the whole output on the host: FILE and FILE.bai through FILE.tmp / FILE.bai.tmp
-void sorted_bam_write(const uint8_t* input_header, size_t header_size, const uint8_t* records, uint64_t size, const std::string& path, agpu_sorted_bam_info* info) {
+void sorted_bam_write(const uint8_t* input_header, size_t header_size, const uint8_t* records, uint64_t size, const std::string& path, agpu_sorted_bam_info* info, int level) {
+	if (level != 0 && level != 1) throw std::runtime_error("the compression level of a sorted BAM file is 0 (stored) or 1");
 	std::vector<uint8_t> header, framed_header, bai, eof; std::vector<uint32_t> ref_length;
 	sorted_bam_header(input_header, header_size, header, ref_length);
 	sorted_bam_frame(header.data(), header.size(), framed_header);
@@ -239,7 +321,7 @@ void sorted_bam_write(const uint8_t* input_header, size_t header_size, const uin
 	const bool with_index = references_fit_bai(ref_length.data(), (uint32_t) ref_length.size());
 	if (!with_index) std::cerr << "WARNING: a reference is longer than 2^29 bases, which a BAI index cannot address: '" << path << "' is written without '" << path << ".bai'" << std::endl;
 	SortedBam sorted;
-	sorted_bam_of(records, size, framed_header.size(), with_index ? ref_length.data() : NULL, (uint32_t) ref_length.size(), sorted);
+	sorted_bam_of(records, size, framed_header.size(), with_index ? ref_length.data() : NULL, (uint32_t) ref_length.size(), sorted, level);
 	const std::string bam_tmp = path + ".tmp", bai_tmp = path + ".bai.tmp";
 	try {
 		write_file(bam_tmp, { &framed_header, &sorted.blocks, &eof });

@@ -65,6 +65,7 @@ void usage() {
 	             " -u duplicates are marked in the BAM file   -X extra columns for discarded fusions   -I fill gaps of the fusion transcript from the assembly   -h this text\n"
 	             " --device N  the GPU to use (0)            --host-ingest  read_chimeric_alignments on the host instead of on the GPU\n"
 	             " --sorted-bam FILE  the records of -x in coordinate order (BAM, stored BGZF blocks) and FILE.bai: what samtools sort + samtools index make of Aligned.out.bam\n"
+	             " --sorted-bam-compression N  0: stored blocks (the default); 1: the record blocks of --sorted-bam deflated on the GPU (as samtools sort compresses its output)\n"
 	             " --supporting-alignments PREFIX  PREFIX_ID.bam and .bam.bai per row of -o: the alignments of its read_identifiers near its breakpoints (extract_fusion-supporting_alignments.sh)\n"
 	             " --supporting-window INT  how far from a breakpoint they may lie (1000000)\n";
 }
@@ -90,14 +91,17 @@ int main(int argc, char** argv) {
 	require(argv[1][0] == '-' && argv[1][1] != '\0', std::string("cannot interpret the first argument: ") + argv[1]);
 	// the long options of this implementation are taken out first; the rest is the reference's getopt string (source/options.cpp:282)
 	std::vector<char*> arguments(1, argv[0]);
+	bool compression_given = false;
 	for (int a = 1; a < argc; ++a) {
 		if (strcmp(argv[a], "--host-ingest") == 0) options.host_ingest = 1;
 		else if (strcmp(argv[a], "--sorted-bam") == 0 && a + 1 < argc) { options.sorted_bam_file = argv[++a]; parent_exists(options.sorted_bam_file); }
+		else if (strcmp(argv[a], "--sorted-bam-compression") == 0 && a + 1 < argc) { long level; require(parse_int(argv[++a], level) && (level == 0 || level == 1), "invalid argument to --sorted-bam-compression: 0 (stored) or 1"); options.sorted_bam_compression = (int) level; compression_given = true; }
 		else if (strcmp(argv[a], "--supporting-alignments") == 0 && a + 1 < argc) { options.supporting_alignments_prefix = argv[++a]; parent_exists(options.supporting_alignments_prefix); }
 		else if (strcmp(argv[a], "--supporting-window") == 0 && a + 1 < argc) { long window; require(parse_int(argv[++a], window) && window > 0 && window <= 0x7FFFFFFFl, "invalid argument to --supporting-window"); options.supporting_alignments_window = window; }
 		else if (strcmp(argv[a], "--device") == 0 && a + 1 < argc) { long device; require(parse_int(argv[++a], device) && device >= 0, "invalid argument to --device"); options.device_index = (int) device; }
 		else arguments.push_back(argv[a]);
 	}
+	require(!compression_given || options.sorted_bam_file != nullptr, "--sorted-bam-compression needs --sorted-bam");
 	std::string interesting_contigs, viral_contigs;
 	bool seen[256]; memset(seen, 0, sizeof(seen));
 	bool blacklist_enabled = true;

@@ -30,6 +30,8 @@ extern "C" int agpu_sorted_bam_begin(agpu_ctx* ctx, agpu_sorted_bam_info* info) 
 extern "C" int agpu_sorted_bam_next(agpu_ctx* ctx, void* pinned, uint64_t capacity, uint64_t* bytes) __attribute__((weak));
 extern "C" int agpu_sorted_bam_index(agpu_ctx* ctx, uint64_t first_block_file_offset, const uint32_t* ref_length, uint32_t n_ref, agpu_sorted_bam_index_arrays* index) __attribute__((weak));
 extern "C" int agpu_sorted_bam_end(agpu_ctx* ctx) __attribute__((weak));
+extern "C" int agpu_sorted_bam_set_compression(agpu_ctx* ctx, int level) __attribute__((weak));
+extern "C" int agpu_sorted_bam_compressed_bytes(agpu_ctx* ctx, uint64_t* bytes) __attribute__((weak));
 // ... and those of --supporting-alignments
 extern "C" int agpu_support_pool_build(agpu_ctx* ctx, const char* names, const uint64_t* name_offset, uint64_t n_names, agpu_support_pool_info* info) __attribute__((weak));
 extern "C" int agpu_supporting_begin(agpu_ctx* ctx, const agpu_supporting_rows* rows, int64_t window, agpu_supporting_info* info) __attribute__((weak));
@@ -435,8 +437,12 @@ bool shard_reads(Run& run, agpu_ingest_result& result, uint64_t windows, uint32_
 void write_sorted_bam(Run& run) {
 	const std::string path = run.options.sorted_bam_file, bam_tmp = path + ".tmp", bai_tmp = path + ".bai.tmp";
 	if (!agpu_sorted_bam_begin || !agpu_sorted_bam_next || !agpu_sorted_bam_index || !agpu_sorted_bam_end) throw Failure{ "ERROR: --sorted-bam needs the device library (agpu_sorted_bam_begin), which this build is not linked with" };
+	const int level = run.options.sorted_bam_compression;
+	if (level != 0 && level != 1) throw Failure{ "ERROR: the compression level of a sorted BAM file is 0 (stored) or 1" };
+	if (level != 0 && (!agpu_sorted_bam_set_compression || !agpu_sorted_bam_compressed_bytes)) throw Failure{ "ERROR: --sorted-bam-compression needs the device library (agpu_sorted_bam_set_compression), which this build is not linked with" };
 	const double started = now_seconds();
 	agpu_sorted_bam_info info;
+	if (level != 0) device_check(agpu_sorted_bam_set_compression(run.device, level));
 	device_check(agpu_sorted_bam_begin(run.device, &info));
 	struct Ender { Run& run; ~Ender() { agpu_sorted_bam_end(run.device); } } ender = { run };
 	FILE* file = nullptr;
@@ -456,7 +462,9 @@ void write_sorted_bam(Run& run) {
 			put(windows[turn & 1], bytes);
 			written += bytes;
 		}
-		if (written != info.file_bytes) throw Failure{ "ERROR: the record blocks of '" + path + "' do not have the size that was announced" };
+		uint64_t expected = info.file_bytes; // (with compression: an upper bound at the begin, the size of the blocks behind the last window)
+		if (level != 0) device_check(agpu_sorted_bam_compressed_bytes(run.device, &expected));
+		if (written != expected || written > info.file_bytes) throw Failure{ "ERROR: the record blocks of '" + path + "' do not have the size that was announced" };
 		uint8_t eof[28];
 		ahost_sorted_bam_eof(eof);
 		put(eof, sizeof(eof));
@@ -1153,7 +1161,7 @@ void run_sample(Run& run, bool already_fed, double sample_started) {
 	else {
 		if (run.ranks != nullptr) throw Failure{ "ERROR: one sample over several ranks needs read_chimeric_alignments on the device (host_ingest = 0): the parts of the batch are exchanged in device format" };
 		host_check(ahost_ingest_bam_file(run.host, o.chimeric_bam_file, o.device.external_duplicate_marking, o.device.max_itd_length));
-		if (o.sorted_bam_file != nullptr) { const double before = now_seconds(); host_check(ahost_sorted_bam_file(o.chimeric_bam_file, o.sorted_bam_file, nullptr)); if (run.timing) run.timing->sorted_bam = now_seconds() - before; } // (the host's stepping of the same code)
+		if (o.sorted_bam_file != nullptr) { const double before = now_seconds(); host_check(ahost_sorted_bam_file_level(o.chimeric_bam_file, o.sorted_bam_file, o.sorted_bam_compression, nullptr)); if (run.timing) run.timing->sorted_bam = now_seconds() - before; } // (the host's stepping of the same code)
 		device_check(agpu_upload_genome(run.device, ahost_genome_view(run.host)));
 		device_check(agpu_upload_batch(run.device, ahost_batch_view(run.host)));
 		run.n_fragments = ahost_batch_view(run.host)->n;
@@ -1338,12 +1346,13 @@ int arriba_workflow_run(const arriba_workflow_options* options, arriba_workflow_
 struct arriba_workflow_session {
 	Run* lanes[2];
 	int processed_lane = 0; // of the sample arriba_workflow_sample worked on last
-	struct Submitted { std::string bam, sorted_bam, supporting; int lane = 0; std::thread feeder; bool fed = false, ingest_finished = false, started = false; std::string error; int error_code = 0; };
+	struct Submitted { std::string bam, sorted_bam, supporting; int sorted_bam_level = 0; int lane = 0; std::thread feeder; bool fed = false, ingest_finished = false, started = false; std::string error; int error_code = 0; };
 	std::deque<std::unique_ptr<Submitted>> queue; // oldest first; at most two
 	std::mutex mutex; std::condition_variable changed;
 	bool ingest_busy = false; // a lane is between agpu_ingest_begin and agpu_ingest_finish
 	std::string next_sorted_bam; // arriba_workflow_sorted_bam: of the sample that is submitted next
 	std::string next_supporting; // arriba_workflow_supporting_alignments: likewise
+	int sorted_bam_level = 0; // arriba_workflow_sorted_bam_compression: of the samples submitted from now on (at first: options.sorted_bam_compression of arriba_workflow_open)
 	bool defer_output = false;
 	bool retrying = false; // arriba_workflow_sample runs a sample again after the device ran out of memory with two lanes (below)
 	bool finish_ahead = false; // arriba_workflow_finish_ahead: the feeder of a sample also finishes its ingest (the lanes keep their batch buffers)
@@ -1364,7 +1373,7 @@ struct arriba_workflow_session {
 		lanes[lane]->writer_error.clear();
 	}
 	std::string take_deferred_error() { std::lock_guard<std::mutex> lock(writer_mutex); std::string text; text.swap(deferred_error); return text; }
-	arriba_workflow_session(const arriba_workflow_options& o) { lanes[0] = new Run(o); lanes[1] = nullptr; }
+	arriba_workflow_session(const arriba_workflow_options& o) { lanes[0] = new Run(o); lanes[1] = nullptr; sorted_bam_level = o.sorted_bam_compression; }
 	~arriba_workflow_session() {
 		drain();
 		leave();
@@ -1408,11 +1417,12 @@ struct arriba_workflow_session {
 		Run& run = *lanes[lane];
 		run.bam_path = bam; run.options.chimeric_bam_file = run.bam_path.c_str();
 		run.sorted_bam_path.swap(next_sorted_bam); next_sorted_bam.clear(); run.options.sorted_bam_file = run.sorted_bam_path.empty() ? nullptr : run.sorted_bam_path.c_str();
+		run.options.sorted_bam_compression = sorted_bam_level;
 		run.supporting_prefix.swap(next_supporting); next_supporting.clear(); run.options.supporting_alignments_prefix = run.supporting_prefix.empty() ? nullptr : run.supporting_prefix.c_str();
 		run.timing = nullptr; run.report = nullptr;
 		prepare_sample(run);
 		std::unique_ptr<Submitted> sample(new Submitted());
-		sample->bam = bam; sample->sorted_bam = run.sorted_bam_path; sample->supporting = run.supporting_prefix; sample->lane = lane;
+		sample->bam = bam; sample->sorted_bam = run.sorted_bam_path; sample->supporting = run.supporting_prefix; sample->sorted_bam_level = sorted_bam_level; sample->lane = lane;
 		Submitted* mine = sample.get();
 		{ std::lock_guard<std::mutex> lock(mutex); queue.push_back(std::move(sample)); }
 		if (!run.device_ingest) { join_writer_of(lane); std::lock_guard<std::mutex> lock(mutex); mine->fed = true; return; } // (the host ingest reads the file inside arriba_workflow_sample)
@@ -1451,6 +1461,13 @@ arriba_workflow_session* arriba_workflow_open(const arriba_workflow_options* opt
 int arriba_workflow_sorted_bam(arriba_workflow_session* session, const char* sorted_bam_file) {
 	if (!session) { g_error = "ERROR: null argument"; return -1; }
 	session->next_sorted_bam = sorted_bam_file ? sorted_bam_file : "";
+	return 0;
+}
+
+int arriba_workflow_sorted_bam_compression(arriba_workflow_session* session, int level) {
+	if (!session) { g_error = "ERROR: null argument"; return -1; }
+	if (level != 0 && level != 1) { g_error = "ERROR: the compression level of a sorted BAM file is 0 (stored) or 1"; return -1; }
+	session->sorted_bam_level = level;
 	return 0;
 }
 
@@ -1517,6 +1534,7 @@ int arriba_workflow_sample(arriba_workflow_session* session, const char* chimeri
 		const std::string first_error = g_error;
 		const std::string behind = session->queue.empty() ? std::string() : session->queue.front()->bam;
 		const std::string behind_sorted_bam = session->queue.empty() ? std::string() : session->queue.front()->sorted_bam, again_sorted_bam = lane->sorted_bam_path;
+		const int behind_level = session->queue.empty() ? 0 : session->queue.front()->sorted_bam_level, again_level = lane->options.sorted_bam_compression, session_level = session->sorted_bam_level;
 		const std::string behind_supporting = session->queue.empty() ? std::string() : session->queue.front()->supporting, again_supporting = lane->supporting_prefix;
 		session->drain();
 		session->join_writer_of(0); session->join_writer_of(1);
@@ -1526,13 +1544,14 @@ int arriba_workflow_sample(arriba_workflow_session* session, const char* chimeri
 		delete session->lanes[1]; session->lanes[1] = nullptr; session->processed_lane = 0;
 		fprintf(stderr, "arriba_workflow_sample: %s -- with two samples in flight; '%s' is run again with the device to itself\n", first_error.c_str(), chimeric_bam_file);
 		session->retrying = true;
-		session->next_sorted_bam = again_sorted_bam; session->next_supporting = again_supporting;
+		session->next_sorted_bam = again_sorted_bam; session->next_supporting = again_supporting; session->sorted_bam_level = again_level;
 		status = arriba_workflow_sample(session, chimeric_bam_file, output_file, discarded_output_file, report, timing);
 		session->retrying = false;
 		if (status == 0 && !behind.empty()) { // (as its caller submitted it: a failure to feed it is reported by the call that asks for it)
-			try { session->next_sorted_bam = behind_sorted_bam; session->next_supporting = behind_supporting; session->submit(behind.c_str()); }
+			try { session->next_sorted_bam = behind_sorted_bam; session->next_supporting = behind_supporting; session->sorted_bam_level = behind_level; session->submit(behind.c_str()); }
 			catch (const Failure&) {} catch (const std::exception&) {}
 		}
+		session->sorted_bam_level = session_level;
 	}
 	return status;
 }

@@ -153,9 +153,16 @@ class WorkflowSession(object):
         self.timings, self._profiling_on, self.ingest_result = {}, False, None  # (what bench.py reads from a DevicePipeline)
         self._profiled = set()
 
-    def submit(self, bam, sorted_bam_file=None, supporting_alignments_prefix=None):
+    def sorted_bam_compression(self, level):
+        """--sorted-bam-compression of the samples submitted from now on: 0 stored blocks, 1 deflated on the device"""
+        if self._lib.arriba_workflow_sorted_bam_compression(self._session, int(level)) != 0:
+            raise ArribaError(self._lib.arriba_workflow_last_error().decode())
+
+    def submit(self, bam, sorted_bam_file=None, supporting_alignments_prefix=None, sorted_bam_compression=None):
         """the sample that comes after the one `sample` is called for next: its file is fed (PCIe, the front of read_chimeric_alignments) while the stages of that one run;
-        sorted_bam_file: its records in coordinate order with their index (--sorted-bam), written when its ingest is finished"""
+        sorted_bam_file: its records in coordinate order with their index (--sorted-bam), written when its ingest is finished; sorted_bam_compression: its level (None: as it is)"""
+        if sorted_bam_compression is not None:
+            self.sorted_bam_compression(sorted_bam_compression)
         self._lib.arriba_workflow_sorted_bam(self._session, sorted_bam_file.encode() if sorted_bam_file else None)
         self._lib.arriba_workflow_supporting_alignments(self._session, supporting_alignments_prefix.encode() if supporting_alignments_prefix else None)  # (--supporting-alignments: PREFIX_ID.bam per row of its fusions file)
         if self._lib.arriba_workflow_submit(self._session, bam.encode()) != 0:
@@ -252,10 +259,12 @@ class WorkflowSession(object):
     def _lane_contexts(self):
         return [ctx for ctx in (self._lib.arriba_workflow_lane_device(self._session, lane) for lane in (0, 1)) if ctx]
 
-    def sample(self, bam, output_file, discarded_output_file=None, sorted_bam_file=None, supporting_alignments_prefix=None):
+    def sample(self, bam, output_file, discarded_output_file=None, sorted_bam_file=None, supporting_alignments_prefix=None, sorted_bam_compression=None):
         """one sample, BAM file -> fusions.tsv (and discarded.tsv); returns the stages with their "(remaining=N)" counts.  sorted_bam_file (--sorted-bam): for a sample that was
         not submitted ahead; one that was says it to `submit`"""
         report, timing = _capi.WorkflowReport(), _capi.WorkflowTiming()
+        if sorted_bam_compression is not None:  # (as sorted_bam_file: for a sample that was not submitted ahead)
+            self.sorted_bam_compression(sorted_bam_compression)
         if sorted_bam_file:
             self._lib.arriba_workflow_sorted_bam(self._session, sorted_bam_file.encode())
         if supporting_alignments_prefix:  # (as sorted_bam_file: for a sample that was not submitted ahead)
@@ -463,8 +472,9 @@ class DevicePipeline(object):
 
     MAX_BAI_REFERENCE = 1 << 29
 
-    def write_sorted_bam(self, path):
-        """The records of the file of the last read_chimeric_alignments in coordinate order as `path` (BAM of stored BGZF blocks) and `path`.bai -- what run_arriba.sh:47-51 gets
+    def write_sorted_bam(self, path, compression=0):
+        """compression (--sorted-bam-compression): 0 stored blocks; 1 every record block deflated on the device (agpu_sorted_bam_set_compression), "file_bytes" is then what the
+        blocks really take.  The records of the file of the last read_chimeric_alignments in coordinate order as `path` (BAM of stored BGZF blocks) and `path`.bai -- what run_arriba.sh:47-51 gets
         from `samtools sort` / `samtools index` -- from the record stream that is still in HBM (agpu_sorted_bam_*).  Valid after read_chimeric_alignments and before the next one.
         Written through `path`.tmp / `path`.bai.tmp; returns {"records", "uncompressed_bytes", "file_bytes", "windows", "indexed"}; the seconds of its parts: self.sorted_bam_seconds."""
         import os
@@ -475,6 +485,8 @@ class DevicePipeline(object):
         lib, handle = self.session._lib, self.session._session
         started = time.perf_counter()
         info = _capi.SortedBamInfo()
+        if compression != 0:
+            self._check(self.api.sorted_bam_set_compression(self.ctx, int(compression)))  # (0: the call is not made, as before the level existed)
         self._check(self.api.sorted_bam_begin(self.ctx, byref(info)))  # (refused before anything is written: the stream given back, another ingest begun, a part of a sample)
         sorted_at = time.perf_counter()
         seconds = {"sort": sorted_at - started, "gather_and_copy": 0.0, "write": 0.0, "index": 0.0}
@@ -507,7 +519,10 @@ class DevicePipeline(object):
                     seconds["write"] += time.perf_counter() - middle
                     written += got.value
                     turn += 1
-                if written != info.file_bytes:
+                expected = c_uint64(info.file_bytes)
+                if compression != 0:  # (announced: the upper bound)
+                    self._check(self.api.sorted_bam_compressed_bytes(self.ctx, byref(expected)))
+                if written != expected.value or written > info.file_bytes:
                     raise ArribaError("ERROR: the record blocks of the sorted BAM file have %d bytes, %d were announced" % (written, info.file_bytes))
                 eof = ctypes.create_string_buffer(28)
                 lib.ahost_sorted_bam_eof(eof)
@@ -537,7 +552,7 @@ class DevicePipeline(object):
             self.api.sorted_bam_end(self.ctx)
         seconds["total"] = time.perf_counter() - started
         self.sorted_bam_seconds = seconds
-        return {"records": int(info.records), "uncompressed_bytes": int(info.uncompressed_bytes), "file_bytes": int(info.file_bytes), "windows": int(info.windows), "indexed": indexed}
+        return {"records": int(info.records), "uncompressed_bytes": int(info.uncompressed_bytes), "file_bytes": int(written), "windows": int(info.windows), "indexed": indexed}
 
     def build_support_pool(self, names=None):
         """Phase 1 of --supporting-alignments: the records of the listed read names copied out of the record stream of the last read_chimeric_alignments into a pool that stays with
@@ -558,6 +573,12 @@ class DevicePipeline(object):
 
     def release_support_pool(self):
         self._check(self.api.support_pool_release(self.ctx))
+
+    def sorted_bam_compression_allocated_bytes(self):
+        """bytes of the device buffers that only --sorted-bam-compression 1 has: 0 as long as it was never used"""
+        count = c_uint64()
+        self._check(self.api.sorted_bam_compression_allocated_bytes(self.ctx, byref(count)))
+        return int(count.value)
 
     def support_allocated_bytes(self):
         count = c_uint64()

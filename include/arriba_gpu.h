@@ -297,6 +297,20 @@ int agpu_sorted_bam_begin(agpu_ctx* ctx, agpu_sorted_bam_info* info);
 int agpu_sorted_bam_next(agpu_ctx* ctx, void* pinned, uint64_t capacity, uint64_t* bytes);
 int agpu_sorted_bam_index(agpu_ctx* ctx, uint64_t first_block_file_offset, const uint32_t* ref_length, uint32_t n_ref, agpu_sorted_bam_index_arrays* index);
 int agpu_sorted_bam_end(agpu_ctx* ctx);
+/* --sorted-bam-compression: the record blocks deflated on the device (arriba_amd/csrc/device/deflate_out_core.hpp).
+ *   agpu_sorted_bam_set_compression   before agpu_sorted_bam_begin, for that one begin ... end (the one after it is at level 0 again).  0, the default: stored blocks, the file of
+ *                                     the functions above byte for byte; no kernel and no buffer of the compressor exists.  1: every record block is one deflate block, the smallest
+ *                                     of stored / fixed Huffman / dynamic Huffman over LZ77 tokens -- never larger than the stored block, and byte for byte what
+ *                                     ahost_sorted_bam_level gives at level 1.  Another level: AGPU_ERR_INVALID with a message.
+ *                                     At level 1 info.file_bytes and info.window_bytes of agpu_sorted_bam_begin are UPPER BOUNDS (the stored sizes: what the blocks will really take
+ *                                     is not known before they are made); agpu_sorted_bam_next returns the packed bytes of its window, still a whole number of blocks;
+ *                                     agpu_sorted_bam_index needs the sizes of all blocks and fails with a message before the last window has been fetched.
+ *   agpu_sorted_bam_compressed_bytes  the bytes of all record blocks as fetched (at level 0: info.file_bytes); valid behind the agpu_sorted_bam_next that fetched the last window
+ *   agpu_sorted_bam_compression_allocated_bytes   of the device buffers that only level 1 has ("sortedbam.tokens", ".block_bytes", ".window_offset", ".packed", ".block_offset"):
+ *                                     0 as long as the level was never 1 on the context's pool */
+int agpu_sorted_bam_set_compression(agpu_ctx* ctx, int level);
+int agpu_sorted_bam_compressed_bytes(agpu_ctx* ctx, uint64_t* bytes);
+int agpu_sorted_bam_compression_allocated_bytes(agpu_ctx* ctx, uint64_t* bytes);
 /* ---- one small sorted, indexed BAM file per row of fusions.tsv, with the alignments of the row's read_identifiers that lie near its breakpoints: what the reference's
  * scripts/extract_fusion-supporting_alignments.sh gets from samtools view / sort / index, from the record stream in HBM (arriba_amd/csrc/device/agpu_supporting.hip,
  * supporting_core.hpp).  Two phases, because the stream goes to the next feed right behind the ingest and the rows exist only at the end of the sample:

@@ -92,6 +92,13 @@ void ahost_sorted_bam_eof(uint8_t* block /* [28] */);
  /*  ahost_sorted_bam_file       the same for a file (BAM in BGZF, gzip or raw; SAM text): read whole into host memory -- what --host-ingest does for --sorted-bam */
 int ahost_sorted_bam_file(const char* input_path, const char* path, agpu_sorted_bam_info* info /* may be NULL */);
 int ahost_sorted_bam_write(const void* input_header, size_t header_size, const void* records, size_t size, const char* path, agpu_sorted_bam_info* info /* may be NULL */);
+/* --sorted-bam-compression: the same three with a level.  0: the stored blocks of the functions above, byte for byte.  1: every record block is one deflate block, the smallest of
+ * stored / fixed Huffman / dynamic Huffman over LZ77 tokens (arriba_amd/csrc/device/deflate_out_core.hpp stepped on the host: the bytes agpu_sorted_bam_* give at level 1); the
+ * virtual offsets of the index come from the sizes the blocks really have; info->file_bytes is the size the record blocks really have.  The header blocks and the end-of-file block
+ * are the same at every level.  Another level: an error with a message. */
+int ahost_sorted_bam_level(const void* records, size_t size, uint64_t first_block_file_offset, const uint32_t* ref_length, uint32_t n_ref, int level, const uint8_t** blocks, agpu_sorted_bam_info* info, agpu_sorted_bam_index_arrays* index);
+int ahost_sorted_bam_file_level(const char* input_path, const char* path, int level, agpu_sorted_bam_info* info /* may be NULL */);
+int ahost_sorted_bam_write_level(const void* input_header, size_t header_size, const void* records, size_t size, const char* path, int level, agpu_sorted_bam_info* info /* may be NULL */);
 /* ---- --supporting-alignments: the host side of agpu_support_pool_build / agpu_supporting_* (include/arriba_gpu.h) -- one sorted, indexed BAM file per row of fusions.tsv with
  * the alignments of the row's read_identifiers near its breakpoints (the reference's scripts/extract_fusion-supporting_alignments.sh), PREFIX_ID.bam and PREFIX_ID.bam.bai, ID = 1-based
  * rank of the row ----

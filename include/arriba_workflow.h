@@ -53,6 +53,9 @@ typedef struct {
 	                                         agpu_supporting_*).  Of arriba_workflow_run's sample; the samples of a session say theirs with arriba_workflow_supporting_alignments.
 	                                         Not for one sample over several ranks. */
 	int64_t supporting_alignments_window; /* --supporting-window: SEARCH_WINDOW of the script; 0 = its default, 1000000 */
+	int sorted_bam_compression;           /* --sorted-bam-compression: 0 (and a zero-initialised struct) = the record blocks of sorted_bam_file are stored; 1 = each is deflated on the device
+	                                         (include/arriba_gpu.h: agpu_sorted_bam_set_compression; with host_ingest: the same code stepped on the host).  Anything else fails the sample.  The files
+	                                         of supporting_alignments_prefix stay stored. */
 } arriba_workflow_options;
 
 /* what the reference prints as "(remaining=N)" / "(total=N)" / "(marked=N)", in the order of the stages; stage names as in the reference's source */
@@ -107,6 +110,9 @@ int arriba_workflow_submit(arriba_workflow_session* session, const char* chimeri
  * that finishes the ingest of that sample, before the stream in HBM goes to the feed of the sample behind it; if it cannot be written the sample fails with the message, FILE.tmp and
  * FILE.bai.tmp are removed, and the session takes the next sample. */
 int arriba_workflow_sorted_bam(arriba_workflow_session* session, const char* sorted_bam_file);
+/* --sorted-bam-compression of the samples that are submitted FROM NOW ON (until the next call; at first options.sorted_bam_compression of arriba_workflow_open): 0 or 1, anything
+ * else is refused with a message. */
+int arriba_workflow_sorted_bam_compression(arriba_workflow_session* session, int level);
 /* --supporting-alignments of the sample that is submitted NEXT, in the same way; NULL: none.  The pool of its supporting alignments is built by the thread that finishes its ingest and
  * belongs to its lane until its fusions file is written; the window is options.supporting_alignments_window of arriba_workflow_open. */
 int arriba_workflow_supporting_alignments(arriba_workflow_session* session, const char* prefix);

@@ -14,4 +14,9 @@ for MODE in thread address,undefined; do
 		ARRIBA_INGEST_THREADS=$THREADS ASAN_OPTIONS=detect_leaks=0 $WORK/ingest_$MODE $WORK/data.fa $WORK/data.gtf $WORK/data.bam $WORK/data.blacklist.tsv $WORK/data.known_fusions.tsv 2>&1 | grep -v "SAM records were malformed\|^WARNING" || true
 	done
 done
+# the host stepping of --sorted-bam-compression (arriba_amd/csrc/device/deflate_out_core.hpp): the same file sorted and deflated at level 1, and the code-length builder on counts
+# that make trees deeper than its limits (tools/deflate_out_main.cpp)
+g++ -std=c++17 -O1 -g -pthread -fsanitize=address,undefined -fno-sanitize-recover=undefined -fno-omit-frame-pointer -I$ROOT/include -I$ROOT/arriba_amd/csrc/host -o $WORK/deflate_out_main $ROOT/tools/deflate_out_main.cpp $ROOT/arriba_amd/csrc/host/*.cpp -lz
+echo "== -fsanitize=address,undefined, --sorted-bam-compression 1 on the host"
+ASAN_OPTIONS=detect_leaks=0 $WORK/deflate_out_main $WORK/data.bam $WORK/data.sorted.bam
 rm -rf $WORK
