@@ -117,6 +117,17 @@ class SupportingIndex(ctypes.Structure):
     _fields_ = [("n_rows", c_uint32), ("n_records", c_uint64)] + [(name, c_void_p) for name in ("row_first", "ref", "pos", "end_flag", "bin", "begin", "end")]
 
 
+class VirusCounters(ctypes.Structure):
+    """agpu_virus_counters: what agpu_virus_expression / ahost_virus_expression count; the arrays belong to the callee"""
+    _fields_ = [("total", c_uint64), ("n_viruses", c_uint32), ("n_active", c_uint32)] + [(name, c_void_p) for name in ("reads", "covered", "kmer_count", "active", "shared")] + [
+        (name, c_uint64) for name in ("candidates", "kmer_keys", "kmer_rounds", "peak_bytes")] + [("seconds", ctypes.c_double * 4)]
+
+
+class VirusContigs(ctypes.Structure):
+    """ahost_virus_contigs: the viral contigs of a header -- slot v is reference viral_ref[v]"""
+    _fields_ = [("n_ref", c_uint32), ("n_viruses", c_uint32), ("viral_ref", c_void_p), ("viral_length", c_void_p), ("names", c_void_p), ("name_offset", c_void_p)]
+
+
 class BamPiece(ctypes.Structure):
     """ahost_bam_piece: stored_bgzf is the KIND of the piece -- 0 stream bytes, 1 stored BGZF, 2 deflated BGZF, 3 lines of SAM text (first_line: the number of its first line)"""
     _fields_ = [("stored_bgzf", c_int), ("bytes", c_size_t), ("stream_bytes", c_size_t), ("n_blocks", c_uint32), ("first_line", c_uint64)]
@@ -267,6 +278,8 @@ def bind_device_api(lib, prefix="agpu_"):
         "supporting_end": (c_int, [ctx]),
         "support_pool_release": (c_int, [ctx]),
         "support_allocated_bytes": (c_int, [ctx, POINTER(c_uint64)]),
+        "virus_expression": (c_int, [ctx, c_void_p, c_void_p, c_uint32, c_uint32, POINTER(VirusCounters)]),
+        "virus_allocated_bytes": (c_int, [ctx, POINTER(c_uint64)]),
         "shard_export_size": (c_int, [ctx, POINTER(c_uint64)]),
         "shard_export": (c_int, [ctx, c_void_p, c_uint64]),
         "shard_merge": (c_int, [ctx, c_void_p, c_uint64, c_uint32, POINTER(IngestResult)]),
@@ -358,6 +371,12 @@ def bind_host_api(lib):
         "ahost_supporting_writer_close": (c_int, [c_void_p, c_int]),
         "ahost_supporting_alignments": (c_int, [c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_void_p, c_uint64, POINTER(SupportingRows), ctypes.c_int64, c_char_p, POINTER(SupportingInfo)]),
         "ahost_supporting_alignments_file": (c_int, [session, c_void_p, c_char_p, ctypes.c_int64, c_char_p, POINTER(SupportingInfo)]),
+        "ahost_virus_contigs_of_session": (c_int, [session, POINTER(VirusContigs)]),
+        "ahost_virus_contigs_of": (c_int, [c_void_p, c_size_t, c_char_p, POINTER(VirusContigs)]),
+        "ahost_virus_expression": (c_int, [c_void_p, c_size_t, POINTER(VirusContigs), POINTER(VirusCounters)]),
+        "ahost_virus_expression_table": (c_int, [POINTER(VirusCounters), POINTER(VirusContigs), POINTER(c_void_p), POINTER(c_uint64)]),
+        "ahost_virus_expression_write": (c_int, [POINTER(VirusCounters), POINTER(VirusContigs), c_char_p]),
+        "ahost_virus_expression_file": (c_int, [session, c_char_p, c_char_p]),
         "ahost_set_batch_rows": (c_int, [session, POINTER(BatchRows), c_void_p]),
         "ahost_fusion_table_reads": (c_int, [POINTER(FusionTable), c_int, c_void_p, c_uint64, POINTER(c_uint64)]),
         "ahost_read_length_sum_of": (c_float, [c_float, c_void_p, c_void_p, c_uint64]),
@@ -380,7 +399,7 @@ class WorkflowOptions(ctypes.Structure):
                                               "protein_domains_file", "genomic_breakpoints_file", "interesting_contigs", "viral_contigs", "gtf_features")] + [
         ("device", Params), ("min_itd_support", c_uint32), ("min_itd_allele_fraction", c_float), ("high_expression_quantile", c_float), ("min_spliced_events", c_uint32), ("min_anchor_length", c_uint32),
         ("max_homolog_identity", c_float), ("top_viral_contigs", c_uint32), ("viral_contig_min_covered_fraction", c_float), ("max_genomic_breakpoint_distance", c_int32),
-        ("print_extra_info_for_discarded_fusions", c_uint8), ("fill_sequence_gaps", c_uint8), ("device_index", c_int), ("log_to_stdout", c_uint8), ("host_ingest", c_uint8), ("sorted_bam_file", c_char_p), ("supporting_alignments_prefix", c_char_p), ("supporting_alignments_window", ctypes.c_int64), ("sorted_bam_compression", c_int)]
+        ("print_extra_info_for_discarded_fusions", c_uint8), ("fill_sequence_gaps", c_uint8), ("device_index", c_int), ("log_to_stdout", c_uint8), ("host_ingest", c_uint8), ("sorted_bam_file", c_char_p), ("supporting_alignments_prefix", c_char_p), ("supporting_alignments_window", ctypes.c_int64), ("sorted_bam_compression", c_int), ("virus_expression_file", c_char_p)]
 
 
 class WorkflowStage(ctypes.Structure):
@@ -392,7 +411,7 @@ class WorkflowReport(ctypes.Structure):
 
 
 class WorkflowTiming(ctypes.Structure):
-    _fields_ = [(name, ctypes.c_double) for name in ("total", "feed", "ingest", "adopt", "stages", "filter_mismappers", "output", "output_results", "output_rows", "output_format", "feed_read", "feed_push", "feed_total", "exchange_parts", "exchange_verdicts", "exchange_rows", "shard_fragments", "exchanged_bytes", "sorted_bam", "supporting_alignments")]
+    _fields_ = [(name, ctypes.c_double) for name in ("total", "feed", "ingest", "adopt", "stages", "filter_mismappers", "output", "output_results", "output_rows", "output_format", "feed_read", "feed_push", "feed_total", "exchange_parts", "exchange_verdicts", "exchange_rows", "shard_fragments", "exchanged_bytes", "sorted_bam", "supporting_alignments", "virus_expression")]
 
 
 WORKFLOW_MAX, WORKFLOW_MIN, WORKFLOW_SUM = 0, 1, 2
@@ -425,6 +444,7 @@ def workflow_library():
         lib.arriba_workflow_submit.argtypes = [c_void_p, c_char_p]; lib.arriba_workflow_submit.restype = c_int
         lib.arriba_workflow_sorted_bam.argtypes = [c_void_p, c_char_p]; lib.arriba_workflow_sorted_bam.restype = c_int
         lib.arriba_workflow_supporting_alignments.argtypes = [c_void_p, c_char_p]; lib.arriba_workflow_supporting_alignments.restype = c_int
+        lib.arriba_workflow_virus_expression.argtypes = [c_void_p, c_char_p]; lib.arriba_workflow_virus_expression.restype = c_int
         lib.arriba_workflow_sorted_bam_compression.argtypes = [c_void_p, c_int]; lib.arriba_workflow_sorted_bam_compression.restype = c_int
         lib.arriba_workflow_cancel.argtypes = [c_void_p]; lib.arriba_workflow_cancel.restype = c_int
         lib.arriba_workflow_defer_output.argtypes = [c_void_p, c_int]; lib.arriba_workflow_defer_output.restype = c_int

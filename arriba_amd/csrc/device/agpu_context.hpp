@@ -117,6 +117,15 @@ struct SupportState {
 	uint32_t n_rows = 0; uint64_t emissions = 0, blocks = 0, window_blocks = 0, next_block = 0, gathered_block = ~0ull, index_first = 0;
 	std::vector<uint64_t> row_first, row_bytes, row_block_begin, row_out_offset; // [n_rows + 1]: first record, payload bytes, first block, first byte of the framed blocks
 };
+// --virus-expression (agpu_virus.hip): the "virus.*" buffers are the context's own and live inside one agpu_virus_expression; what the call returns stays in host memory here
+struct VirusState {
+	std::map<std::string, DeviceBuffer> buffers;
+	DeviceBuffer& buffer(const char* name) { return buffers[name]; }
+	void release_all() { for (std::map<std::string, DeviceBuffer>::iterator b = buffers.begin(); b != buffers.end(); ++b) b->second.release(); }
+	uint64_t allocated() const { uint64_t sum = 0; for (std::map<std::string, DeviceBuffer>::const_iterator b = buffers.begin(); b != buffers.end(); ++b) sum += b->second.capacity; return sum; }
+	bool active = false;
+	std::vector<uint64_t> reads, covered, kmer_count, shared; std::vector<uint32_t> active_slots;
+};
 }
 struct agpu_ctx {
 	explicit agpu_ctx(std::shared_ptr<agpu::ScratchPool> shared = std::shared_ptr<agpu::ScratchPool>()) : pool(shared ? shared : std::make_shared<agpu::ScratchPool>()),
@@ -204,6 +213,7 @@ struct agpu_ctx {
 	int sorted_bam_level_next = 0, sorted_bam_level = 0; // agpu_sorted_bam_set_compression: of the next agpu_sorted_bam_begin; of the begin ... end under way
 	uint64_t sorted_bam_compressed_bytes = 0;            // of the windows fetched so far
 	agpu::SupportState support; // --supporting-alignments (agpu_supporting.hip)
+	agpu::VirusState virus;     // --virus-expression (agpu_virus.hip)
 	// A pushed piece: copied on the context's stream (piece_copied: the caller's buffer is free), unwrapped and CRC-checked on a stream of its own (piece_stream; piece_ready: its
 	// bytes are in the stream, piece_done: the raw bytes are not needed any more), so that the copy of the next piece never waits for a kernel; AGPU_PIECE_SLOTS raw buffers in turn
 	hipStream_t piece_stream = nullptr, piece_stream2 = nullptr /* deflated pieces take the two in turn */; hipEvent_t piece_copied[AGPU_PIECE_SLOTS] = {}, piece_ready[AGPU_PIECE_SLOTS] = {}, piece_done[AGPU_PIECE_SLOTS] = {};

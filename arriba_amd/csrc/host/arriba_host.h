@@ -272,6 +272,14 @@ private:
 };
 void supporting_alignments(const uint8_t* input_header, size_t header_size, const uint8_t* records, uint64_t size, const char* names, const uint64_t* name_offset, uint64_t n_names, bool strip_hit_index,
                            const agpu_supporting_rows& rows, int64_t window, const std::string& prefix, agpu_supporting_info* info);
+// --virus-expression on the host (virus.cpp): the viral contigs of a header (a BAM header, or the '@' lines of SAM text) by the patterns of -v, arriba_amd/csrc/device/virus_core.hpp
+// stepped over records in host memory, and what turns the counters -- the host's or the device's -- into the text of the reference's scripts/quantify_virus_expression.sh
+struct VirusContigs { uint32_t n_ref = 0; std::vector<int32_t> ref; std::vector<uint32_t> length; std::vector<std::string> name; std::string names; std::vector<uint32_t> name_offset; ahost_virus_contigs view(); };
+struct VirusCounters { uint64_t total = 0, candidates = 0, kmer_keys = 0; std::vector<uint64_t> reads, covered, kmer_count, shared; std::vector<uint32_t> active; agpu_virus_counters view() const; };
+void virus_contigs_of(const uint8_t* input, size_t size, const std::string& viral_contigs, VirusContigs& contigs);
+void virus_expression(const uint8_t* records, uint64_t size, const int32_t* viral_ref, const uint32_t* viral_length, uint32_t n_viruses, uint32_t n_ref, VirusCounters& counters);
+std::string virus_expression_table(const agpu_virus_counters& counters, const ahost_virus_contigs& contigs);
+void virus_expression_write(const std::string& text, const std::string& path); // through path + ".tmp"; on a failure nothing is left behind
 const std::vector<uint8_t>& bam_feed_header_bytes(BamFeed* feed); // the head of the uncompressed input as the feed read it: the BAM header, or the '@' lines of SAM text
 
 // reference: source/read_chimeric_alignments.cpp:560-773 with separate_chimeric_bam_file=false, is_rna_bam_file=true

@@ -761,6 +761,49 @@ int ahost_supporting_alignments_file(ahost_session* session, const ahost_fusion_
 	} catch (const std::exception& e) { g_error = e.what(); return -1; }
 }
 
+// ---- --virus-expression (include/arriba_host.h) ----
+namespace {
+thread_local VirusContigs g_virus_contigs; thread_local VirusCounters g_virus_counters; thread_local std::string g_virus_text;
+}
+int ahost_virus_contigs_of_session(ahost_session* session, ahost_virus_contigs* contigs) {
+	if (!session || !contigs) { g_error = "null argument"; return -1; }
+	if (session->input_header.empty()) { g_error = "ahost_bam_open must run first"; return -1; }
+	try { virus_contigs_of(session->input_header.data(), session->input_header.size(), session->options.viral_contigs, g_virus_contigs); *contigs = g_virus_contigs.view(); return 0; }
+	catch (const std::exception& e) { g_error = e.what(); return -1; }
+}
+int ahost_virus_contigs_of(const void* input_header, size_t size, const char* viral_contigs, ahost_virus_contigs* contigs) {
+	if (!input_header || !contigs) { g_error = "null argument"; return -1; }
+	try { virus_contigs_of((const uint8_t*) input_header, size, viral_contigs ? viral_contigs : IngestOptions().viral_contigs, g_virus_contigs); *contigs = g_virus_contigs.view(); return 0; }
+	catch (const std::exception& e) { g_error = e.what(); return -1; }
+}
+int ahost_virus_expression(const void* records, size_t size, const ahost_virus_contigs* contigs, agpu_virus_counters* counters) {
+	if ((!records && size > 0) || !contigs || !counters) { g_error = "null argument"; return -1; }
+	try { virus_expression((const uint8_t*) records, size, contigs->viral_ref, contigs->viral_length, contigs->n_viruses, contigs->n_ref, g_virus_counters); *counters = g_virus_counters.view(); return 0; }
+	catch (const std::exception& e) { g_error = e.what(); return -1; }
+}
+int ahost_virus_expression_table(const agpu_virus_counters* counters, const ahost_virus_contigs* contigs, const char** text, uint64_t* bytes) {
+	if (!counters || !contigs || !text || !bytes) { g_error = "null argument"; return -1; }
+	try { g_virus_text = virus_expression_table(*counters, *contigs); *text = g_virus_text.data(); *bytes = g_virus_text.size(); return 0; }
+	catch (const std::exception& e) { g_error = e.what(); return -1; }
+}
+int ahost_virus_expression_write(const agpu_virus_counters* counters, const ahost_virus_contigs* contigs, const char* path) {
+	if (!counters || !contigs || !path) { g_error = "null argument"; return -1; }
+	try { virus_expression_write(virus_expression_table(*counters, *contigs), path); return 0; }
+	catch (const std::exception& e) { g_error = e.what(); return -1; }
+}
+int ahost_virus_expression_file(ahost_session* session, const char* input_path, const char* path) {
+	if (!session || !input_path || !path) { g_error = "null argument"; return -1; }
+	try {
+		std::vector<uint8_t> stream;
+		const uint64_t at = read_whole_bam(input_path, stream); // (SAM text comes out as the BAM stream of its alignments, behind a BAM header)
+		VirusContigs contigs; VirusCounters counters;
+		virus_contigs_of(stream.data(), at, session->options.viral_contigs, contigs);
+		virus_expression(stream.data() + at, stream.size() - at, contigs.ref.data(), contigs.length.data(), (uint32_t) contigs.ref.size(), contigs.n_ref, counters);
+		virus_expression_write(virus_expression_table(counters.view(), contigs.view()), path);
+		return 0;
+	} catch (const std::exception& e) { g_error = e.what(); return -1; }
+}
+
 void ahost_bam_close(ahost_session* session) { if (session && session->feed) { close_bam_feed(session->feed); session->feed = nullptr; } }
 
 int ahost_adopt_device_ingest(ahost_session* session, const agpu_ingest_result* result, const uint64_t* viral_read_counts, const uint16_t* coverage, const uint8_t* fragment_starts, const uint8_t* fragment_ends) {

@@ -12,6 +12,29 @@ import numpy as np
 from . import _capi
 
 
+def _array(pointer, count, kind):
+    return np.ctypeslib.as_array(ctypes.cast(pointer, POINTER(kind)), (count,)).copy() if count else np.zeros(0, np.dtype(kind))
+
+
+def virus_counters_of(counters):
+    """agpu_virus_counters (the device's or the host's) as a dict of numbers and arrays of its own"""
+    n, m = counters.n_viruses, counters.n_active
+    out = {name: _array(getattr(counters, name), n, c_uint64) for name in ("reads", "covered", "kmer_count")}
+    out.update({"total": int(counters.total), "active": _array(counters.active, m, c_uint32), "shared": _array(counters.shared, m * m, c_uint64).reshape(m, m)})
+    out.update({name: int(getattr(counters, name)) for name in ("candidates", "kmer_keys", "kmer_rounds", "peak_bytes")})
+    out["seconds"] = dict(zip(("scan", "candidates", "kmer_sets", "covered"), counters.seconds))
+    return out
+
+
+def virus_contigs_of(contigs):
+    """ahost_virus_contigs as a dict"""
+    n = contigs.n_viruses
+    offsets = _array(contigs.name_offset, n + 1, c_uint32)
+    text = ctypes.string_at(contigs.names, int(offsets[-1])) if n else b""
+    return {"n_ref": int(contigs.n_ref), "viral_ref": _array(contigs.viral_ref, n, c_int32), "viral_length": _array(contigs.viral_length, n, c_uint32),
+            "names": [text[offsets[k]:offsets[k + 1]].decode() for k in range(n)]}
+
+
 class ArribaError(RuntimeError):
     pass
 
@@ -158,13 +181,14 @@ class WorkflowSession(object):
         if self._lib.arriba_workflow_sorted_bam_compression(self._session, int(level)) != 0:
             raise ArribaError(self._lib.arriba_workflow_last_error().decode())
 
-    def submit(self, bam, sorted_bam_file=None, supporting_alignments_prefix=None, sorted_bam_compression=None):
+    def submit(self, bam, sorted_bam_file=None, supporting_alignments_prefix=None, sorted_bam_compression=None, virus_expression_file=None):
         """the sample that comes after the one `sample` is called for next: its file is fed (PCIe, the front of read_chimeric_alignments) while the stages of that one run;
         sorted_bam_file: its records in coordinate order with their index (--sorted-bam), written when its ingest is finished; sorted_bam_compression: its level (None: as it is)"""
         if sorted_bam_compression is not None:
             self.sorted_bam_compression(sorted_bam_compression)
         self._lib.arriba_workflow_sorted_bam(self._session, sorted_bam_file.encode() if sorted_bam_file else None)
         self._lib.arriba_workflow_supporting_alignments(self._session, supporting_alignments_prefix.encode() if supporting_alignments_prefix else None)  # (--supporting-alignments: PREFIX_ID.bam per row of its fusions file)
+        self._lib.arriba_workflow_virus_expression(self._session, virus_expression_file.encode() if virus_expression_file else None)  # (--virus-expression: its table, written when its ingest is finished)
         if self._lib.arriba_workflow_submit(self._session, bam.encode()) != 0:
             raise ArribaError(self._lib.arriba_workflow_last_error().decode())
         if self._profiling_on:
@@ -259,7 +283,7 @@ class WorkflowSession(object):
     def _lane_contexts(self):
         return [ctx for ctx in (self._lib.arriba_workflow_lane_device(self._session, lane) for lane in (0, 1)) if ctx]
 
-    def sample(self, bam, output_file, discarded_output_file=None, sorted_bam_file=None, supporting_alignments_prefix=None, sorted_bam_compression=None):
+    def sample(self, bam, output_file, discarded_output_file=None, sorted_bam_file=None, supporting_alignments_prefix=None, sorted_bam_compression=None, virus_expression_file=None):
         """one sample, BAM file -> fusions.tsv (and discarded.tsv); returns the stages with their "(remaining=N)" counts.  sorted_bam_file (--sorted-bam): for a sample that was
         not submitted ahead; one that was says it to `submit`"""
         report, timing = _capi.WorkflowReport(), _capi.WorkflowTiming()
@@ -269,6 +293,8 @@ class WorkflowSession(object):
             self._lib.arriba_workflow_sorted_bam(self._session, sorted_bam_file.encode())
         if supporting_alignments_prefix:  # (as sorted_bam_file: for a sample that was not submitted ahead)
             self._lib.arriba_workflow_supporting_alignments(self._session, supporting_alignments_prefix.encode())
+        if virus_expression_file:  # (likewise)
+            self._lib.arriba_workflow_virus_expression(self._session, virus_expression_file.encode())
         if self._lib.arriba_workflow_sample(self._session, bam.encode(), output_file.encode(), discarded_output_file.encode() if discarded_output_file else None, byref(report), byref(timing)) != 0:
             raise ArribaError(self._lib.arriba_workflow_last_error().decode())
         self.ctx = self._lib.arriba_workflow_device(self._session)  # (the lane that worked on this sample)
@@ -571,6 +597,35 @@ class DevicePipeline(object):
             self._check(self.api.support_pool_build(self.ctx, ctypes.cast(text, ctypes.c_void_p), offsets.ctypes.data, len(encoded), byref(info)))
         return {name: int(getattr(info, name)) for name in ("names", "stream_records", "pooled_records", "pool_bytes")}
 
+    def virus_expression(self):
+        """The counters of --virus-expression from the record stream of the last read_chimeric_alignments (agpu_virus_expression), for the viral contigs that the session's -v names
+        in the header of its file.  Valid after read_chimeric_alignments and before the next one.  Returns (counters, contigs): counters {"total", "reads", "covered", "kmer_count"
+        [n_viruses], "active" [n_active], "shared" [n_active, n_active], "candidates", "kmer_keys", "kmer_rounds", "peak_bytes", "seconds"}; contigs {"n_ref", "viral_ref",
+        "viral_length", "names"}.  The two structures as the C ABI filled them are kept for write_virus_expression."""
+        if not self.device_ingest or not hasattr(self.api, "virus_expression"):
+            raise ArribaError("ERROR: a virus expression table needs the record stream of an ingest on the device (DevicePipeline(bam=...))")
+        lib, handle = self.session._lib, self.session._session
+        contigs = _capi.VirusContigs()
+        if lib.ahost_virus_contigs_of_session(handle, byref(contigs)) != 0:
+            raise ArribaError("ERROR: " + lib.ahost_last_error().decode())
+        counters = _capi.VirusCounters()
+        self._check(self.api.virus_expression(self.ctx, contigs.viral_ref, contigs.viral_length, contigs.n_viruses, contigs.n_ref, byref(counters)))
+        self._virus = (counters, contigs)
+        return virus_counters_of(counters), virus_contigs_of(contigs)
+
+    def write_virus_expression(self, path):
+        """--virus-expression: the table of the reference's scripts/quantify_virus_expression.sh (default parameters) as `path`, written through `path`.tmp; returns the counters"""
+        counters, contigs = self.virus_expression()
+        lib = self.session._lib
+        if lib.ahost_virus_expression_write(byref(self._virus[0]), byref(self._virus[1]), path.encode()) != 0:
+            raise ArribaError("ERROR: " + lib.ahost_last_error().decode())
+        return counters
+
+    def virus_allocated_bytes(self):
+        count = c_uint64()
+        self._check(self.api.virus_allocated_bytes(self.ctx, byref(count)))
+        return int(count.value)
+
     def release_support_pool(self):
         self._check(self.api.support_pool_release(self.ctx))
 
@@ -824,13 +879,15 @@ class DevicePipeline(object):
                      max_genomic_breakpoint_distance=100000, strandedness=None, evalue_cutoff=0.3,
                      min_itd_support=10, min_itd_allele_fraction=0.07, high_expression_quantile=0.998, min_spliced_events=4, min_anchor_length=23,
                      max_homolog_identity=0.3, max_itd_length=100, fill_sequence_gaps=False, top_viral_contigs=5, viral_contig_min_covered_fraction=0.05,
-                     print_extra_info_for_discarded_fusions=False, log=None, sorted_bam_file=None, supporting_alignments_prefix=None, supporting_alignments_window=1000000):
+                     print_extra_info_for_discarded_fusions=False, log=None, sorted_bam_file=None, supporting_alignments_prefix=None, supporting_alignments_window=1000000, virus_expression_file=None):
         """The reference's main() behind read_chimeric_alignments (source/arriba.cpp:119-610) with its default parameters: the read-level cascade, find_fusions,
         every candidate-level filter in the reference's order, assign_confidence, and the two output files.  `log` receives (stage, remaining) pairs --
         the numbers the reference prints as "(remaining=N)".  Filters switched off with -f are skipped by the stages themselves (agpu_params.filter_enabled)."""
         note = log if log is not None else (lambda stage, remaining: None)
         if sorted_bam_file:  # first: the record stream is still in HBM (it is given back when the stages need the memory)
             self.write_sorted_bam(sorted_bam_file)
+        if virus_expression_file:  # (--virus-expression: likewise from the stream)
+            self.write_virus_expression(virus_expression_file)
         if supporting_alignments_prefix:  # (--supporting-alignments, phase 1: the records of the names of the batch leave the stream while it is there)
             self.build_support_pool()
         self.run_read_level(strandedness, top_viral_contigs, viral_contig_min_covered_fraction)

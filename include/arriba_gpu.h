@@ -372,6 +372,30 @@ int agpu_supporting_index(agpu_ctx* ctx, uint64_t first_block_file_offset, agpu_
 int agpu_supporting_end(agpu_ctx* ctx);
 int agpu_support_pool_release(agpu_ctx* ctx);
 int agpu_support_allocated_bytes(agpu_ctx* ctx, uint64_t* bytes); /* of the "support.*" buffers of the context: 0 as long as the option was never used on it, and behind agpu_support_pool_release */
+/* --virus-expression: the counters of the table that the reference's workflow gets from scripts/quantify_virus_expression.sh (default parameters), from the record stream of the
+ * last ingest while it is in HBM (arriba_amd/csrc/device/agpu_virus.hip, virus_core.hpp; the rule: DESIGN.md 4.11).  The host turns them into the text (include/arriba_host.h:
+ * ahost_virus_expression_table).
+ *   agpu_virus_expression   behind agpu_ingest_finish, before the next agpu_ingest_begin on this context or its sibling (the refusals of agpu_sorted_bam_begin).  viral_ref: the
+ *                           refIDs of the viral contigs, ascending -- entry v is virus slot v --, viral_length: their LN, n_ref: references of the header.  More than 65 535 viral
+ *                           contigs: AGPU_ERR_INVALID with a message.  Buffers that do not fit: AGPU_ERR_NO_MEMORY, nothing is left behind.  The device buffers ("virus.*") are the
+ *                           context's own and are released before the call returns; the arrays `counters` points at are host memory of the context, valid until the next call.
+ * ARRIBA_VIRUS_KMER_WINDOW: k-mer keys that are emitted, sorted and merged into the set at a time (default 2^25; DESIGN.md 4.11 has the bound on memory that follows from it). */
+typedef struct {
+	uint64_t total;               /* records with flag bit 4 clear, on every contig */
+	uint32_t n_viruses, n_active; /* slots; slots with reads > 0 */
+	const uint64_t* reads;        /* [n_viruses] high-quality records */
+	const uint64_t* covered;      /* [n_viruses] distinct positions marked by M and X */
+	const uint64_t* kmer_count;   /* [n_viruses] distinct 12-mers */
+	const uint32_t* active;       /* [n_active] the slots with reads > 0, ascending */
+	const uint64_t* shared;       /* [n_active x n_active] entry a * n_active + b: 12-mers that active[a] and active[b] both have (the diagonal is 0) */
+	uint64_t candidates;          /* records that passed flag, reference and CIGAR (before the tandem test) */
+	uint64_t kmer_keys;           /* keys emitted (with duplicates) */
+	uint64_t kmer_rounds;         /* sort-and-merge rounds */
+	uint64_t peak_bytes;          /* of the "virus.*" buffers (0 on the host) */
+	double seconds[4];            /* scan; per candidate; k-mer sets and shared counts; coverage popcount and copies (device: from HIP events, 0 on the host) */
+} agpu_virus_counters;
+int agpu_virus_expression(agpu_ctx* ctx, const int32_t* viral_ref, const uint32_t* viral_length, uint32_t n_viruses, uint32_t n_ref, agpu_virus_counters* counters);
+int agpu_virus_allocated_bytes(agpu_ctx* ctx, uint64_t* bytes); /* of the "virus.*" buffers of the context: 0 outside agpu_virus_expression */
 /* what the host's sequential stages and its output writer need from a batch that lives on the device:
  *   agpu_get_viral_read_counts   mapped_viral_reads_by_contig (source/read_chimeric_alignments.cpp:735-739)
  *   agpu_get_coverage            coverage_t as the reference holds it (16-bit saturating windows, start/end flags); sizes by coverage_window_offset

@@ -120,6 +120,30 @@ int ahost_supporting_writer_index(ahost_supporting_writer* writer, const agpu_su
 int ahost_supporting_writer_close(ahost_supporting_writer* writer, int commit);
 int ahost_supporting_alignments(const void* input_header, size_t header_size, const void* records, size_t size, const char* names, const uint64_t* name_offset, uint64_t n_names,
                                 const agpu_supporting_rows* rows, int64_t window, const char* prefix, agpu_supporting_info* info /* may be NULL */);
+/* ---- --virus-expression: the host side of agpu_virus_expression (include/arriba_gpu.h) -- the table of the reference's scripts/quantify_virus_expression.sh with its default
+ * parameters (the rule: DESIGN.md 4.11) ----
+ *   ahost_virus_contigs_of_session  the viral contigs of the header of the file the last ahost_bam_open opened, by the patterns of -v of the session: slot v is viral_ref[v]
+ *   ahost_virus_contigs_of       the same from the head of an uncompressed input in memory (a BAM header, or the '@' lines of SAM text); viral_contigs NULL: "AC_* NC_*".
+ *                                Both: valid until the next call on the thread
+ *   ahost_virus_expression       arriba_amd/csrc/device/virus_core.hpp stepped on the host over BAM records in host memory: the counters the device gives (its comparator; the
+ *                                CPU tier); valid until the next call on the thread
+ *   ahost_virus_expression_table counters to the text: RPKM in double precision, related strains collapsed onto the most expressed one, the thresholds of 100 bases and 5 %,
+ *                                numbers as awk prints them, rows in the order of `LC_ALL=C sort -k6,6gr`; valid until the next call on the thread
+ *   ahost_virus_expression_write the text into `path`, through path.tmp; on a failure nothing is left behind
+ *   ahost_virus_expression_file  all of it for a file (BAM in BGZF, gzip or raw; SAM text) with the patterns of the session: what --host-ingest runs */
+typedef struct {
+	uint32_t n_ref, n_viruses;
+	const int32_t* viral_ref;     /* [n_viruses] ascending refIDs */
+	const uint32_t* viral_length; /* [n_viruses] LN */
+	const char* names;            /* the names of the viral contigs, one behind the other */
+	const uint32_t* name_offset;  /* [n_viruses + 1] */
+} ahost_virus_contigs;
+int ahost_virus_contigs_of_session(ahost_session* session, ahost_virus_contigs* contigs);
+int ahost_virus_contigs_of(const void* input_header, size_t size, const char* viral_contigs, ahost_virus_contigs* contigs);
+int ahost_virus_expression(const void* records, size_t size, const ahost_virus_contigs* contigs, agpu_virus_counters* counters);
+int ahost_virus_expression_table(const agpu_virus_counters* counters, const ahost_virus_contigs* contigs, const char** text, uint64_t* bytes);
+int ahost_virus_expression_write(const agpu_virus_counters* counters, const ahost_virus_contigs* contigs, const char* path);
+int ahost_virus_expression_file(ahost_session* session, const char* input_path, const char* path);
 int ahost_adopt_device_ingest(ahost_session* session, const agpu_ingest_result* result, const uint64_t* viral_read_counts, const uint16_t* coverage, const uint8_t* fragment_starts, const uint8_t* fragment_ends);
 int ahost_set_batch_rows(ahost_session* session, const agpu_batch_rows* rows, const uint32_t* fragments /* [rows->n] ascending: the fragment every row holds; NULL: row k holds the fragment
                          of entry k of the read lists of the table the next ahost_write_fusions writes (the reads of a candidate next to each other; the table then carries read_filter_of_rows) */);

@@ -56,6 +56,10 @@ typedef struct {
 	int sorted_bam_compression;           /* --sorted-bam-compression: 0 (and a zero-initialised struct) = the record blocks of sorted_bam_file are stored; 1 = each is deflated on the device
 	                                         (include/arriba_gpu.h: agpu_sorted_bam_set_compression; with host_ingest: the same code stepped on the host).  Anything else fails the sample.  The files
 	                                         of supporting_alignments_prefix stay stored. */
+	const char* virus_expression_file;    /* --virus-expression; NULL (and a zero-initialised struct) = none.  The table of the reference's scripts/quantify_virus_expression.sh with its default
+	                                         parameters -- per viral contig (-v) genome size, covered bases, covered fraction, high-quality alignments and RPKM, related strains collapsed onto the
+	                                         most expressed one --, counted behind read_chimeric_alignments from the record stream in HBM (include/arriba_gpu.h: agpu_virus_expression; DESIGN.md
+	                                         4.11).  Of arriba_workflow_run's sample; the samples of a session say theirs with arriba_workflow_virus_expression.  Not for one sample over several ranks. */
 } arriba_workflow_options;
 
 /* what the reference prints as "(remaining=N)" / "(total=N)" / "(marked=N)", in the order of the stages; stage names as in the reference's source */
@@ -95,6 +99,7 @@ typedef struct { /* seconds of one sample, by part (wall clock of the calling th
 	double exchanged_bytes;  /*   ... and the bytes this rank received from the others in the exchanges of the sample (host collectives) */
 	double sorted_bam;       /* --sorted-bam: keys, sort, gather, copy back, the two files (inside `ingest`; beside the sample in front when the ingest was finished ahead) */
 	double supporting_alignments; /* --supporting-alignments: the pool behind the ingest (name table, marks, compaction) and the files behind fusions.tsv (join, gather, copy back, files, indexes) */
+	double virus_expression; /* --virus-expression: scan, candidates, k-mer sets, copies, the table (inside `ingest`; beside the sample in front when the ingest was finished ahead) */
 } arriba_workflow_timing;
 /* options->chimeric_bam_file, output_file and discarded_output_file are not used by open (they belong to a sample); NULL + arriba_workflow_last_error() on failure */
 arriba_workflow_session* arriba_workflow_open(const arriba_workflow_options* options);
@@ -116,6 +121,8 @@ int arriba_workflow_sorted_bam_compression(arriba_workflow_session* session, int
 /* --supporting-alignments of the sample that is submitted NEXT, in the same way; NULL: none.  The pool of its supporting alignments is built by the thread that finishes its ingest and
  * belongs to its lane until its fusions file is written; the window is options.supporting_alignments_window of arriba_workflow_open. */
 int arriba_workflow_supporting_alignments(arriba_workflow_session* session, const char* prefix);
+/* --virus-expression of the sample that is submitted NEXT, in the same way; NULL: none.  The table is written by the thread that finishes its ingest. */
+int arriba_workflow_virus_expression(arriba_workflow_session* session, const char* path);
 /* (If the device runs out of memory while two samples are in flight, arriba_workflow_sample throws away what was fed ahead, closes the second lane, runs its sample again with the device
  * to itself and submits the other sample again behind it -- once; a sample that does not fit the device alone fails the call.  INTEGRATION.md, "Memory".) */
 /* on: arriba_workflow_sample returns when the last output file of the sample (-O if given, else -o) has everything it needs off the device; the file is formatted and written
