@@ -262,6 +262,7 @@ def bind_device_api(lib, prefix="agpu_"):
         "ingest_sam_targets": (c_int, [ctx, c_void_p, c_void_p, c_uint32]),
         "ingest_push_sam": (c_int, [ctx, c_void_p, c_size_t, c_uint64]),
         "sam_transcode": (c_int, [ctx, c_void_p, c_size_t, c_void_p, c_void_p, c_uint32, c_void_p, c_size_t, POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64)]),
+        "bgzf_unpack": (c_int, [ctx, c_void_p, c_size_t, POINTER(BgzfBlock), c_uint32, c_int, c_void_p, c_size_t, c_void_p, POINTER(c_uint32), POINTER(c_uint32)]),
         "ingest_finish": (c_int, [ctx, POINTER(IngestResult)]),
         "sorted_bam_begin": (c_int, [ctx, POINTER(SortedBamInfo)]),
         "sorted_bam_next": (c_int, [ctx, c_void_p, c_uint64, POINTER(c_uint64)]),

@@ -104,8 +104,9 @@ __global__ void __launch_bounds__(BLOCK) bgzf_inflate_resolve_kernel(const agpu_
 }
 
 // The decoder of round 4: one wavefront per deflated block (inflate_core.hpp).  It takes the blocks pass 1 hands back (INFLATE_RETRY: more matches than it has room to note)
-// -- status == nullptr: all blocks (ARRIBA_INFLATE=wave, the measured alternative).
-__global__ void __launch_bounds__(64, 3) bgzf_inflate_kernel(const uint8_t* raw, const agpu_bgzf_block* blocks, uint8_t* stream, uint8_t* spill, int* status, unsigned int* failures) {
+// -- status == nullptr: all blocks (ARRIBA_INFLATE=wave, the measured alternative).  The status of a block taken over stays INFLATE_RETRY -- that is why pass 2 leaves the
+// block alone (its list of notes is a part of the block's matches); what became of it goes to `verdict`, where somebody asks (agpu_bgzf_unpack; the ingest counts `failures`).
+__global__ void __launch_bounds__(64, 3) bgzf_inflate_kernel(const uint8_t* raw, const agpu_bgzf_block* blocks, uint8_t* stream, uint8_t* spill, int* status, int* verdict, unsigned int* failures) {
 	__shared__ InflateShared shared;
 	if (status != nullptr && status[blockIdx.x] != INFLATE_RETRY) return;
 	const agpu_bgzf_block block = blocks[blockIdx.x];
@@ -114,6 +115,7 @@ __global__ void __launch_bounds__(64, 3) bgzf_inflate_kernel(const uint8_t* raw,
 	auto sync = [] () { __syncthreads(); };
 	auto broadcast = [] (uint32_t value) { return (uint32_t) __builtin_amdgcn_readfirstlane((int) value); };
 	const int result = inflate_block(raw + block.raw_offset + block.payload_offset, block.payload_size, target, block.isize, shared, threadIdx.x, 64u, sync, broadcast);
+	if (verdict != nullptr && threadIdx.x == 0) verdict[blockIdx.x] = result;
 	if (result != INFLATE_OK) { if (threadIdx.x == 0) atomicAdd(failures, 1u); return; }
 	if (partial) {
 		__syncthreads();
@@ -904,6 +906,59 @@ void fill_pack_target(agpu_ctx* ctx, PackTarget& out) {
 	out.seq_pool = ctx->seq_pool.as<uint8_t>(); out.name_offset = ctx->name_offset.as<uint64_t>(); out.row_name_offset = nullptr; out.names = ctx->names.as<char>();
 }
 
+// ---- the kernels of one piece of BGZF blocks ----------------------------------------------------------------------------------------------------------------
+// What agpu_ingest_push_bgzf launches for a piece of the file and agpu_bgzf_unpack (tests and tools) for a caller's blocks: the payloads into the stream -- stored blocks
+// moved, deflated ones through the two passes (or, lanes == -1, all of them through the one-wavefront-per-block decoder) --, `ready` recorded behind them, then the CRC-32s.
+struct BgzfPiece {
+	const uint8_t* raw; const agpu_bgzf_block* blocks; uint32_t n_blocks; // (on the device)
+	uint64_t raw_bytes, stream_bytes; // (for the profile)
+	uint8_t* target;                  // where stream_offset 0 of the blocks lies
+	uint8_t* spill;                   // deflated blocks: 2 x 64 KB
+	int lanes;                        // deflated blocks: blocks per wavefront in pass 1 (16, 24, anything else: 20); -1: no pass 1
+	unsigned long long* notes; uint32_t* note_count; int* status; // lanes != -1: [n_blocks x INFLATE_MATCH_CAPACITY], [n_blocks], [n_blocks]
+	int* verdict;                     // [n_blocks] or null: bgzf_inflate_kernel
+	unsigned int* counters;           // [0] blocks whose CRC-32 is not that of their trailer, [1] deflated blocks that did not decode
+	const Crc32Tables* crc_tables;    // null: the CRC-32s are not checked
+	hipEvent_t ready_before, ready;   // `ready` is recorded when the bytes of the blocks are in the stream, behind `ready_before`; null: no such event
+};
+int launch_bgzf_piece(agpu_ctx* ctx, hipStream_t pieces, bool deflated, const BgzfPiece& p) {
+	const uint32_t n_blocks = p.n_blocks;
+	if (deflated) {
+		unsigned int* failures = p.counters + 1;
+		if (p.lanes == -1) {
+			KernelTimer timer(ctx, "bgzf_inflate_kernel", p.raw_bytes + p.stream_bytes, pieces);
+			bgzf_inflate_kernel<<<n_blocks, 64, 0, pieces>>>(p.raw, p.blocks, p.target, p.spill, nullptr, p.verdict, failures);
+		} else {
+			{ KernelTimer timer(ctx, "bgzf_inflate_tokens_kernel", p.raw_bytes + p.stream_bytes, pieces);
+			  #define TOKENS(LANES) bgzf_inflate_tokens_kernel<LANES><<<(n_blocks + LANES - 1) / LANES, LANES, 0, pieces>>>(p.raw, p.blocks, n_blocks, p.target, p.spill, p.notes, p.note_count, p.status, failures)
+			  if (p.lanes == 16) TOKENS(16); else if (p.lanes == 24) TOKENS(24); else TOKENS(20);
+			  #undef TOKENS
+			}
+			bgzf_inflate_kernel<<<n_blocks, 64, 0, pieces>>>(p.raw, p.blocks, p.target, p.spill, p.status, p.verdict, failures); // (returns at once but for the blocks handed back)
+			{ KernelTimer timer(ctx, "bgzf_inflate_resolve_kernel", p.stream_bytes, pieces);
+			  bgzf_inflate_resolve_kernel<<<(n_blocks + BLOCK / 64 - 1) / (BLOCK / 64), BLOCK, 0, pieces>>>(p.blocks, n_blocks, p.target, p.spill, p.notes, p.note_count, p.status); }
+		}
+	}
+	else { KernelTimer timer(ctx, "bgzf_unwrap_kernel", p.raw_bytes + p.stream_bytes, pieces);
+	  bgzf_unwrap_kernel<<<n_blocks, BLOCK, 0, pieces>>>(p.raw, p.blocks, p.target); }
+	if (p.ready_before) HIP_CHECK(hipStreamWaitEvent(pieces, p.ready_before, 0)); // (ready in the order of the pieces, whichever stream they took)
+	if (p.ready) HIP_CHECK(hipEventRecord(p.ready, pieces));
+	if (p.crc_tables) { // (~1 ms per 256 MB piece; between the copies on one stream it cost 0.3 s of a 54 GB file)
+		KernelTimer timer(ctx, "bgzf_crc_kernel", deflated ? p.stream_bytes : p.raw_bytes, pieces);
+		if (deflated) bgzf_crc_kernel<true><<<(n_blocks + 3) / 4, 256, 0, pieces>>>(p.target, p.blocks, n_blocks, p.crc_tables, p.counters);
+		else bgzf_crc_kernel<false><<<(n_blocks + 3) / 4, 256, 0, pieces>>>(p.raw, p.blocks, n_blocks, p.crc_tables, p.counters);
+	}
+	return AGPU_OK;
+}
+int upload_crc_tables(agpu_ctx* ctx) { // (once per context)
+	if (ctx->scratch("ingest.crc_tables").ptr != nullptr) return AGPU_OK;
+	ALLOC(ctx->scratch("ingest.crc_tables"), sizeof(Crc32Tables));
+	static Crc32Tables tables; static bool made = false;
+	if (!made) { crc32_make_tables(tables); made = true; }
+	HIP_CHECK(hipMemcpy(ctx->scratch("ingest.crc_tables").ptr, &tables, sizeof(tables), hipMemcpyHostToDevice));
+	return AGPU_OK;
+}
+
 }
 
 int agpu::ingest_grow_stream(agpu_ctx* ctx, uint64_t needed) { return grow_stream(ctx, needed); }
@@ -921,6 +976,7 @@ bool agpu::release_ingest_buffers(agpu_ctx* ctx) {
 		"ingest.valid", "ingest.sizes", "ingest.refs", "ingest.order", "ingest.order_keys", "ingest.order_keys_sorted", "ingest.cigar_words", "ingest.sequence_bytes", "ingest.name_lengths", "ingest.new_group", "ingest.cigar_base",
 		"ingest.sequence_base", "ingest.name_base", "ingest.group_id", "ingest.qname_differs", "ingest.qname_run", "ingest.run_keys", "ingest.run_keys_sorted", "ingest.window_rocprim", "ingest.segment_first", "ingest.segment_end", "ingest.segment_end_before", "ingest.segment_count", "ingest.segment_base", "ingest.segment_mismatch", "ingest.rocprim", "ingest.coverage_summed", "ingest.hit_index",
 		"sam.wave_count", "sam.wave_base", "sam.line_start", "sam.record_size", "sam.record_offset", "sam.rocprim", "sam.tool_text", "sam.tool_records",
+		"bgzf.tool_raw", "bgzf.tool_blocks", "bgzf.tool_out", "bgzf.tool_notes", "bgzf.tool_note_count", "bgzf.tool_status", "bgzf.tool_verdict",
 		"sortedbam.keys", "sortedbam.keys_sorted", "sortedbam.order", "sortedbam.sizes", "sortedbam.sizes_sorted", "sortedbam.end_flag", "sortedbam.out_offset", "sortedbam.block_first", "sortedbam.staging", "sortedbam.rocprim", "sortedbam.crc_tables",
 		"sortedbam.ref_length", "sortedbam.interval_offset", "sortedbam.intervals", "sortedbam.ref_stats", "sortedbam.heads", "sortedbam.chunk_id", "sortedbam.chunk_key", "sortedbam.chunk_begin", "sortedbam.chunk_end", "sortedbam.chunk_key_sorted", "sortedbam.chunk_order", "sortedbam.chunk_out" };
 	ctx->last_ingest_kept = false; // (agpu_sorted_bam_begin says so instead of reading freed memory)
@@ -961,12 +1017,7 @@ int agpu_ingest_begin(agpu_ctx* ctx, const agpu_ingest_config* config) {
 	ctx->ingest_n_targets = config->n_targets; ctx->ingest_first_record = config->first_record_offset; ctx->ingest_stream_size = 0; ctx->ingest_pushes = 0; ctx->ingest_deflated_pieces = false; ctx->ingest_sam = false;
 	{ const char* knob = getenv("ARRIBA_VERIFY_CRC"); ctx->ingest_verify_crc = !(knob != nullptr && knob[0] == '0'); } // (the stored blocks are checked as htslib checks them; "0": a measurement without)
 	ALLOC(ctx->scratch("ingest.crc_mismatches"), 8); // [0] blocks whose payload does not give the CRC-32 of their trailer, [1] deflated blocks that did not decode (read whatever ARRIBA_VERIFY_CRC says)
-	if (ctx->ingest_verify_crc && ctx->scratch("ingest.crc_tables").ptr == nullptr) {
-		ALLOC(ctx->scratch("ingest.crc_tables"), sizeof(Crc32Tables));
-		static Crc32Tables tables; static bool made = false;
-		if (!made) { crc32_make_tables(tables); made = true; }
-		HIP_CHECK(hipMemcpy(ctx->scratch("ingest.crc_tables").ptr, &tables, sizeof(tables), hipMemcpyHostToDevice));
-	}
+	if (ctx->ingest_verify_crc) TRY(upload_crc_tables(ctx));
 	HIP_CHECK(hipMemsetAsync(ctx->scratch("ingest.crc_mismatches").ptr, 0, 8, s));
 	ctx->ingest_external_duplicate_marking = config->external_duplicate_marking; ctx->ingest_max_itd_length = config->max_itd_length; ctx->ingest_part_of_sample = config->part_of_sample != 0;
 	ALLOC(ctx->ingest_tid_to_contig, std::max<size_t>(config->n_targets, 1) * 4);
@@ -1046,50 +1097,97 @@ int agpu_ingest_push_bgzf(agpu_ctx* ctx, const void* raw, size_t raw_size, const
 		HIP_CHECK(hipMemcpyAsync(ctx->ingest_blocks[slot].ptr, blocks, (size_t) n_blocks * sizeof(agpu_bgzf_block), hipMemcpyHostToDevice, s));
 		HIP_CHECK(hipEventRecord(ctx->piece_copied[slot], s));
 		HIP_CHECK(hipStreamWaitEvent(pieces, ctx->piece_copied[slot], 0));
+		BgzfPiece piece = {};
+		piece.raw = ctx->ingest_raw[slot].as<uint8_t>(); piece.blocks = ctx->ingest_blocks[slot].as<agpu_bgzf_block>(); piece.n_blocks = n_blocks; piece.raw_bytes = raw_size; piece.stream_bytes = stream_bytes;
+		piece.target = ctx->ingest_stream.as<uint8_t>() + ctx->ingest_stream_size;
+		piece.counters = ctx->scratch("ingest.crc_mismatches").as<unsigned int>();
 		if (deflated) {
 			ctx->ingest_deflated_pieces = true;
-			uint8_t* target = ctx->ingest_stream.as<uint8_t>() + ctx->ingest_stream_size;
-			unsigned int* failures = ctx->scratch("ingest.crc_mismatches").as<unsigned int>() + 1;
+			piece.spill = ctx->scratch("ingest.inflate_spill").as<uint8_t>();
 			static const char* way = getenv("ARRIBA_INFLATE"); // "wave": the one-wavefront-per-block decoder of round 4 for every block; "16" / "24": other numbers of blocks per wavefront in pass 1 (measurements)
-			if (way != nullptr && strcmp(way, "wave") == 0) {
-				KernelTimer timer(ctx, "bgzf_inflate_kernel", (uint64_t) raw_size + stream_bytes, pieces);
-				bgzf_inflate_kernel<<<n_blocks, 64, 0, pieces>>>(ctx->ingest_raw[slot].as<uint8_t>(), ctx->ingest_blocks[slot].as<agpu_bgzf_block>(), target, ctx->scratch("ingest.inflate_spill").as<uint8_t>(), nullptr, failures);
-			} else {
+			// (20 lanes x 2 032 bytes of tables: four such workgroups fill the 160 KB of a CU -- 80 blocks per CU, all ~17 000 blocks of a piece resident at once)
+			piece.lanes = way != nullptr && strcmp(way, "wave") == 0 ? -1 : way != nullptr && atoi(way) > 0 ? atoi(way) : 20;
+			if (piece.lanes != -1) {
 				// (the kernels of the pieces of one stream run one after the other: one set of notes per stream serves all slots)
 				DeviceBuffer& notes = ctx->scratch(set ? "ingest.inflate_notes2" : "ingest.inflate_notes"); DeviceBuffer& note_count = ctx->scratch(set ? "ingest.inflate_note_count2" : "ingest.inflate_note_count"); DeviceBuffer& status = ctx->scratch(set ? "ingest.inflate_status2" : "ingest.inflate_status");
 				if ((size_t) n_blocks * INFLATE_MATCH_CAPACITY * 8 > notes.capacity || (size_t) n_blocks * 4 > status.capacity) {
 					HIP_CHECK(hipStreamSynchronize(pieces)); // (the pieces before this one read the buffers that are about to be replaced)
 					ALLOC(notes, (size_t) n_blocks * INFLATE_MATCH_CAPACITY * 8); ALLOC(note_count, (size_t) n_blocks * 4); ALLOC(status, (size_t) n_blocks * 4);
 				}
-				const int lanes = way != nullptr && atoi(way) > 0 ? atoi(way) : 20; // (20 lanes x 2 032 bytes of tables: four such workgroups fill the 160 KB of a CU -- 80 blocks per CU, all ~17 000 blocks of a piece resident at once)
-				{ KernelTimer timer(ctx, "bgzf_inflate_tokens_kernel", (uint64_t) raw_size + stream_bytes, pieces);
-				  #define TOKENS(LANES) bgzf_inflate_tokens_kernel<LANES><<<(n_blocks + LANES - 1) / LANES, LANES, 0, pieces>>>(ctx->ingest_raw[slot].as<uint8_t>(), ctx->ingest_blocks[slot].as<agpu_bgzf_block>(), n_blocks, target, \
-				  	ctx->scratch("ingest.inflate_spill").as<uint8_t>(), notes.as<unsigned long long>(), note_count.as<uint32_t>(), status.as<int>(), failures)
-				  if (lanes == 16) TOKENS(16); else if (lanes == 24) TOKENS(24); else TOKENS(20);
-				  #undef TOKENS
-				}
-				bgzf_inflate_kernel<<<n_blocks, 64, 0, pieces>>>(ctx->ingest_raw[slot].as<uint8_t>(), ctx->ingest_blocks[slot].as<agpu_bgzf_block>(), target, ctx->scratch("ingest.inflate_spill").as<uint8_t>(), status.as<int>(), failures); // (returns at once but for the blocks handed back)
-				{ KernelTimer timer(ctx, "bgzf_inflate_resolve_kernel", (uint64_t) stream_bytes, pieces);
-				  bgzf_inflate_resolve_kernel<<<(n_blocks + BLOCK / 64 - 1) / (BLOCK / 64), BLOCK, 0, pieces>>>(ctx->ingest_blocks[slot].as<agpu_bgzf_block>(), n_blocks, target, ctx->scratch("ingest.inflate_spill").as<uint8_t>(),
-				  	notes.as<unsigned long long>(), note_count.as<uint32_t>(), status.as<int>()); }
+				piece.notes = notes.as<unsigned long long>(); piece.note_count = note_count.as<uint32_t>(); piece.status = status.as<int>();
 			}
 		}
-		else { KernelTimer timer(ctx, "bgzf_unwrap_kernel", (uint64_t) raw_size + stream_bytes, pieces);
-		  bgzf_unwrap_kernel<<<n_blocks, BLOCK, 0, pieces>>>(ctx->ingest_raw[slot].as<uint8_t>(), ctx->ingest_blocks[slot].as<agpu_bgzf_block>(), ctx->ingest_stream.as<uint8_t>() + ctx->ingest_stream_size); }
-		const uint64_t piece_stream_offset = ctx->ingest_stream_size;
+		if (ctx->ingest_pushes > 0) piece.ready_before = ctx->piece_ready[(ctx->ingest_pushes - 1) % AGPU_PIECE_SLOTS];
+		piece.ready = ctx->piece_ready[slot];
+		if (ctx->ingest_verify_crc) piece.crc_tables = ctx->scratch("ingest.crc_tables").as<Crc32Tables>();
 		ctx->ingest_stream_size += stream_bytes;
-		if (ctx->ingest_pushes > 0) HIP_CHECK(hipStreamWaitEvent(pieces, ctx->piece_ready[(ctx->ingest_pushes - 1) % AGPU_PIECE_SLOTS], 0)); // (ready in the order of the pieces, whichever stream they took)
-		HIP_CHECK(hipEventRecord(ctx->piece_ready[slot], pieces));
-		if (ctx->ingest_verify_crc) { // (~1 ms per 256 MB piece; between the copies on one stream it cost 0.3 s of a 54 GB file)
-			KernelTimer timer(ctx, "bgzf_crc_kernel", deflated ? stream_bytes : raw_size, pieces);
-			if (deflated) bgzf_crc_kernel<true><<<(n_blocks + 3) / 4, 256, 0, pieces>>>(ctx->ingest_stream.as<uint8_t>() + piece_stream_offset, ctx->ingest_blocks[slot].as<agpu_bgzf_block>(), n_blocks, ctx->scratch("ingest.crc_tables").as<Crc32Tables>(), ctx->scratch("ingest.crc_mismatches").as<unsigned int>());
-			else bgzf_crc_kernel<false><<<(n_blocks + 3) / 4, 256, 0, pieces>>>(ctx->ingest_raw[slot].as<uint8_t>(), ctx->ingest_blocks[slot].as<agpu_bgzf_block>(), n_blocks, ctx->scratch("ingest.crc_tables").as<Crc32Tables>(), ctx->scratch("ingest.crc_mismatches").as<unsigned int>());
-		}
+		TRY(launch_bgzf_piece(ctx, pieces, deflated, piece));
 		HIP_CHECK(hipEventRecord(ctx->piece_done[slot], pieces));
 	} else { HIP_CHECK(hipEventRecord(ctx->piece_copied[slot], s)); HIP_CHECK(hipEventRecord(ctx->piece_ready[slot], s)); }
 	TRY(wait_for_previous_push(ctx));
 	++ctx->ingest_pushes;
 	return windows_after_push(ctx);
+}
+
+int agpu_bgzf_unpack(agpu_ctx* ctx, const void* raw, size_t raw_size, const agpu_bgzf_block* blocks, uint32_t n_blocks, int way, void* out, size_t out_capacity, int32_t* block_status, uint32_t* handed_back, uint32_t* crc_mismatches) {
+	if (!ctx || !raw || !blocks || !out || !block_status || !handed_back || !crc_mismatches) { set_last_error("null argument"); return AGPU_ERR_INVALID; }
+	if (ctx->ingest_active) { set_last_error("agpu_bgzf_unpack: an ingest is under way on this context"); return AGPU_ERR_INVALID; }
+	if (way != 0 && way != 16 && way != 24 && way != -1) { set_last_error("agpu_bgzf_unpack: way is 0, 16, 24 or -1"); return AGPU_ERR_INVALID; }
+	*handed_back = 0; *crc_mismatches = 0;
+	if (n_blocks == 0) return AGPU_OK;
+	bool deflated = false;
+	for (uint32_t b = 0; b < n_blocks; ++b) deflated = deflated || blocks[b].isize != 0;
+	// nothing a kernel reads or writes may lie outside the caller's buffers (the feeder of the product makes its tables itself: arriba_amd/csrc/host/ingest.cpp)
+	for (uint32_t b = 0; b < n_blocks; ++b) {
+		const agpu_bgzf_block& block = blocks[b];
+		const bool partial = deflated && (block.skip != 0 || block.keep != block.isize);
+		const uint64_t written = !deflated ? block.payload_size : partial && block.crc32 == 0 ? block.keep : block.isize; // (a block with a CRC-32 is read there in full)
+		bool fits = block.raw_offset <= raw_size && (uint64_t) block.payload_offset + block.payload_size <= raw_size - block.raw_offset && block.stream_offset <= out_capacity && written + 64 <= out_capacity - block.stream_offset;
+		if (deflated) fits = fits && block.isize <= 65536 && (uint64_t) block.skip + block.keep <= block.isize && (!partial || b == 0 || b == n_blocks - 1); // (the spill buffer has a half for the first and one for the last block)
+		if (!fits) { set_last_error("agpu_bgzf_unpack: block " + std::to_string(b) + " does not fit the buffers"); return AGPU_ERR_INVALID; }
+	}
+	HIP_CHECK(hipSetDevice(ctx->device));
+	hipStream_t s = ctx->stream;
+	DeviceBuffer& device_raw = ctx->scratch("bgzf.tool_raw"); DeviceBuffer& device_blocks = ctx->scratch("bgzf.tool_blocks"); DeviceBuffer& device_out = ctx->scratch("bgzf.tool_out"); DeviceBuffer& counters = ctx->scratch("bgzf.tool_counters");
+	DeviceBuffer& notes = ctx->scratch("bgzf.tool_notes"); DeviceBuffer& note_count = ctx->scratch("bgzf.tool_note_count"); DeviceBuffer& status = ctx->scratch("bgzf.tool_status"); DeviceBuffer& verdict = ctx->scratch("bgzf.tool_verdict");
+	ALLOC(device_raw, raw_size + 256); ALLOC(device_blocks, (size_t) n_blocks * sizeof(agpu_bgzf_block)); ALLOC(device_out, out_capacity); ALLOC(counters, 8); // (+ 256: as agpu_ingest_push_bgzf)
+	TRY(upload_crc_tables(ctx));
+	HIP_CHECK(hipMemsetAsync(device_raw.as<uint8_t>() + raw_size, 0, 256, s));
+	HIP_CHECK(hipMemcpyAsync(device_raw.ptr, raw, raw_size, hipMemcpyHostToDevice, s));
+	HIP_CHECK(hipMemcpyAsync(device_blocks.ptr, blocks, (size_t) n_blocks * sizeof(agpu_bgzf_block), hipMemcpyHostToDevice, s));
+	HIP_CHECK(hipMemcpyAsync(device_out.ptr, out, out_capacity, hipMemcpyHostToDevice, s));
+	HIP_CHECK(hipMemsetAsync(counters.ptr, 0, 8, s));
+	BgzfPiece piece = {};
+	piece.raw = device_raw.as<uint8_t>(); piece.blocks = device_blocks.as<agpu_bgzf_block>(); piece.n_blocks = n_blocks; piece.raw_bytes = raw_size; piece.stream_bytes = out_capacity;
+	piece.target = device_out.as<uint8_t>(); piece.counters = counters.as<unsigned int>(); piece.crc_tables = ctx->scratch("ingest.crc_tables").as<Crc32Tables>();
+	if (deflated) {
+		ALLOC(ctx->scratch("ingest.inflate_spill"), 2 * 65536); ALLOC(verdict, (size_t) n_blocks * 4);
+		HIP_CHECK(hipMemsetAsync(verdict.ptr, 0, (size_t) n_blocks * 4, s));
+		piece.spill = ctx->scratch("ingest.inflate_spill").as<uint8_t>(); piece.verdict = verdict.as<int>();
+		piece.lanes = way == 0 ? 20 : way;
+		if (piece.lanes != -1) {
+			ALLOC(notes, (size_t) n_blocks * INFLATE_MATCH_CAPACITY * 8); ALLOC(note_count, (size_t) n_blocks * 4); ALLOC(status, (size_t) n_blocks * 4);
+			piece.notes = notes.as<unsigned long long>(); piece.note_count = note_count.as<uint32_t>(); piece.status = status.as<int>();
+		}
+	}
+	TRY(launch_bgzf_piece(ctx, s, deflated, piece));
+	std::vector<int32_t> first(n_blocks, 0), second(n_blocks, 0);
+	uint32_t counts[2] = { 0, 0 };
+	if (deflated && piece.lanes != -1) HIP_CHECK(hipMemcpyAsync(first.data(), status.ptr, (size_t) n_blocks * 4, hipMemcpyDeviceToHost, s));
+	if (deflated) HIP_CHECK(hipMemcpyAsync(second.data(), verdict.ptr, (size_t) n_blocks * 4, hipMemcpyDeviceToHost, s));
+	HIP_CHECK(hipMemcpyAsync(counts, counters.ptr, 8, hipMemcpyDeviceToHost, s));
+	HIP_CHECK(hipMemcpyAsync(out, device_out.ptr, out_capacity, hipMemcpyDeviceToHost, s));
+	HIP_CHECK(hipStreamSynchronize(s));
+	uint32_t refused = 0;
+	for (uint32_t b = 0; b < n_blocks; ++b) { // what pass 1 said of a block, or -- handed back, or no pass 1 at all -- what the other decoder said
+		const bool taken_over = deflated && (piece.lanes == -1 || first[b] == INFLATE_RETRY);
+		if (taken_over && piece.lanes != -1) ++*handed_back;
+		block_status[b] = taken_over ? second[b] : first[b];
+		if (block_status[b] != INFLATE_OK) ++refused;
+	}
+	*crc_mismatches = counts[0];
+	if (refused != counts[1]) { set_last_error("agpu_bgzf_unpack: " + std::to_string(refused) + " blocks have a status, the kernels counted " + std::to_string(counts[1]) + " failures"); return AGPU_ERR_DEVICE; }
+	return AGPU_OK;
 }
 
 int agpu_ingest_finish(agpu_ctx* ctx, agpu_ingest_result* result) {

@@ -258,6 +258,17 @@ int agpu_ingest_finish(agpu_ctx* ctx, agpu_ingest_result* result);
 int agpu_ingest_sam_targets(agpu_ctx* ctx, const char* names, const uint32_t* name_offset, uint32_t n_targets);
 int agpu_ingest_push_sam(agpu_ctx* ctx, const void* text, size_t size, uint64_t first_line_number);
 int agpu_sam_transcode(agpu_ctx* ctx, const void* text, size_t size, const char* names, const uint32_t* name_offset, uint32_t n_targets, void* out, size_t capacity, uint64_t* out_bytes, uint64_t* n_records, uint64_t* bad_line);
+/*   agpu_bgzf_unpack          the container kernels of agpu_ingest_push_bgzf over a caller's blocks (for tests and tools), launched by the code the ingest launches them with.
+ *                             raw[0 .. raw_size) and the table are a piece as above, except that stream_offset is the caller's choice: offsets into out[0 .. out_capacity),
+ *                             which is copied to the device first and copied back at the end, so that what no block writes comes back as it was.  `out` must reach 64 bytes
+ *                             beyond the last byte any block may write (the padding the stream of the ingest has).  isize == 0 in ALL blocks: stored blocks; else all are
+ *                             deflated (one of isize 0 is then an empty DEFLATE stream); only the first and the last block may have skip / keep.
+ *                             way: 0 = what the ingest does (pass 1 with 20 blocks per wavefront, the blocks it hands back to the one-wavefront-per-block decoder, pass 2);
+ *                             16, 24 = other numbers of blocks per wavefront; -1 = the one-wavefront-per-block decoder for every block (ARRIBA_INFLATE=wave).
+ *                             block_status[n_blocks]: 0 or what was wrong with the DEFLATE stream (INFLATE_* of inflate_core.hpp), of the decoder that had the block last;
+ *                             *handed_back: blocks pass 1 handed back; *crc_mismatches: blocks with crc32 != 0 whose bytes give another CRC-32 (a refused block among
+ *                             them, whatever it left in `out`).  AGPU_ERR_INVALID if a block does not fit the buffers.  Not while an ingest is under way on the context. */
+int agpu_bgzf_unpack(agpu_ctx* ctx, const void* raw, size_t raw_size, const agpu_bgzf_block* blocks, uint32_t n_blocks, int way, void* out, size_t out_capacity, int32_t* block_status, uint32_t* handed_back, uint32_t* crc_mismatches);
 /* ---- the records of the last ingest in coordinate order, as a BAM file of stored BGZF blocks with its BAI index (what run_arriba.sh:47-51 gets from `samtools sort` and
  * `samtools index` behind the call of arriba; SAMv1 sections 4.1, 4.2, 5.2).  The stream and the offsets of its records stay in HBM behind agpu_ingest_finish; the sort key is
  * samtools': refID as unsigned (-1 last), pos + 1, the reverse-strand flag, ties in input order; records are moved byte for byte (arriba_amd/csrc/device/agpu_sorted_bam.hip,

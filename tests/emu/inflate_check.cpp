@@ -93,7 +93,29 @@ static std::vector<uint8_t> handmade_block(const std::vector<int>& litlen, const
 	return w.bytes;
 }
 
-int main() {
+// `inflate_check --handed-back FILE`: pass 1 stepped over a caller's blocks (tests/test_bgzf_kernels.py dumps its corpus: a count, then per block the size of the DEFLATE stream,
+// the size it inflates to -- 32 bits each -- and the stream); prints the indices of the blocks pass 1 hands back, i.e. which blocks take that way on the device
+static int list_handed_back(const char* path) {
+	FILE* in = fopen(path, "rb");
+	if (!in) { printf("cannot open %s\n", path); return 1; }
+	uint32_t n = 0;
+	if (fread(&n, 4, 1, in) != 1) { printf("bad dump\n"); return 1; }
+	printf("handed back:");
+	for (uint32_t b = 0; b < n; ++b) {
+		uint32_t sizes[2];
+		if (fread(sizes, 4, 2, in) != 2 || sizes[1] > 65536) { printf("\nbad dump\n"); return 1; }
+		std::vector<uint8_t> packed(sizes[0] + PAD, 0xAA), out(sizes[1] + 64, 0xCD);
+		if (sizes[0] != 0 && fread(packed.data(), 1, sizes[0], in) != sizes[0]) { printf("\nbad dump\n"); return 1; }
+		uint32_t noted = 0;
+		if (inflate_tokens(packed.data(), sizes[0], out.data(), sizes[1], g_notes.data(), INFLATE_MATCH_CAPACITY, noted, *g_tables) == INFLATE_RETRY) printf(" %u", b);
+	}
+	printf("\n");
+	fclose(in);
+	return 0;
+}
+
+int main(int argc, char** argv) {
+	if (argc == 3 && strcmp(argv[1], "--handed-back") == 0) return list_handed_back(argv[2]);
 	std::mt19937 rng(7);
 	InflateShared* shared = new InflateShared();
 	int checked = 0, failures = 0;
