@@ -128,6 +128,21 @@ class VirusContigs(ctypes.Structure):
     _fields_ = [("n_ref", c_uint32), ("n_viruses", c_uint32), ("viral_ref", c_void_p), ("viral_length", c_void_p), ("names", c_void_p), ("name_offset", c_void_p)]
 
 
+class DepthInfo(ctypes.Structure):
+    """agpu_depth_info"""
+    _fields_ = [("positions", c_uint64), ("window_bytes", c_uint64)]
+
+
+class DepthStats(ctypes.Structure):
+    """agpu_depth_stats: what agpu_depth_end / ahost_depth_track count"""
+    _fields_ = [(name, c_uint64) for name in ("records", "segments", "runs", "covered_positions", "aligned_bases", "max_depth", "text_bytes", "position_windows", "text_windows", "peak_bytes")] + [("seconds", ctypes.c_double * 4)]
+
+
+class DepthContigs(ctypes.Structure):
+    """ahost_depth_contigs: the contigs of a header"""
+    _fields_ = [("n_ref", c_uint32), ("length", c_void_p), ("names", c_void_p), ("name_offset", c_void_p)]
+
+
 class BamPiece(ctypes.Structure):
     """ahost_bam_piece: stored_bgzf is the KIND of the piece -- 0 stream bytes, 1 stored BGZF, 2 deflated BGZF, 3 lines of SAM text (first_line: the number of its first line)"""
     _fields_ = [("stored_bgzf", c_int), ("bytes", c_size_t), ("stream_bytes", c_size_t), ("n_blocks", c_uint32), ("first_line", c_uint64)]
@@ -281,6 +296,10 @@ def bind_device_api(lib, prefix="agpu_"):
         "support_allocated_bytes": (c_int, [ctx, POINTER(c_uint64)]),
         "virus_expression": (c_int, [ctx, c_void_p, c_void_p, c_uint32, c_uint32, POINTER(VirusCounters)]),
         "virus_allocated_bytes": (c_int, [ctx, POINTER(c_uint64)]),
+        "depth_begin": (c_int, [ctx, c_void_p, c_void_p, c_void_p, c_uint32, POINTER(DepthInfo)]),
+        "depth_next": (c_int, [ctx, c_void_p, c_uint64, POINTER(c_uint64)]),
+        "depth_end": (c_int, [ctx, POINTER(DepthStats)]),
+        "depth_allocated_bytes": (c_int, [ctx, POINTER(c_uint64)]),
         "shard_export_size": (c_int, [ctx, POINTER(c_uint64)]),
         "shard_export": (c_int, [ctx, c_void_p, c_uint64]),
         "shard_merge": (c_int, [ctx, c_void_p, c_uint64, c_uint32, POINTER(IngestResult)]),
@@ -378,6 +397,12 @@ def bind_host_api(lib):
         "ahost_virus_expression_table": (c_int, [POINTER(VirusCounters), POINTER(VirusContigs), POINTER(c_void_p), POINTER(c_uint64)]),
         "ahost_virus_expression_write": (c_int, [POINTER(VirusCounters), POINTER(VirusContigs), c_char_p]),
         "ahost_virus_expression_file": (c_int, [session, c_char_p, c_char_p]),
+        "ahost_depth_contigs_of_session": (c_int, [session, POINTER(DepthContigs)]),
+        "ahost_depth_contigs_of": (c_int, [c_void_p, c_size_t, POINTER(DepthContigs)]),
+        "ahost_depth_track": (c_int, [c_void_p, c_size_t, POINTER(DepthContigs), POINTER(c_void_p), POINTER(c_uint64), POINTER(DepthStats)]),
+        "ahost_depth_line": (c_int, [c_char_p, c_uint32, c_uint32, c_uint32, c_void_p, c_uint32, POINTER(c_uint32)]),
+        "ahost_depth_write": (c_int, [c_void_p, c_uint64, c_char_p]),
+        "ahost_depth_file": (c_int, [c_char_p, c_char_p, POINTER(DepthStats)]),
         "ahost_set_batch_rows": (c_int, [session, POINTER(BatchRows), c_void_p]),
         "ahost_fusion_table_reads": (c_int, [POINTER(FusionTable), c_int, c_void_p, c_uint64, POINTER(c_uint64)]),
         "ahost_read_length_sum_of": (c_float, [c_float, c_void_p, c_void_p, c_uint64]),
@@ -400,7 +425,7 @@ class WorkflowOptions(ctypes.Structure):
                                               "protein_domains_file", "genomic_breakpoints_file", "interesting_contigs", "viral_contigs", "gtf_features")] + [
         ("device", Params), ("min_itd_support", c_uint32), ("min_itd_allele_fraction", c_float), ("high_expression_quantile", c_float), ("min_spliced_events", c_uint32), ("min_anchor_length", c_uint32),
         ("max_homolog_identity", c_float), ("top_viral_contigs", c_uint32), ("viral_contig_min_covered_fraction", c_float), ("max_genomic_breakpoint_distance", c_int32),
-        ("print_extra_info_for_discarded_fusions", c_uint8), ("fill_sequence_gaps", c_uint8), ("device_index", c_int), ("log_to_stdout", c_uint8), ("host_ingest", c_uint8), ("sorted_bam_file", c_char_p), ("supporting_alignments_prefix", c_char_p), ("supporting_alignments_window", ctypes.c_int64), ("sorted_bam_compression", c_int), ("virus_expression_file", c_char_p)]
+        ("print_extra_info_for_discarded_fusions", c_uint8), ("fill_sequence_gaps", c_uint8), ("device_index", c_int), ("log_to_stdout", c_uint8), ("host_ingest", c_uint8), ("sorted_bam_file", c_char_p), ("supporting_alignments_prefix", c_char_p), ("supporting_alignments_window", ctypes.c_int64), ("sorted_bam_compression", c_int), ("virus_expression_file", c_char_p), ("coverage_file", c_char_p)]
 
 
 class WorkflowStage(ctypes.Structure):
@@ -412,7 +437,7 @@ class WorkflowReport(ctypes.Structure):
 
 
 class WorkflowTiming(ctypes.Structure):
-    _fields_ = [(name, ctypes.c_double) for name in ("total", "feed", "ingest", "adopt", "stages", "filter_mismappers", "output", "output_results", "output_rows", "output_format", "feed_read", "feed_push", "feed_total", "exchange_parts", "exchange_verdicts", "exchange_rows", "shard_fragments", "exchanged_bytes", "sorted_bam", "supporting_alignments", "virus_expression")]
+    _fields_ = [(name, ctypes.c_double) for name in ("total", "feed", "ingest", "adopt", "stages", "filter_mismappers", "output", "output_results", "output_rows", "output_format", "feed_read", "feed_push", "feed_total", "exchange_parts", "exchange_verdicts", "exchange_rows", "shard_fragments", "exchanged_bytes", "sorted_bam", "supporting_alignments", "virus_expression", "coverage")]
 
 
 WORKFLOW_MAX, WORKFLOW_MIN, WORKFLOW_SUM = 0, 1, 2
@@ -446,6 +471,7 @@ def workflow_library():
         lib.arriba_workflow_sorted_bam.argtypes = [c_void_p, c_char_p]; lib.arriba_workflow_sorted_bam.restype = c_int
         lib.arriba_workflow_supporting_alignments.argtypes = [c_void_p, c_char_p]; lib.arriba_workflow_supporting_alignments.restype = c_int
         lib.arriba_workflow_virus_expression.argtypes = [c_void_p, c_char_p]; lib.arriba_workflow_virus_expression.restype = c_int
+        lib.arriba_workflow_coverage.argtypes = [c_void_p, c_char_p]; lib.arriba_workflow_coverage.restype = c_int
         lib.arriba_workflow_sorted_bam_compression.argtypes = [c_void_p, c_int]; lib.arriba_workflow_sorted_bam_compression.restype = c_int
         lib.arriba_workflow_cancel.argtypes = [c_void_p]; lib.arriba_workflow_cancel.restype = c_int
         lib.arriba_workflow_defer_output.argtypes = [c_void_p, c_int]; lib.arriba_workflow_defer_output.restype = c_int

@@ -126,6 +126,22 @@ struct VirusState {
 	bool active = false;
 	std::vector<uint64_t> reads, covered, kmer_count, shared; std::vector<uint32_t> active_slots;
 };
+// --coverage (agpu_depth.hip): the "depth.*" buffers are the context's own and live from agpu_depth_begin to agpu_depth_end
+struct DepthState {
+	std::map<std::string, DeviceBuffer> buffers;
+	DeviceBuffer& buffer(const char* name) { return buffers[name]; }
+	void release_all() { for (std::map<std::string, DeviceBuffer>::iterator b = buffers.begin(); b != buffers.end(); ++b) b->second.release(); }
+	uint64_t allocated() const { uint64_t sum = 0; for (std::map<std::string, DeviceBuffer>::const_iterator b = buffers.begin(); b != buffers.end(); ++b) sum += b->second.capacity; return sum; }
+	bool active = false;
+	uint32_t n_ref = 0;
+	uint64_t slots = 0, window = 0, text_window = 0; // slots of the array of depths; positions per window of runs; bytes per window of text
+	uint64_t next_slot = 0;                           // where the next window of positions begins
+	bool carry = false;                               // a run is open at next_slot (its first slot is in "depth.carry")
+	uint64_t batch_begin = 0, batch_end = 0, batch_runs = 0; // the text of the runs found last: bytes [batch_begin, batch_end) of the file
+	uint64_t written = 0, flushed = 0;                // bytes of the file that are in the staging window or were fetched; bytes fetched
+	agpu_depth_stats stats = {};
+	hipEvent_t events[2] = { nullptr, nullptr };
+};
 }
 struct agpu_ctx {
 	explicit agpu_ctx(std::shared_ptr<agpu::ScratchPool> shared = std::shared_ptr<agpu::ScratchPool>()) : pool(shared ? shared : std::make_shared<agpu::ScratchPool>()),
@@ -214,6 +230,7 @@ struct agpu_ctx {
 	uint64_t sorted_bam_compressed_bytes = 0;            // of the windows fetched so far
 	agpu::SupportState support; // --supporting-alignments (agpu_supporting.hip)
 	agpu::VirusState virus;     // --virus-expression (agpu_virus.hip)
+	agpu::DepthState depth;     // --coverage (agpu_depth.hip)
 	// A pushed piece: copied on the context's stream (piece_copied: the caller's buffer is free), unwrapped and CRC-checked on a stream of its own (piece_stream; piece_ready: its
 	// bytes are in the stream, piece_done: the raw bytes are not needed any more), so that the copy of the next piece never waits for a kernel; AGPU_PIECE_SLOTS raw buffers in turn
 	hipStream_t piece_stream = nullptr, piece_stream2 = nullptr /* deflated pieces take the two in turn */; hipEvent_t piece_copied[AGPU_PIECE_SLOTS] = {}, piece_ready[AGPU_PIECE_SLOTS] = {}, piece_done[AGPU_PIECE_SLOTS] = {};

@@ -280,6 +280,13 @@ void virus_contigs_of(const uint8_t* input, size_t size, const std::string& vira
 void virus_expression(const uint8_t* records, uint64_t size, const int32_t* viral_ref, const uint32_t* viral_length, uint32_t n_viruses, uint32_t n_ref, VirusCounters& counters);
 std::string virus_expression_table(const agpu_virus_counters& counters, const ahost_virus_contigs& contigs);
 void virus_expression_write(const std::string& text, const std::string& path); // through path + ".tmp"; on a failure nothing is left behind
+void header_contigs(const uint8_t* input, size_t size, std::vector<std::string>& names, std::vector<uint32_t>& lengths); // the references of a BAM header, or of the '@' lines of SAM text, in their order
+// --coverage on the host (depth.cpp): the contigs of a header, arriba_amd/csrc/device/depth_core.hpp stepped over records in host memory -- the comparator of agpu_depth.hip, and
+// what --host-ingest and the CPU tier run --: the bedGraph text and the statistics of the device
+struct DepthContigs { std::vector<uint32_t> length; std::string names; std::vector<uint32_t> name_offset; ahost_depth_contigs view() const; };
+void depth_contigs_of(const uint8_t* input, size_t size, DepthContigs& contigs);
+void depth_track(const uint8_t* records, uint64_t size, const ahost_depth_contigs& contigs, std::string& text, agpu_depth_stats& stats);
+std::string depth_line_text(const std::string& name, uint32_t start, uint32_t end, uint32_t depth);
 const std::vector<uint8_t>& bam_feed_header_bytes(BamFeed* feed); // the head of the uncompressed input as the feed read it: the BAM header, or the '@' lines of SAM text
 
 // reference: source/read_chimeric_alignments.cpp:560-773 with separate_chimeric_bam_file=false, is_rna_bam_file=true

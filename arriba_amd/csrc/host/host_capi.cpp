@@ -804,6 +804,53 @@ int ahost_virus_expression_file(ahost_session* session, const char* input_path, 
 	} catch (const std::exception& e) { g_error = e.what(); return -1; }
 }
 
+// ---- --coverage (include/arriba_host.h) ----
+namespace {
+thread_local DepthContigs g_depth_contigs; thread_local std::string g_depth_text;
+}
+int ahost_depth_contigs_of_session(ahost_session* session, ahost_depth_contigs* contigs) {
+	if (!session || !contigs) { g_error = "null argument"; return -1; }
+	if (session->input_header.empty()) { g_error = "ahost_bam_open must run first"; return -1; }
+	try { depth_contigs_of(session->input_header.data(), session->input_header.size(), g_depth_contigs); *contigs = g_depth_contigs.view(); return 0; }
+	catch (const std::exception& e) { g_error = e.what(); return -1; }
+}
+int ahost_depth_contigs_of(const void* input_header, size_t size, ahost_depth_contigs* contigs) {
+	if (!input_header || !contigs) { g_error = "null argument"; return -1; }
+	try { depth_contigs_of((const uint8_t*) input_header, size, g_depth_contigs); *contigs = g_depth_contigs.view(); return 0; }
+	catch (const std::exception& e) { g_error = e.what(); return -1; }
+}
+int ahost_depth_track(const void* records, size_t size, const ahost_depth_contigs* contigs, const char** text, uint64_t* bytes, agpu_depth_stats* stats) {
+	if ((!records && size > 0) || !contigs || !text || !bytes || !stats) { g_error = "null argument"; return -1; }
+	try { depth_track((const uint8_t*) records, size, *contigs, g_depth_text, *stats); *text = g_depth_text.data(); *bytes = g_depth_text.size(); return 0; }
+	catch (const std::exception& e) { g_error = e.what(); return -1; }
+}
+int ahost_depth_line(const char* name, uint32_t start, uint32_t end, uint32_t depth, char* out, uint32_t capacity, uint32_t* bytes) {
+	if (!name || !out || !bytes) { g_error = "null argument"; return -1; }
+	const std::string line = depth_line_text(name, start, end, depth);
+	*bytes = (uint32_t) line.size();
+	if (line.size() > capacity) { g_error = "ahost_depth_line: the line does not fit the buffer"; return -1; }
+	memcpy(out, line.data(), line.size());
+	return 0;
+}
+int ahost_depth_write(const void* text, uint64_t bytes, const char* path) {
+	if ((!text && bytes > 0) || !path) { g_error = "null argument"; return -1; }
+	try { virus_expression_write(std::string((const char*) text, bytes), path); return 0; } // (the writer of a text through path.tmp)
+	catch (const std::exception& e) { g_error = e.what(); return -1; }
+}
+int ahost_depth_file(const char* input_path, const char* path, agpu_depth_stats* stats) {
+	if (!input_path || !path) { g_error = "null argument"; return -1; }
+	try {
+		std::vector<uint8_t> stream;
+		const uint64_t at = read_whole_bam(input_path, stream); // (SAM text comes out as the BAM stream of its alignments, behind a BAM header)
+		DepthContigs contigs; std::string text; agpu_depth_stats counted;
+		depth_contigs_of(stream.data(), at, contigs);
+		depth_track(stream.data() + at, stream.size() - at, contigs.view(), text, counted);
+		virus_expression_write(text, path);
+		if (stats) *stats = counted;
+		return 0;
+	} catch (const std::exception& e) { g_error = e.what(); return -1; }
+}
+
 void ahost_bam_close(ahost_session* session) { if (session && session->feed) { close_bam_feed(session->feed); session->feed = nullptr; } }
 
 int ahost_adopt_device_ingest(ahost_session* session, const agpu_ingest_result* result, const uint64_t* viral_read_counts, const uint16_t* coverage, const uint8_t* fragment_starts, const uint8_t* fragment_ends) {

@@ -40,9 +40,9 @@ agpu_virus_counters VirusCounters::view() const {
 	return v;
 }
 
-// the references of the header in their order -- a virus's index is its position in this list --, and those of them that -v names
-void virus_contigs_of(const uint8_t* input, size_t size, const std::string& viral_contigs, VirusContigs& contigs) {
-	std::vector<std::string> names; std::vector<uint32_t> lengths;
+// the references of a header (a BAM header, or the '@' lines of SAM text) in their order
+void header_contigs(const uint8_t* input, size_t size, std::vector<std::string>& names, std::vector<uint32_t>& lengths) {
+	names.clear(); lengths.clear();
 	if (size >= 4 && memcmp(input, "BAM\1", 4) == 0) {
 		if (size < 12) throw std::runtime_error("failed to read SAM header");
 		const uint64_t l_text = get32(input + 4);
@@ -78,6 +78,12 @@ void virus_contigs_of(const uint8_t* input, size_t size, const std::string& vira
 			at = next;
 		}
 	}
+}
+
+// a virus's index is its position in the list of the header; those of the references that -v names
+void virus_contigs_of(const uint8_t* input, size_t size, const std::string& viral_contigs, VirusContigs& contigs) {
+	std::vector<std::string> names; std::vector<uint32_t> lengths;
+	header_contigs(input, size, names, lengths);
 	contigs = VirusContigs();
 	contigs.n_ref = (uint32_t) names.size();
 	contigs.name_offset.push_back(0);

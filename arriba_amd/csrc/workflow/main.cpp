@@ -68,7 +68,8 @@ void usage() {
 	             " --sorted-bam-compression N  0: stored blocks (the default); 1: the record blocks of --sorted-bam deflated on the GPU (as samtools sort compresses its output)\n"
 	             " --supporting-alignments PREFIX  PREFIX_ID.bam and .bam.bai per row of -o: the alignments of its read_identifiers near its breakpoints (extract_fusion-supporting_alignments.sh)\n"
 	             " --supporting-window INT  how far from a breakpoint they may lie (1000000)\n"
-	             " --virus-expression FILE  per viral contig (-v) genome size, covered bases, high-quality alignments and RPKM, related strains collapsed (quantify_virus_expression.sh)\n";
+	             " --virus-expression FILE  per viral contig (-v) genome size, covered bases, high-quality alignments and RPKM, related strains collapsed (quantify_virus_expression.sh)\n"
+	             " --coverage FILE  the per-base alignment depth of -x as bedGraph text: a line per run of equal depth > 0, contigs in header order\n";
 }
 
 }
@@ -99,6 +100,7 @@ int main(int argc, char** argv) {
 		else if (strcmp(argv[a], "--sorted-bam-compression") == 0 && a + 1 < argc) { long level; require(parse_int(argv[++a], level) && (level == 0 || level == 1), "invalid argument to --sorted-bam-compression: 0 (stored) or 1"); options.sorted_bam_compression = (int) level; compression_given = true; }
 		else if (strcmp(argv[a], "--supporting-alignments") == 0 && a + 1 < argc) { options.supporting_alignments_prefix = argv[++a]; parent_exists(options.supporting_alignments_prefix); }
 		else if (strcmp(argv[a], "--virus-expression") == 0 && a + 1 < argc) { options.virus_expression_file = argv[++a]; parent_exists(options.virus_expression_file); }
+		else if (strcmp(argv[a], "--coverage") == 0 && a + 1 < argc) { options.coverage_file = argv[++a]; parent_exists(options.coverage_file); }
 		else if (strcmp(argv[a], "--supporting-window") == 0 && a + 1 < argc) { long window; require(parse_int(argv[++a], window) && window > 0 && window <= 0x7FFFFFFFl, "invalid argument to --supporting-window"); options.supporting_alignments_window = window; }
 		else if (strcmp(argv[a], "--device") == 0 && a + 1 < argc) { long device; require(parse_int(argv[++a], device) && device >= 0, "invalid argument to --device"); options.device_index = (int) device; }
 		else arguments.push_back(argv[a]);

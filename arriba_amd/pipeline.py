@@ -35,6 +35,13 @@ def virus_contigs_of(contigs):
             "names": [text[offsets[k]:offsets[k + 1]].decode() for k in range(n)]}
 
 
+def depth_stats_of(stats):
+    """agpu_depth_stats (the device's or the host's) as a dict"""
+    out = {name: int(getattr(stats, name)) for name in ("records", "segments", "runs", "covered_positions", "aligned_bases", "max_depth", "text_bytes", "position_windows", "text_windows", "peak_bytes")}
+    out["seconds"] = dict(zip(("marks", "scan", "runs", "text"), stats.seconds))
+    return out
+
+
 class ArribaError(RuntimeError):
     pass
 
@@ -181,7 +188,7 @@ class WorkflowSession(object):
         if self._lib.arriba_workflow_sorted_bam_compression(self._session, int(level)) != 0:
             raise ArribaError(self._lib.arriba_workflow_last_error().decode())
 
-    def submit(self, bam, sorted_bam_file=None, supporting_alignments_prefix=None, sorted_bam_compression=None, virus_expression_file=None):
+    def submit(self, bam, sorted_bam_file=None, supporting_alignments_prefix=None, sorted_bam_compression=None, virus_expression_file=None, coverage_file=None):
         """the sample that comes after the one `sample` is called for next: its file is fed (PCIe, the front of read_chimeric_alignments) while the stages of that one run;
         sorted_bam_file: its records in coordinate order with their index (--sorted-bam), written when its ingest is finished; sorted_bam_compression: its level (None: as it is)"""
         if sorted_bam_compression is not None:
@@ -189,6 +196,7 @@ class WorkflowSession(object):
         self._lib.arriba_workflow_sorted_bam(self._session, sorted_bam_file.encode() if sorted_bam_file else None)
         self._lib.arriba_workflow_supporting_alignments(self._session, supporting_alignments_prefix.encode() if supporting_alignments_prefix else None)  # (--supporting-alignments: PREFIX_ID.bam per row of its fusions file)
         self._lib.arriba_workflow_virus_expression(self._session, virus_expression_file.encode() if virus_expression_file else None)  # (--virus-expression: its table, written when its ingest is finished)
+        self._lib.arriba_workflow_coverage(self._session, coverage_file.encode() if coverage_file else None)  # (--coverage: its depth track, written when its ingest is finished)
         if self._lib.arriba_workflow_submit(self._session, bam.encode()) != 0:
             raise ArribaError(self._lib.arriba_workflow_last_error().decode())
         if self._profiling_on:
@@ -283,7 +291,7 @@ class WorkflowSession(object):
     def _lane_contexts(self):
         return [ctx for ctx in (self._lib.arriba_workflow_lane_device(self._session, lane) for lane in (0, 1)) if ctx]
 
-    def sample(self, bam, output_file, discarded_output_file=None, sorted_bam_file=None, supporting_alignments_prefix=None, sorted_bam_compression=None, virus_expression_file=None):
+    def sample(self, bam, output_file, discarded_output_file=None, sorted_bam_file=None, supporting_alignments_prefix=None, sorted_bam_compression=None, virus_expression_file=None, coverage_file=None):
         """one sample, BAM file -> fusions.tsv (and discarded.tsv); returns the stages with their "(remaining=N)" counts.  sorted_bam_file (--sorted-bam): for a sample that was
         not submitted ahead; one that was says it to `submit`"""
         report, timing = _capi.WorkflowReport(), _capi.WorkflowTiming()
@@ -295,6 +303,8 @@ class WorkflowSession(object):
             self._lib.arriba_workflow_supporting_alignments(self._session, supporting_alignments_prefix.encode())
         if virus_expression_file:  # (likewise)
             self._lib.arriba_workflow_virus_expression(self._session, virus_expression_file.encode())
+        if coverage_file:  # (likewise)
+            self._lib.arriba_workflow_coverage(self._session, coverage_file.encode())
         if self._lib.arriba_workflow_sample(self._session, bam.encode(), output_file.encode(), discarded_output_file.encode() if discarded_output_file else None, byref(report), byref(timing)) != 0:
             raise ArribaError(self._lib.arriba_workflow_last_error().decode())
         self.ctx = self._lib.arriba_workflow_device(self._session)  # (the lane that worked on this sample)
@@ -400,6 +410,7 @@ class DevicePipeline(object):
         if self.ctx:
             self._free_pieces()
             self._free_sorted_windows()
+            self._free_depth_windows()
             self.api.destroy(self.ctx)
             self.ctx = None
 
@@ -620,6 +631,58 @@ class DevicePipeline(object):
         if lib.ahost_virus_expression_write(byref(self._virus[0]), byref(self._virus[1]), path.encode()) != 0:
             raise ArribaError("ERROR: " + lib.ahost_last_error().decode())
         return counters
+
+    def write_coverage(self, path):
+        """--coverage: the per-base alignment depth of the records of the last read_chimeric_alignments as bedGraph text -- NAME START END DEPTH per run of equal depth > 0,
+        contigs in header order --, computed and formatted on the device from the record stream that is still in HBM (agpu_depth_*).  Valid after
+        read_chimeric_alignments and before the next one.  Written through `path`.tmp; returns the statistics {"records", "segments", "runs", "covered_positions", "aligned_bases",
+        "max_depth", "text_bytes", "position_windows", "text_windows", "peak_bytes", "seconds"}."""
+        import os
+        if not self.device_ingest or not hasattr(self.api, "depth_begin"):
+            raise ArribaError("ERROR: a coverage track needs the record stream of an ingest on the device (DevicePipeline(bam=...))")
+        lib, handle = self.session._lib, self.session._session
+        contigs = _capi.DepthContigs()
+        if lib.ahost_depth_contigs_of_session(handle, byref(contigs)) != 0:
+            raise ArribaError("ERROR: " + lib.ahost_last_error().decode())
+        info, stats = _capi.DepthInfo(), _capi.DepthStats()
+        self._check(self.api.depth_begin(self.ctx, contigs.length, contigs.names, contigs.name_offset, contigs.n_ref, byref(info)))  # (refused before anything is written)
+        try:
+            if getattr(self, "_depth_windows", None) is None or self._depth_windows[0] < info.window_bytes:  # two pinned buffers in turn: they stay with the pipeline
+                self._free_depth_windows()
+                buffers = [self.api.host_alloc(info.window_bytes) for _ in range(2)]
+                self._depth_windows = (info.window_bytes, buffers)
+                if not all(buffers):
+                    self._free_depth_windows()
+                    raise ArribaError("ERROR: " + self.api.last_error().decode())
+            capacity, buffers = self._depth_windows
+            with open(path + ".tmp", "wb") as out:
+                got, turn = c_uint64(), 0
+                while True:
+                    self._check(self.api.depth_next(self.ctx, buffers[turn & 1], capacity, byref(got)))
+                    if got.value == 0:
+                        break
+                    out.write((ctypes.c_char * got.value).from_address(buffers[turn & 1]))
+                    turn += 1
+            self._check(self.api.depth_end(self.ctx, byref(stats)))
+            os.rename(path + ".tmp", path)
+        except BaseException:
+            self.api.depth_end(self.ctx, None)
+            if os.path.exists(path + ".tmp"):
+                os.remove(path + ".tmp")
+            raise
+        return depth_stats_of(stats)
+
+    def _free_depth_windows(self):
+        if getattr(self, "_depth_windows", None) is not None:
+            for buffer in self._depth_windows[1]:
+                if buffer:
+                    self.api.host_free(buffer)
+            self._depth_windows = None
+
+    def depth_allocated_bytes(self):
+        count = c_uint64()
+        self._check(self.api.depth_allocated_bytes(self.ctx, byref(count)))
+        return int(count.value)
 
     def virus_allocated_bytes(self):
         count = c_uint64()
@@ -879,7 +942,7 @@ class DevicePipeline(object):
                      max_genomic_breakpoint_distance=100000, strandedness=None, evalue_cutoff=0.3,
                      min_itd_support=10, min_itd_allele_fraction=0.07, high_expression_quantile=0.998, min_spliced_events=4, min_anchor_length=23,
                      max_homolog_identity=0.3, max_itd_length=100, fill_sequence_gaps=False, top_viral_contigs=5, viral_contig_min_covered_fraction=0.05,
-                     print_extra_info_for_discarded_fusions=False, log=None, sorted_bam_file=None, supporting_alignments_prefix=None, supporting_alignments_window=1000000, virus_expression_file=None):
+                     print_extra_info_for_discarded_fusions=False, log=None, sorted_bam_file=None, supporting_alignments_prefix=None, supporting_alignments_window=1000000, virus_expression_file=None, coverage_file=None):
         """The reference's main() behind read_chimeric_alignments (source/arriba.cpp:119-610) with its default parameters: the read-level cascade, find_fusions,
         every candidate-level filter in the reference's order, assign_confidence, and the two output files.  `log` receives (stage, remaining) pairs --
         the numbers the reference prints as "(remaining=N)".  Filters switched off with -f are skipped by the stages themselves (agpu_params.filter_enabled)."""
@@ -888,6 +951,8 @@ class DevicePipeline(object):
             self.write_sorted_bam(sorted_bam_file)
         if virus_expression_file:  # (--virus-expression: likewise from the stream)
             self.write_virus_expression(virus_expression_file)
+        if coverage_file:  # (--coverage: likewise)
+            self.write_coverage(coverage_file)
         if supporting_alignments_prefix:  # (--supporting-alignments, phase 1: the records of the names of the batch leave the stream while it is there)
             self.build_support_pool()
         self.run_read_level(strandedness, top_viral_contigs, viral_contig_min_covered_fraction)

@@ -407,6 +407,38 @@ typedef struct {
 } agpu_virus_counters;
 int agpu_virus_expression(agpu_ctx* ctx, const int32_t* viral_ref, const uint32_t* viral_length, uint32_t n_viruses, uint32_t n_ref, agpu_virus_counters* counters);
 int agpu_virus_allocated_bytes(agpu_ctx* ctx, uint64_t* bytes); /* of the "virus.*" buffers of the context: 0 outside agpu_virus_expression */
+/* --coverage: the per-base alignment depth of the records of the last ingest as bedGraph text -- NAME\tSTART\tEND\tDEPTH\n per maximal run of equal depth > 0, contigs in header
+ * order -- computed and formatted on the device while the stream is in HBM (arriba_amd/csrc/device/agpu_depth.hip, depth_core.hpp; the rule: DESIGN.md 4.13).
+ *   agpu_depth_begin   behind agpu_ingest_finish, before the next agpu_ingest_begin on this context or its sibling (the refusals of agpu_sorted_bam_begin).  ref_length: LN of
+ *                      the n_ref contigs of the header; names / name_offset [n_ref + 1]: their names, one behind the other.  Marks every record into a difference array of
+ *                      LN + 1 slots per contig and scans it.  info: what follows.
+ *   agpu_depth_next    the next window of text (info.window_bytes at most; every window but the last is full, a line may straddle two) into pinned[0 .. capacity);
+ *                      *bytes == 0 at the end.  Runs are found over windows of positions and their lines written into a staging window as the calls go on.
+ *   agpu_depth_end     stats (may be NULL): of what was fetched so far, complete behind the agpu_depth_next that returned 0 bytes.  The device buffers ("depth.*") are the
+ *                      context's own and are released here -- and by a begin that fails.  Without a begin: AGPU_OK, zeros.
+ * A buffer that does not fit: AGPU_ERR_NO_MEMORY.
+ * ARRIBA_DEPTH_WINDOW: positions whose runs are found at a time (default 2^25); ARRIBA_DEPTH_TEXT_WINDOW: bytes of a staging window (default 16 MiB).  DESIGN.md 4.13 has the
+ * bound on memory that follows from them. */
+typedef struct {
+	uint64_t positions;        /* slots of the difference array: the sum of LN + 1 over the contigs */
+	uint64_t window_bytes;     /* what a buffer of agpu_depth_next must hold */
+} agpu_depth_info;
+typedef struct {
+	uint64_t records;           /* records that count */
+	uint64_t segments;          /* maximal covered segments of theirs that lie on their contig: pairs of marks */
+	uint64_t runs;              /* lines */
+	uint64_t covered_positions; /* sum of end - start over the runs */
+	uint64_t aligned_bases;     /* sum of (end - start) * depth */
+	uint64_t max_depth;
+	uint64_t text_bytes;
+	uint64_t position_windows, text_windows; /* windows of positions whose runs were found; windows of text that were fetched (the host: 1 each, or 0) */
+	uint64_t peak_bytes;        /* of the "depth.*" buffers (0 on the host) */
+	double seconds[4];          /* marks; scan; runs (flags, scan, emission, line lengths, scan); text and copies (device: from HIP events, 0 on the host) */
+} agpu_depth_stats;
+int agpu_depth_begin(agpu_ctx* ctx, const uint32_t* ref_length, const char* names, const uint32_t* name_offset, uint32_t n_ref, agpu_depth_info* info);
+int agpu_depth_next(agpu_ctx* ctx, void* pinned, uint64_t capacity, uint64_t* bytes);
+int agpu_depth_end(agpu_ctx* ctx, agpu_depth_stats* stats);
+int agpu_depth_allocated_bytes(agpu_ctx* ctx, uint64_t* bytes); /* of the "depth.*" buffers of the context: 0 outside agpu_depth_begin ... agpu_depth_end */
 /* what the host's sequential stages and its output writer need from a batch that lives on the device:
  *   agpu_get_viral_read_counts   mapped_viral_reads_by_contig (source/read_chimeric_alignments.cpp:735-739)
  *   agpu_get_coverage            coverage_t as the reference holds it (16-bit saturating windows, start/end flags); sizes by coverage_window_offset

@@ -144,6 +144,27 @@ int ahost_virus_expression(const void* records, size_t size, const ahost_virus_c
 int ahost_virus_expression_table(const agpu_virus_counters* counters, const ahost_virus_contigs* contigs, const char** text, uint64_t* bytes);
 int ahost_virus_expression_write(const agpu_virus_counters* counters, const ahost_virus_contigs* contigs, const char* path);
 int ahost_virus_expression_file(ahost_session* session, const char* input_path, const char* path);
+/* ---- --coverage: the host side of agpu_depth_begin / _next / _end (include/arriba_gpu.h) -- the per-base alignment depth of the records as bedGraph text (the rule: DESIGN.md
+ * 4.13) ----
+ *   ahost_depth_contigs_of_session  the contigs of the header of the file the last ahost_bam_open opened: what agpu_depth_begin takes
+ *   ahost_depth_contigs_of   the same from the head of an uncompressed input in memory (a BAM header, or the '@' lines of SAM text).  Both: valid until the next call on the thread
+ *   ahost_depth_track        arriba_amd/csrc/device/depth_core.hpp stepped on the host over BAM records in host memory: the text and the statistics the device gives (its
+ *                            comparator; the CPU tier); the text is valid until the next call on the thread
+ *   ahost_depth_line         the line formatter alone: NAME\tSTART\tEND\tDEPTH\n into out[0 .. capacity); *bytes: its length (nothing is written if it does not fit: -1)
+ *   ahost_depth_write        bytes into `path`, through path.tmp; on a failure nothing is left behind
+ *   ahost_depth_file         all of it for a file (BAM in BGZF, gzip or raw; SAM text): what --host-ingest runs; stats may be NULL */
+typedef struct {
+	uint32_t n_ref;
+	const uint32_t* length;      /* [n_ref] LN */
+	const char* names;           /* the names of the contigs, one behind the other */
+	const uint32_t* name_offset; /* [n_ref + 1] */
+} ahost_depth_contigs;
+int ahost_depth_contigs_of_session(ahost_session* session, ahost_depth_contigs* contigs);
+int ahost_depth_contigs_of(const void* input_header, size_t size, ahost_depth_contigs* contigs);
+int ahost_depth_track(const void* records, size_t size, const ahost_depth_contigs* contigs, const char** text, uint64_t* bytes, agpu_depth_stats* stats);
+int ahost_depth_line(const char* name, uint32_t start, uint32_t end, uint32_t depth, char* out, uint32_t capacity, uint32_t* bytes);
+int ahost_depth_write(const void* text, uint64_t bytes, const char* path);
+int ahost_depth_file(const char* input_path, const char* path, agpu_depth_stats* stats);
 int ahost_adopt_device_ingest(ahost_session* session, const agpu_ingest_result* result, const uint64_t* viral_read_counts, const uint16_t* coverage, const uint8_t* fragment_starts, const uint8_t* fragment_ends);
 int ahost_set_batch_rows(ahost_session* session, const agpu_batch_rows* rows, const uint32_t* fragments /* [rows->n] ascending: the fragment every row holds; NULL: row k holds the fragment
                          of entry k of the read lists of the table the next ahost_write_fusions writes (the reads of a candidate next to each other; the table then carries read_filter_of_rows) */);

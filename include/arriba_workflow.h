@@ -60,6 +60,10 @@ typedef struct {
 	                                         parameters -- per viral contig (-v) genome size, covered bases, covered fraction, high-quality alignments and RPKM, related strains collapsed onto the
 	                                         most expressed one --, counted behind read_chimeric_alignments from the record stream in HBM (include/arriba_gpu.h: agpu_virus_expression; DESIGN.md
 	                                         4.11).  Of arriba_workflow_run's sample; the samples of a session say theirs with arriba_workflow_virus_expression.  Not for one sample over several ranks. */
+	const char* coverage_file;            /* --coverage; NULL (and a zero-initialised struct) = none.  The per-base alignment depth of the records of chimeric_bam_file as bedGraph text -- a line
+	                                         NAME START END DEPTH per run of equal depth > 0, contigs in header order --, computed and formatted behind read_chimeric_alignments from the record
+	                                         stream in HBM (include/arriba_gpu.h: agpu_depth_begin).  Of arriba_workflow_run's sample; the samples of a session say theirs with
+	                                         arriba_workflow_coverage.  Not for one sample over several ranks. */
 } arriba_workflow_options;
 
 /* what the reference prints as "(remaining=N)" / "(total=N)" / "(marked=N)", in the order of the stages; stage names as in the reference's source */
@@ -100,6 +104,7 @@ typedef struct { /* seconds of one sample, by part (wall clock of the calling th
 	double sorted_bam;       /* --sorted-bam: keys, sort, gather, copy back, the two files (inside `ingest`; beside the sample in front when the ingest was finished ahead) */
 	double supporting_alignments; /* --supporting-alignments: the pool behind the ingest (name table, marks, compaction) and the files behind fusions.tsv (join, gather, copy back, files, indexes) */
 	double virus_expression; /* --virus-expression: scan, candidates, k-mer sets, copies, the table (inside `ingest`; beside the sample in front when the ingest was finished ahead) */
+	double coverage;         /* --coverage: marks, scan, runs, text, copies, the file (inside `ingest`; beside the sample in front when the ingest was finished ahead) */
 } arriba_workflow_timing;
 /* options->chimeric_bam_file, output_file and discarded_output_file are not used by open (they belong to a sample); NULL + arriba_workflow_last_error() on failure */
 arriba_workflow_session* arriba_workflow_open(const arriba_workflow_options* options);
@@ -123,6 +128,8 @@ int arriba_workflow_sorted_bam_compression(arriba_workflow_session* session, int
 int arriba_workflow_supporting_alignments(arriba_workflow_session* session, const char* prefix);
 /* --virus-expression of the sample that is submitted NEXT, in the same way; NULL: none.  The table is written by the thread that finishes its ingest. */
 int arriba_workflow_virus_expression(arriba_workflow_session* session, const char* path);
+/* --coverage of the sample that is submitted NEXT, in the same way; NULL: none.  The track is written by the thread that finishes its ingest. */
+int arriba_workflow_coverage(arriba_workflow_session* session, const char* path);
 /* (If the device runs out of memory while two samples are in flight, arriba_workflow_sample throws away what was fed ahead, closes the second lane, runs its sample again with the device
  * to itself and submits the other sample again behind it -- once; a sample that does not fit the device alone fails the call.  INTEGRATION.md, "Memory".) */
 /* on: arriba_workflow_sample returns when the last output file of the sample (-O if given, else -o) has everything it needs off the device; the file is formatted and written
