@@ -142,6 +142,17 @@ struct DepthState {
 	agpu_depth_stats stats = {};
 	hipEvent_t events[2] = { nullptr, nullptr };
 };
+// --mark-duplicates (agpu_markdup.hip): the "markdup.*" buffers are the context's own; all but "markdup.flag" (one byte per record) are released before agpu_sorted_bam_begin
+// allocates "sortedbam.*", that one by agpu_sorted_bam_end
+struct MarkdupState {
+	std::map<std::string, DeviceBuffer> buffers;
+	DeviceBuffer& buffer(const char* name) { return buffers[name]; }
+	void release_all() { for (std::map<std::string, DeviceBuffer>::iterator b = buffers.begin(); b != buffers.end(); ++b) b->second.release(); }
+	void release_all_but(const char* kept) { for (std::map<std::string, DeviceBuffer>::iterator b = buffers.begin(); b != buffers.end(); ++b) if (b->first != kept) b->second.release(); }
+	uint64_t allocated() const { uint64_t sum = 0; for (std::map<std::string, DeviceBuffer>::const_iterator b = buffers.begin(); b != buffers.end(); ++b) sum += b->second.capacity; return sum; }
+	bool next = false, on = false; // agpu_sorted_bam_set_mark_duplicates: of the next agpu_sorted_bam_begin; of the begin ... end under way
+	agpu_markdup_counts counts = {};
+};
 }
 struct agpu_ctx {
 	explicit agpu_ctx(std::shared_ptr<agpu::ScratchPool> shared = std::shared_ptr<agpu::ScratchPool>()) : pool(shared ? shared : std::make_shared<agpu::ScratchPool>()),
@@ -231,6 +242,7 @@ struct agpu_ctx {
 	agpu::SupportState support; // --supporting-alignments (agpu_supporting.hip)
 	agpu::VirusState virus;     // --virus-expression (agpu_virus.hip)
 	agpu::DepthState depth;     // --coverage (agpu_depth.hip)
+	agpu::MarkdupState markdup; // --mark-duplicates (agpu_markdup.hip)
 	// A pushed piece: copied on the context's stream (piece_copied: the caller's buffer is free), unwrapped and CRC-checked on a stream of its own (piece_stream; piece_ready: its
 	// bytes are in the stream, piece_done: the raw bytes are not needed any more), so that the copy of the next piece never waits for a kernel; AGPU_PIECE_SLOTS raw buffers in turn
 	hipStream_t piece_stream = nullptr, piece_stream2 = nullptr /* deflated pieces take the two in turn */; hipEvent_t piece_copied[AGPU_PIECE_SLOTS] = {}, piece_ready[AGPU_PIECE_SLOTS] = {}, piece_done[AGPU_PIECE_SLOTS] = {};
@@ -296,6 +308,8 @@ int ingest_grow_stream(agpu_ctx* ctx, uint64_t needed);
 int ingest_piece_pushed(agpu_ctx* ctx);
 // agpu_sam.hip, for agpu_ingest_finish: AGPU_ERR_INVALID with "failed to load alignments: SAM line N: <reason>" if a line of the SAM text of this ingest was malformed
 int sam_ingest_verdict(agpu_ctx* ctx);
+// agpu_markdup.hip, for agpu_sorted_bam_begin: one byte per record of the stream of the last ingest (MDUP_FLAG_MASK or 0) into "markdup.flag", everything else of "markdup.*" released
+int markdup_find(agpu_ctx* ctx);
 // agpu_api.hip: the buffers that hold a sample (batch, gene sets, candidates, read lists, k-mer index, ...) change hands between the lanes of a session: `ctx`, about to build
 // its batch, takes what its sibling -- whose sample is done on the device -- holds wherever that is the larger buffer; the sibling's sample is gone afterwards
 void take_sample_buffers(agpu_ctx* ctx, bool batch_group = true, bool stage_group = true);

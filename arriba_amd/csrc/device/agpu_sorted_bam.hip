@@ -20,6 +20,7 @@
 #include "agpu_context.hpp"
 #include "crc32_core.hpp"
 #include "deflate_out_core.hpp"
+#include "markdup_core.hpp"
 #include "device_utils.hpp"
 #include "sorted_bam_core.hpp"
 #include "sorted_bam_device.hpp"
@@ -76,8 +77,12 @@ static_assert(sizeof(GatherShared) * 2 <= 160 * 1024, "two workgroups per CU");
 
 // The parts of the records that fall into block b (payload bytes begin .. begin + length of the output) into image[payload_at ..): one wavefront per record, the batches of
 // sources and destinations through LDS.  Shared: GatherShared, or a struct that begins like it.  No barrier behind the last copy.
+// duplicate (--mark-duplicates; may be null: the bytes of the stream as they are): one byte per record of the stream, not 0 if it leaves with bit 0x400.  The bit travels in bit 63 of
+// the record's source; behind the copy of the record one lane sets or clears MDUP_FLAG_MASK in byte MDUP_FLAG_BYTE of the record in the image, if that byte lies in this block -- a
+// byte store: the words around it may hold bytes of the neighbouring records, which other wavefronts copy.
+const uint64_t GATHER_DUPLICATE_BIT = 1ull << 63;
 template <class Shared> __device__ __forceinline__ void gather_payload(Shared& shared, const uint8_t* __restrict__ stream, const uint64_t* __restrict__ record_offset, const uint32_t* __restrict__ order,
-		const uint64_t* __restrict__ out_offset, const uint32_t* __restrict__ block_first, uint64_t n, uint64_t n_blocks, uint64_t b, uint64_t begin, uint32_t length, uint8_t* image, uint32_t payload_at, uint32_t t) {
+		const uint64_t* __restrict__ out_offset, const uint32_t* __restrict__ block_first, uint64_t n, uint64_t n_blocks, uint64_t b, uint64_t begin, uint32_t length, uint8_t* image, uint32_t payload_at, uint32_t t, const uint8_t* __restrict__ duplicate) {
 	const uint32_t lane = t % 64, wave = t / 64;
 	const uint64_t first_record = block_first[b], last_record = b + 1 < n_blocks ? block_first[b + 1] : n - 1;
 	for (uint64_t batch = first_record; batch <= last_record; batch += GATHER_BATCH) {
@@ -85,21 +90,35 @@ template <class Shared> __device__ __forceinline__ void gather_payload(Shared& s
 		__syncthreads(); // (the batch before has been copied)
 		for (uint32_t j = t; j <= count; j += GATHER_THREADS) {
 			shared.destination[j] = out_offset[batch + j]; // (batch + count <= n: out_offset has n + 1 entries)
-			if (j < count) shared.source[j] = record_offset[order[batch + j]];
+			if (j < count) {
+				const uint32_t record = order[batch + j];
+				uint64_t source = record_offset[record];
+				if (duplicate != nullptr && duplicate[record] != 0) source |= GATHER_DUPLICATE_BIT;
+				shared.source[j] = source;
+			}
 		}
 		__syncthreads();
 		for (uint32_t j = wave; j < count; j += GATHER_THREADS / 64) {
 			const uint64_t record_begin = shared.destination[j], record_end = shared.destination[j + 1];
 			const uint64_t from = record_begin > begin ? record_begin : begin, to = record_end < begin + length ? record_end : begin + length;
 			if (from >= to) continue;
-			sbam_wave_copy<uint32_t>(image, payload_at + (uint32_t) (from - begin), payload_at + (uint32_t) (to - begin), stream, shared.source[j] + (from - record_begin), lane);
+			const uint64_t source = shared.source[j];
+			sbam_wave_copy<uint32_t>(image, payload_at + (uint32_t) (from - begin), payload_at + (uint32_t) (to - begin), stream, (source & ~GATHER_DUPLICATE_BIT) + (from - record_begin), lane);
+			if (duplicate != nullptr) {
+				const uint64_t flag_byte = record_begin + MDUP_FLAG_BYTE;
+				__builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront"); // (the byte was written by a lane of this wavefront)
+				if (lane == 0 && flag_byte >= from && flag_byte < to) {
+					uint8_t* const byte = image + payload_at + (uint32_t) (flag_byte - begin);
+					*byte = (uint8_t) ((*byte & ~MDUP_FLAG_MASK) | ((source & GATHER_DUPLICATE_BIT) ? MDUP_FLAG_MASK : 0u));
+				}
+			}
 		}
 	}
 }
 
 // One workgroup per BGZF block: block first_block + blockIdx.x of the file goes to out + blockIdx.x * SBAM_BLOCK.  n > 0.
 __global__ void __launch_bounds__(GATHER_THREADS) sorted_bam_gather_kernel(const uint8_t* __restrict__ stream, const uint64_t* __restrict__ record_offset, const uint32_t* __restrict__ order,
-		const uint64_t* __restrict__ out_offset, const uint32_t* __restrict__ block_first, uint64_t n, uint64_t total_bytes, uint64_t n_blocks, uint64_t first_block, const Crc32Tables* __restrict__ tables, uint8_t* out) {
+		const uint64_t* __restrict__ out_offset, const uint32_t* __restrict__ block_first, uint64_t n, uint64_t total_bytes, uint64_t n_blocks, uint64_t first_block, const Crc32Tables* __restrict__ tables, uint8_t* out, const uint8_t* __restrict__ duplicate) {
 	__shared__ GatherShared shared;
 	const uint32_t t = threadIdx.x;
 	const uint64_t b = first_block + blockIdx.x;
@@ -112,7 +131,7 @@ __global__ void __launch_bounds__(GATHER_THREADS) sorted_bam_gather_kernel(const
 	const uint32_t payload_at = pad + SBAM_HEAD;
 	sbam_frame_begin(shared.frame, tables, pad, length, t);
 
-	gather_payload(shared, stream, record_offset, order, out_offset, block_first, n, n_blocks, b, begin, length, image, payload_at, t);
+	gather_payload(shared, stream, record_offset, order, out_offset, block_first, n, n_blocks, b, begin, length, image, payload_at, t, duplicate);
 	__syncthreads();
 	sbam_frame_finish(shared.frame, (uint32_t*) shared.source, pad, length, block_out, t);
 }
@@ -142,7 +161,7 @@ struct LdsOr { uint32_t* words; __device__ __forceinline__ void operator()(uint3
 // pieces of DEFLATE_GRID blocks, one behind the other on the stream, over the same token words).  n > 0.
 __global__ void __launch_bounds__(GATHER_THREADS) sorted_bam_deflate_kernel(const uint8_t* __restrict__ stream, const uint64_t* __restrict__ record_offset, const uint32_t* __restrict__ order,
 		const uint64_t* __restrict__ out_offset, const uint32_t* __restrict__ block_first, uint64_t n, uint64_t total_bytes, uint64_t n_blocks, uint64_t first_block, uint32_t window_block,
-		const Crc32Tables* __restrict__ tables, uint8_t* out, uint32_t* tokens, uint32_t* block_bytes) {
+		const Crc32Tables* __restrict__ tables, uint8_t* out, uint32_t* tokens, uint32_t* block_bytes, const uint8_t* __restrict__ duplicate) {
 	__shared__ DeflateShared shared;
 	const uint32_t t = threadIdx.x, lane = t % 64, wave = (uint32_t) __builtin_amdgcn_readfirstlane((int) (t / 64));
 	uint32_t* const token = tokens + (uint64_t) blockIdx.x * DEFLATE_TOKEN_WORDS;
@@ -158,7 +177,7 @@ __global__ void __launch_bounds__(GATHER_THREADS) sorted_bam_deflate_kernel(cons
 		const uint32_t pad = (uint32_t) ((uint64_t) block_out & 15u);
 		const uint32_t payload_at = pad + SBAM_HEAD;
 		sbam_frame_begin(shared.frame, tables, pad, length, t);
-		gather_payload(shared, stream, record_offset, order, out_offset, block_first, n, n_blocks, b, begin, length, image, payload_at, t);
+		gather_payload(shared, stream, record_offset, order, out_offset, block_first, n, n_blocks, b, begin, length, image, payload_at, t, duplicate);
 		for (uint32_t i = t; i < DFO_MAX_SEGMENTS * DFO_HASH_SLOTS; i += GATHER_THREADS) (&shared.table[0][0])[i] = 0;
 		for (uint32_t i = t; i < sizeof(DfoState) / 4; i += GATHER_THREADS) ((uint32_t*) &state)[i] = 0;
 		__syncthreads();
@@ -375,11 +394,12 @@ const char* const COMPRESSION_BUFFERS[] = { "sortedbam.tokens", "sortedbam.block
 int launch_gather(agpu_ctx* ctx, uint64_t first_block) {
 	const uint64_t blocks = std::min<uint64_t>(ctx->sorted_bam_window_blocks, ctx->sorted_bam_blocks - first_block);
 	const uint64_t bytes = std::min<uint64_t>(blocks * SBAM_PAYLOAD, ctx->sorted_bam_bytes - first_block * SBAM_PAYLOAD);
+	const uint8_t* const duplicate = ctx->markdup.on ? ctx->markdup.buffer("markdup.flag").as<uint8_t>() : nullptr; // (--mark-duplicates off: the kernels do what they did without it)
 	if (ctx->sorted_bam_level == 0) {
 		KernelTimer timer(ctx, "sorted_bam_gather_kernel", 2 * bytes + blocks * (SBAM_HEAD + SBAM_TAIL));
 		sorted_bam_gather_kernel<<<(unsigned int) blocks, GATHER_THREADS, 0, ctx->stream>>>(ctx->ingest_stream.as<uint8_t>(), ctx->scratch("ingest.record_offset").as<uint64_t>(), ctx->scratch("sortedbam.order").as<uint32_t>(),
 			ctx->scratch("sortedbam.out_offset").as<uint64_t>(), ctx->scratch("sortedbam.block_first").as<uint32_t>(), ctx->sorted_bam_records, ctx->sorted_bam_bytes, ctx->sorted_bam_blocks, first_block,
-			ctx->scratch("sortedbam.crc_tables").as<Crc32Tables>(), ctx->scratch("sortedbam.staging").as<uint8_t>());
+			ctx->scratch("sortedbam.crc_tables").as<Crc32Tables>(), ctx->scratch("sortedbam.staging").as<uint8_t>(), duplicate);
 	} else { // compressed blocks into their staging slots, their sizes scanned, the blocks packed
 		hipStream_t s = ctx->stream;
 		DeviceBuffer& block_bytes = ctx->scratch("sortedbam.block_bytes"); DeviceBuffer& window_offset = ctx->scratch("sortedbam.window_offset"); DeviceBuffer& rocprim_scratch = ctx->scratch("sortedbam.rocprim");
@@ -387,7 +407,7 @@ int launch_gather(agpu_ctx* ctx, uint64_t first_block) {
 		  for (uint64_t done = 0; done < blocks; done += DEFLATE_GRID)
 		  sorted_bam_deflate_kernel<<<(unsigned int) std::min<uint64_t>(blocks - done, DEFLATE_GRID), GATHER_THREADS, 0, s>>>(ctx->ingest_stream.as<uint8_t>(), ctx->scratch("ingest.record_offset").as<uint64_t>(), ctx->scratch("sortedbam.order").as<uint32_t>(),
 			ctx->scratch("sortedbam.out_offset").as<uint64_t>(), ctx->scratch("sortedbam.block_first").as<uint32_t>(), ctx->sorted_bam_records, ctx->sorted_bam_bytes, ctx->sorted_bam_blocks, first_block, (uint32_t) done,
-			ctx->scratch("sortedbam.crc_tables").as<Crc32Tables>(), ctx->scratch("sortedbam.staging").as<uint8_t>(), ctx->scratch("sortedbam.tokens").as<uint32_t>(), block_bytes.as<uint32_t>()); }
+			ctx->scratch("sortedbam.crc_tables").as<Crc32Tables>(), ctx->scratch("sortedbam.staging").as<uint8_t>(), ctx->scratch("sortedbam.tokens").as<uint32_t>(), block_bytes.as<uint32_t>(), duplicate); }
 		size_t temporary = 0;
 		HIP_CHECK(rocprim::exclusive_scan(nullptr, temporary, block_bytes.as<uint32_t>() + first_block, window_offset.as<uint64_t>(), (uint64_t) 0, (size_t) blocks + 1, rocprim::plus<uint64_t>(), s));
 		if (temporary > rocprim_scratch.capacity) { HIP_CHECK(hipStreamSynchronize(s)); ALLOC(rocprim_scratch, temporary); }
@@ -495,7 +515,10 @@ int agpu_sorted_bam_begin(agpu_ctx* ctx, agpu_sorted_bam_info* info) {
 	HIP_CHECK(hipSetDevice(ctx->device));
 	hipStream_t s = ctx->stream;
 	ctx->sorted_bam_active = true; // (from here on nothing of this context is given back when an allocation fails: DeviceBuffer::release_idle_buffers)
-	struct Guard { agpu_ctx* ctx; bool keep; ~Guard() { if (!keep) ctx->sorted_bam_active = false; } } guard = { ctx, false };
+	struct Guard { agpu_ctx* ctx; bool keep; ~Guard() { if (!keep) { ctx->sorted_bam_active = false; ctx->markdup.on = false; ctx->markdup.release_all(); } } } guard = { ctx, false };
+	// --mark-duplicates: one byte per record, found now -- its working buffers are gone before those of the file are allocated, so the two peaks do not add
+	const bool mark_duplicates = ctx->markdup.next;
+	if (mark_duplicates) TRY(markdup_find(ctx));
 	const uint64_t bytes = size - base, n_blocks = sbam_block_count(bytes);
 	uint64_t window_bytes = DEFAULT_WINDOW_BYTES;
 	{ const char* knob = getenv("ARRIBA_SORTED_BAM_WINDOW"); if (knob != nullptr && knob[0] != 0) window_bytes = strtoull(knob, nullptr, 10); }
@@ -545,6 +568,7 @@ int agpu_sorted_bam_begin(agpu_ctx* ctx, agpu_sorted_bam_info* info) {
 	} else if (bytes != 0) { set_last_error("agpu_sorted_bam_begin: the records of the stream do not add up to its size"); return AGPU_ERR_INVALID; }
 	ctx->sorted_bam_records = n; ctx->sorted_bam_bytes = bytes; ctx->sorted_bam_blocks = n_blocks; ctx->sorted_bam_window_blocks = window_blocks; ctx->sorted_bam_next_block = 0; ctx->sorted_bam_gathered_block = ~0ull;
 	ctx->sorted_bam_index_ready = false; ctx->sorted_bam_level = level; ctx->sorted_bam_level_next = 0; ctx->sorted_bam_compressed_bytes = 0;
+	ctx->markdup.on = mark_duplicates; ctx->markdup.next = false;
 	memset(info, 0, sizeof(*info));
 	info->records = n; info->uncompressed_bytes = bytes; info->file_bytes = bytes + n_blocks * (SBAM_HEAD + SBAM_TAIL); info->windows = (n_blocks + window_blocks - 1) / window_blocks;
 	info->window_bytes = std::max<uint64_t>(std::min(window_blocks, n_blocks), 1) * SBAM_BLOCK;
@@ -644,6 +668,7 @@ int agpu_sorted_bam_end(agpu_ctx* ctx) {
 	(void) hipSetDevice(ctx->device);
 	const hipError_t status = hipStreamSynchronize(ctx->stream); // (a window gathered ahead that nobody asked for)
 	ctx->sorted_bam_active = false; ctx->sorted_bam_index_ready = false; ctx->sorted_bam_gathered_block = ~0ull; ctx->sorted_bam_level = 0;
+	ctx->markdup.on = false; ctx->markdup.release_all(); // (behind the synchronisation: no gather reads "markdup.flag" any more)
 	collect_kernel_samples(ctx);
 	if (status != hipSuccess) { set_last_error(std::string("agpu_sorted_bam_end: ") + hipGetErrorString(status)); return AGPU_ERR_DEVICE; }
 	return AGPU_OK;

@@ -247,12 +247,14 @@ struct SortedBam {
 void sorted_bam_header(const uint8_t* input, size_t size, std::vector<uint8_t>& out, std::vector<uint32_t>& ref_length);
 void sorted_bam_frame(const uint8_t* bytes, uint64_t size, std::vector<uint8_t>& out);
 bool references_fit_bai(const uint32_t* ref_length, uint32_t n_ref);
-void sorted_bam_of(const uint8_t* records, uint64_t size, uint64_t first_block_file_offset, const uint32_t* ref_length /* NULL: no index */, uint32_t n_ref, SortedBam& result, int level = 0); // level: 0 stored blocks, 1 deflate_out_core.hpp stepped on the host
+void sorted_bam_of(const uint8_t* records, uint64_t size, uint64_t first_block_file_offset, const uint32_t* ref_length /* NULL: no index */, uint32_t n_ref, SortedBam& result, int level = 0, const uint8_t* duplicate = NULL); // level: 0 stored blocks, 1 deflate_out_core.hpp stepped on the host; duplicate: --mark-duplicates, one byte per record
 struct SortedBamIndexed { int32_t ref, pos, end; bool unmapped; uint64_t begin_offset, end_offset; }; // a record of a file for its index: coordinates, and the virtual offsets of its first byte and behind its last
 void sorted_bam_index_of(uint64_t n, const std::function<SortedBamIndexed(uint64_t)>& record, const uint32_t* ref_length, uint32_t n_ref, SortedBam& result);
 void sorted_bam_bai(const agpu_sorted_bam_index_arrays& index, std::vector<uint8_t>& out);
 void write_file(const std::string& path, const std::vector<const std::vector<uint8_t>*>& parts);
-void sorted_bam_write(const uint8_t* input_header, size_t header_size, const uint8_t* records, uint64_t size, const std::string& path, agpu_sorted_bam_info* info, int level = 0);
+void sorted_bam_write(const uint8_t* input_header, size_t header_size, const uint8_t* records, uint64_t size, const std::string& path, agpu_sorted_bam_info* info, int level = 0, bool mark_duplicates = false, agpu_markdup_counts* counts = NULL);
+// --mark-duplicates on the host (markdup.cpp): arriba_amd/csrc/device/markdup_core.hpp stepped over records in host memory; flag[r]: MDUP_FLAG_MASK if record r leaves with 0x400
+void markdup_flags(const uint8_t* records, uint64_t size, std::vector<uint8_t>& flag, agpu_markdup_counts& counts);
 // --supporting-alignments on the host (supporting.cpp): the writer that cuts the framed record blocks of all rows -- one row's behind the other's, from the device or from the
 // stepping -- into PREFIX_ID.bam and makes PREFIX_ID.bam.bai from the arrays of their records; everything goes through *.tmp, and unless `commit` ran nothing of the prefix is
 // left behind.  supporting_alignments: arriba_amd/csrc/device/supporting_core.hpp stepped on the host over records in host memory.

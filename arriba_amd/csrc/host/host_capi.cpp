@@ -675,6 +675,29 @@ int ahost_sorted_bam_file_level(const char* input_path, const char* path, int le
 		return 0;
 	} catch (const std::exception& e) { g_error = e.what(); return -1; }
 }
+// --mark-duplicates (include/arriba_host.h)
+int ahost_sorted_bam_file_marked(const char* input_path, const char* path, int level, int mark_duplicates, agpu_sorted_bam_info* info) { return ahost_sorted_bam_file_marked_counts(input_path, path, level, mark_duplicates, info, NULL); }
+int ahost_sorted_bam_file_marked_counts(const char* input_path, const char* path, int level, int mark_duplicates, agpu_sorted_bam_info* info, agpu_markdup_counts* counts) {
+	if (!input_path || !path) { g_error = "null argument"; return -1; }
+	if (level != 0 && level != 1) { g_error = "the compression level of a sorted BAM file is 0 (stored) or 1"; return -1; }
+	try {
+		std::vector<uint8_t> stream;
+		const uint64_t at = read_whole_bam(input_path, stream);
+		sorted_bam_write(stream.data(), at, stream.data() + at, stream.size() - at, path, info, level, mark_duplicates != 0, counts);
+		return 0;
+	} catch (const std::exception& e) { g_error = e.what(); return -1; }
+}
+int ahost_markdup(const void* records, size_t size, uint8_t* flag, uint64_t n_records, agpu_markdup_counts* counts) {
+	if ((!records && size > 0) || (!flag && n_records > 0)) { g_error = "null argument"; return -1; }
+	try {
+		std::vector<uint8_t> bytes; agpu_markdup_counts counted;
+		markdup_flags((const uint8_t*) records, size, bytes, counted);
+		if (bytes.size() != n_records) throw std::runtime_error("ahost_markdup: the stream holds " + std::to_string(bytes.size()) + " records, not " + std::to_string(n_records));
+		if (n_records > 0) memcpy(flag, bytes.data(), n_records);
+		if (counts) *counts = counted;
+		return 0;
+	} catch (const std::exception& e) { g_error = e.what(); return -1; }
+}
 
 // ---- --supporting-alignments (include/arriba_host.h) ----
 struct ahost_supporting_writer { SupportingWriter writer; ahost_supporting_writer(const char* prefix, const uint8_t* header, uint64_t bytes, uint32_t n_rows, const uint64_t* row_file_bytes) : writer(prefix, header, bytes, n_rows, row_file_bytes) {} };

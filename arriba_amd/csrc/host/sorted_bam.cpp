@@ -13,6 +13,7 @@
 #include "../device/crc32_core.hpp"
 #include "../device/sorted_bam_core.hpp"
 #include "../device/deflate_out_core.hpp"
+#include "../device/markdup_core.hpp"
 
 namespace arriba {
 
@@ -197,7 +198,8 @@ agpu_sorted_bam_index_arrays SortedBam::view(uint32_t n_ref) {
 bool references_fit_bai(const uint32_t* ref_length, uint32_t n_ref) { for (uint32_t t = 0; t < n_ref; ++t) if (ref_length[t] > (uint32_t) agpu::SBAM_MAX_REFERENCE) return false; return true; }
 
 // ref_length == NULL: no index
-void sorted_bam_of(const uint8_t* records, uint64_t size, uint64_t first_block_file_offset, const uint32_t* ref_length, uint32_t n_ref, SortedBam& result, int level) {
+// duplicate (--mark-duplicates; NULL: the records as they are): one byte per record of the input, markdup_flags' -- bit 0x400 of every record is set or cleared by it in the copy
+void sorted_bam_of(const uint8_t* records, uint64_t size, uint64_t first_block_file_offset, const uint32_t* ref_length, uint32_t n_ref, SortedBam& result, int level, const uint8_t* duplicate) {
 	using namespace agpu;
 	if (level != 0 && level != 1) throw std::runtime_error("the compression level of a sorted BAM file is 0 (stored) or 1");
 	// the record chain
@@ -219,6 +221,7 @@ void sorted_bam_of(const uint8_t* records, uint64_t size, uint64_t first_block_f
 	// gather and frame
 	std::vector<uint8_t> sorted(size);
 	for (uint64_t i = 0; i < n; ++i) memcpy(sorted.data() + out_offset[i], records + offset[order[i]], parsed[order[i]].size);
+	if (duplicate != NULL) for (uint64_t i = 0; i < n; ++i) { uint8_t& byte = sorted[out_offset[i] + MDUP_FLAG_BYTE]; byte = (uint8_t) ((byte & ~MDUP_FLAG_MASK) | (duplicate[order[i]] != 0 ? MDUP_FLAG_MASK : 0u)); }
 	result.blocks.clear(); result.blocks.reserve(size + sbam_block_count(size) * (SBAM_HEAD + SBAM_TAIL));
 	std::vector<uint64_t> block_offset;
 	sorted_bam_frame_level(sorted.data(), size, level, result.blocks, first_block_file_offset, block_offset);
@@ -312,7 +315,7 @@ void write_file(const std::string& path, const std::vector<const std::vector<uin
 }
 
 // the whole output on the host: FILE and FILE.bai through FILE.tmp / FILE.bai.tmp
-void sorted_bam_write(const uint8_t* input_header, size_t header_size, const uint8_t* records, uint64_t size, const std::string& path, agpu_sorted_bam_info* info, int level) {
+void sorted_bam_write(const uint8_t* input_header, size_t header_size, const uint8_t* records, uint64_t size, const std::string& path, agpu_sorted_bam_info* info, int level, bool mark_duplicates, agpu_markdup_counts* counts) {
 	if (level != 0 && level != 1) throw std::runtime_error("the compression level of a sorted BAM file is 0 (stored) or 1");
 	std::vector<uint8_t> header, framed_header, bai, eof; std::vector<uint32_t> ref_length;
 	sorted_bam_header(input_header, header_size, header, ref_length);
@@ -321,7 +324,10 @@ void sorted_bam_write(const uint8_t* input_header, size_t header_size, const uin
 	const bool with_index = references_fit_bai(ref_length.data(), (uint32_t) ref_length.size());
 	if (!with_index) std::cerr << "WARNING: a reference is longer than 2^29 bases, which a BAI index cannot address: '" << path << "' is written without '" << path << ".bai'" << std::endl;
 	SortedBam sorted;
-	sorted_bam_of(records, size, framed_header.size(), with_index ? ref_length.data() : NULL, (uint32_t) ref_length.size(), sorted, level);
+	std::vector<uint8_t> duplicate; agpu_markdup_counts counted; memset(&counted, 0, sizeof(counted));
+	if (mark_duplicates) markdup_flags(records, size, duplicate, counted);
+	if (counts) *counts = counted;
+	sorted_bam_of(records, size, framed_header.size(), with_index ? ref_length.data() : NULL, (uint32_t) ref_length.size(), sorted, level, mark_duplicates ? duplicate.data() : NULL);
 	const std::string bam_tmp = path + ".tmp", bai_tmp = path + ".bai.tmp";
 	try {
 		write_file(bam_tmp, { &framed_header, &sorted.blocks, &eof });

@@ -69,7 +69,9 @@ void usage() {
 	             " --supporting-alignments PREFIX  PREFIX_ID.bam and .bam.bai per row of -o: the alignments of its read_identifiers near its breakpoints (extract_fusion-supporting_alignments.sh)\n"
 	             " --supporting-window INT  how far from a breakpoint they may lie (1000000)\n"
 	             " --virus-expression FILE  per viral contig (-v) genome size, covered bases, high-quality alignments and RPKM, related strains collapsed (quantify_virus_expression.sh)\n"
-	             " --coverage FILE  the per-base alignment depth of -x as bedGraph text: a line per run of equal depth > 0, contigs in header order\n";
+	             " --coverage FILE  the per-base alignment depth of -x as bedGraph text: a line per run of equal depth > 0, contigs in header order\n"
+	             " --mark-duplicates  the records of --sorted-bam leave with flag 0x400 set on duplicate templates and cleared on all others (what samtools markdup or Picard make of the sorted\n"
+	             "                    file: one library, no optical duplicates, no UMIs); not together with -u, whose input marks it would overwrite\n";
 }
 
 }
@@ -100,12 +102,14 @@ int main(int argc, char** argv) {
 		else if (strcmp(argv[a], "--sorted-bam-compression") == 0 && a + 1 < argc) { long level; require(parse_int(argv[++a], level) && (level == 0 || level == 1), "invalid argument to --sorted-bam-compression: 0 (stored) or 1"); options.sorted_bam_compression = (int) level; compression_given = true; }
 		else if (strcmp(argv[a], "--supporting-alignments") == 0 && a + 1 < argc) { options.supporting_alignments_prefix = argv[++a]; parent_exists(options.supporting_alignments_prefix); }
 		else if (strcmp(argv[a], "--virus-expression") == 0 && a + 1 < argc) { options.virus_expression_file = argv[++a]; parent_exists(options.virus_expression_file); }
+		else if (strcmp(argv[a], "--mark-duplicates") == 0) options.mark_duplicates = 1;
 		else if (strcmp(argv[a], "--coverage") == 0 && a + 1 < argc) { options.coverage_file = argv[++a]; parent_exists(options.coverage_file); }
 		else if (strcmp(argv[a], "--supporting-window") == 0 && a + 1 < argc) { long window; require(parse_int(argv[++a], window) && window > 0 && window <= 0x7FFFFFFFl, "invalid argument to --supporting-window"); options.supporting_alignments_window = window; }
 		else if (strcmp(argv[a], "--device") == 0 && a + 1 < argc) { long device; require(parse_int(argv[++a], device) && device >= 0, "invalid argument to --device"); options.device_index = (int) device; }
 		else arguments.push_back(argv[a]);
 	}
 	require(!compression_given || options.sorted_bam_file != nullptr, "--sorted-bam-compression needs --sorted-bam");
+	require(!options.mark_duplicates || options.sorted_bam_file != nullptr, "--mark-duplicates needs --sorted-bam");
 	std::string interesting_contigs, viral_contigs;
 	bool seen[256]; memset(seen, 0, sizeof(seen));
 	bool blacklist_enabled = true;
@@ -184,6 +188,7 @@ int main(int argc, char** argv) {
 		}
 		require(!(optind < n_arguments && (arguments[optind][0] == '\0' || arguments[optind][0] != '-')), std::string("option -") + (char) c + " has too many arguments (arguments with blanks must be wrapped in quotes)");
 	}
+	require(!(options.mark_duplicates && options.device.external_duplicate_marking), "--mark-duplicates and -u exclude each other: -u says that the duplicate marks of the input are authoritative, --mark-duplicates overwrites them");
 	require(options.chimeric_bam_file != NULL, "missing mandatory option -x");
 	require(options.gene_annotation_file != NULL, "missing mandatory option -g");
 	require(options.output_file != NULL, "missing mandatory option -o");

@@ -40,6 +40,9 @@ extern "C" int agpu_supporting_next(agpu_ctx* ctx, void* pinned, uint64_t capaci
 extern "C" int agpu_supporting_index(agpu_ctx* ctx, uint64_t first_block_file_offset, agpu_supporting_index_arrays* index) __attribute__((weak));
 extern "C" int agpu_supporting_end(agpu_ctx* ctx) __attribute__((weak));
 extern "C" int agpu_support_pool_release(agpu_ctx* ctx) __attribute__((weak));
+// ... and those of --mark-duplicates
+extern "C" int agpu_sorted_bam_set_mark_duplicates(agpu_ctx* ctx, int on) __attribute__((weak));
+extern "C" int agpu_markdup_stats(agpu_ctx* ctx, agpu_markdup_counts* counts) __attribute__((weak));
 // ... and the one of --virus-expression
 extern "C" int agpu_virus_expression(agpu_ctx* ctx, const int32_t* viral_ref, const uint32_t* viral_length, uint32_t n_viruses, uint32_t n_ref, agpu_virus_counters* counters) __attribute__((weak));
 
@@ -213,10 +216,25 @@ struct Run {
 
 // read_chimeric_alignments on the device (source/read_chimeric_alignments.cpp:560-773): the host opens the file, parses the BAM header and feeds the bytes in
 // pieces through two pinned buffers in turn; the batch and coverage_t are built in HBM, the host takes over the counters and coverage_t
+// --mark-duplicates: what is refused, before anything is launched or read for the sample
+void check_mark_duplicates(const arriba_workflow_options& o) {
+	if (!o.mark_duplicates) return;
+	if (o.sorted_bam_file == nullptr) throw Failure{ "ERROR: --mark-duplicates needs --sorted-bam: the marks are written into the sorted BAM file" };
+	if (o.device.external_duplicate_marking) throw Failure{ "ERROR: --mark-duplicates and -u exclude each other: -u says that the duplicate marks of the input are authoritative, --mark-duplicates overwrites them" };
+}
+std::string mark_duplicates_line(const agpu_markdup_counts& c) {
+	std::ostringstream text;
+	text << "Marking duplicates in the sorted BAM file (templates=" << c.templates << ", pairs=" << c.pairs << ", fragments=" << c.fragments << ", duplicate_pairs=" << c.duplicate_pairs << ", duplicate_fragments=" << c.duplicate_fragments
+	     << ", records_flagged=" << c.records_flagged << ", records_changed=" << c.records_changed << ")";
+	return text.str();
+}
+
 void feed_file(Run& run) {
 	const arriba_workflow_options& o = run.options;
 	const double started = now_seconds();
 	run.feed_started = started;
+	check_mark_duplicates(o);
+	if (o.mark_duplicates && (!agpu_sorted_bam_set_mark_duplicates || !agpu_markdup_stats)) throw Failure{ "ERROR: --mark-duplicates needs the device library (agpu_sorted_bam_set_mark_duplicates), which this build is not linked with" }; // (before the feed, not behind it)
 	if (run.ranks != nullptr && o.sorted_bam_file != nullptr) throw Failure{ "ERROR: a sorted BAM file of one sample over several GPUs is not supported" };
 	if (run.ranks != nullptr && o.supporting_alignments_prefix != nullptr) throw Failure{ "ERROR: supporting alignments of one sample over several GPUs are not supported" };
 	if (run.ranks != nullptr && o.virus_expression_file != nullptr) throw Failure{ "ERROR: a virus expression table of one sample over several GPUs is not supported" };
@@ -456,7 +474,10 @@ void write_sorted_bam(Run& run) {
 	const double started = now_seconds();
 	agpu_sorted_bam_info info;
 	if (level != 0) device_check(agpu_sorted_bam_set_compression(run.device, level));
+	const bool mark_duplicates = run.options.mark_duplicates != 0;
+	if (mark_duplicates) { check_mark_duplicates(run.options); device_check(agpu_sorted_bam_set_mark_duplicates(run.device, 1)); }
 	device_check(agpu_sorted_bam_begin(run.device, &info));
+	if (mark_duplicates) { agpu_markdup_counts counts; device_check(agpu_markdup_stats(run.device, &counts)); run.say(mark_duplicates_line(counts)); }
 	struct Ender { Run& run; ~Ender() { agpu_sorted_bam_end(run.device); } } ender = { run };
 	FILE* file = nullptr;
 	try {
@@ -1226,8 +1247,15 @@ void run_sample(Run& run, bool already_fed, double sample_started) {
 	}
 	else {
 		if (run.ranks != nullptr) throw Failure{ "ERROR: one sample over several ranks needs read_chimeric_alignments on the device (host_ingest = 0): the parts of the batch are exchanged in device format" };
+		check_mark_duplicates(o);
 		host_check(ahost_ingest_bam_file(run.host, o.chimeric_bam_file, o.device.external_duplicate_marking, o.device.max_itd_length));
-		if (o.sorted_bam_file != nullptr) { const double before = now_seconds(); host_check(ahost_sorted_bam_file_level(o.chimeric_bam_file, o.sorted_bam_file, o.sorted_bam_compression, nullptr)); if (run.timing) run.timing->sorted_bam = now_seconds() - before; } // (the host's stepping of the same code)
+		if (o.sorted_bam_file != nullptr) { // (the host's stepping of the same code)
+			const double before = now_seconds();
+			agpu_markdup_counts counts;
+			host_check(ahost_sorted_bam_file_marked_counts(o.chimeric_bam_file, o.sorted_bam_file, o.sorted_bam_compression, o.mark_duplicates, nullptr, &counts));
+			if (o.mark_duplicates) run.say(mark_duplicates_line(counts));
+			if (run.timing) run.timing->sorted_bam = now_seconds() - before;
+		}
 		if (o.virus_expression_file != nullptr) { const double before = now_seconds(); host_check(ahost_virus_expression_file(run.host, o.chimeric_bam_file, o.virus_expression_file)); if (run.timing) run.timing->virus_expression = now_seconds() - before; } // (likewise)
 		if (o.coverage_file != nullptr) { const double before = now_seconds(); host_check(ahost_depth_file(o.chimeric_bam_file, o.coverage_file, nullptr)); if (run.timing) run.timing->coverage = now_seconds() - before; } // (likewise)
 		device_check(agpu_upload_genome(run.device, ahost_genome_view(run.host)));
@@ -1414,7 +1442,7 @@ int arriba_workflow_run(const arriba_workflow_options* options, arriba_workflow_
 struct arriba_workflow_session {
 	Run* lanes[2];
 	int processed_lane = 0; // of the sample arriba_workflow_sample worked on last
-	struct Submitted { std::string bam, sorted_bam, supporting, virus_expression, coverage; int sorted_bam_level = 0; int lane = 0; std::thread feeder; bool fed = false, ingest_finished = false, started = false; std::string error; int error_code = 0; };
+	struct Submitted { std::string bam, sorted_bam, supporting, virus_expression, coverage; int sorted_bam_level = 0, mark_duplicates = 0; int lane = 0; std::thread feeder; bool fed = false, ingest_finished = false, started = false; std::string error; int error_code = 0; };
 	std::deque<std::unique_ptr<Submitted>> queue; // oldest first; at most two
 	std::mutex mutex; std::condition_variable changed;
 	bool ingest_busy = false; // a lane is between agpu_ingest_begin and agpu_ingest_finish
@@ -1422,6 +1450,7 @@ struct arriba_workflow_session {
 	std::string next_supporting; // arriba_workflow_supporting_alignments: likewise
 	std::string next_virus_expression; // arriba_workflow_virus_expression: likewise
 	std::string next_coverage; // arriba_workflow_coverage: likewise
+	int mark_duplicates = 0;  // arriba_workflow_sorted_bam_mark_duplicates: of the samples submitted from now on (at first: options.mark_duplicates of arriba_workflow_open)
 	int sorted_bam_level = 0; // arriba_workflow_sorted_bam_compression: of the samples submitted from now on (at first: options.sorted_bam_compression of arriba_workflow_open)
 	bool defer_output = false;
 	bool retrying = false; // arriba_workflow_sample runs a sample again after the device ran out of memory with two lanes (below)
@@ -1443,7 +1472,7 @@ struct arriba_workflow_session {
 		lanes[lane]->writer_error.clear();
 	}
 	std::string take_deferred_error() { std::lock_guard<std::mutex> lock(writer_mutex); std::string text; text.swap(deferred_error); return text; }
-	arriba_workflow_session(const arriba_workflow_options& o) { lanes[0] = new Run(o); lanes[1] = nullptr; sorted_bam_level = o.sorted_bam_compression; }
+	arriba_workflow_session(const arriba_workflow_options& o) { lanes[0] = new Run(o); lanes[1] = nullptr; sorted_bam_level = o.sorted_bam_compression; mark_duplicates = o.mark_duplicates; }
 	~arriba_workflow_session() {
 		drain();
 		leave();
@@ -1487,14 +1516,14 @@ struct arriba_workflow_session {
 		Run& run = *lanes[lane];
 		run.bam_path = bam; run.options.chimeric_bam_file = run.bam_path.c_str();
 		run.sorted_bam_path.swap(next_sorted_bam); next_sorted_bam.clear(); run.options.sorted_bam_file = run.sorted_bam_path.empty() ? nullptr : run.sorted_bam_path.c_str();
-		run.options.sorted_bam_compression = sorted_bam_level;
+		run.options.sorted_bam_compression = sorted_bam_level; run.options.mark_duplicates = mark_duplicates;
 		run.supporting_prefix.swap(next_supporting); next_supporting.clear(); run.options.supporting_alignments_prefix = run.supporting_prefix.empty() ? nullptr : run.supporting_prefix.c_str();
 		run.virus_expression_path.swap(next_virus_expression); next_virus_expression.clear(); run.options.virus_expression_file = run.virus_expression_path.empty() ? nullptr : run.virus_expression_path.c_str();
 		run.coverage_path.swap(next_coverage); next_coverage.clear(); run.options.coverage_file = run.coverage_path.empty() ? nullptr : run.coverage_path.c_str();
 		run.timing = nullptr; run.report = nullptr;
 		prepare_sample(run);
 		std::unique_ptr<Submitted> sample(new Submitted());
-		sample->bam = bam; sample->sorted_bam = run.sorted_bam_path; sample->supporting = run.supporting_prefix; sample->virus_expression = run.virus_expression_path; sample->coverage = run.coverage_path; sample->sorted_bam_level = sorted_bam_level; sample->lane = lane;
+		sample->bam = bam; sample->sorted_bam = run.sorted_bam_path; sample->supporting = run.supporting_prefix; sample->virus_expression = run.virus_expression_path; sample->coverage = run.coverage_path; sample->sorted_bam_level = sorted_bam_level; sample->mark_duplicates = mark_duplicates; sample->lane = lane;
 		Submitted* mine = sample.get();
 		{ std::lock_guard<std::mutex> lock(mutex); queue.push_back(std::move(sample)); }
 		if (!run.device_ingest) { join_writer_of(lane); std::lock_guard<std::mutex> lock(mutex); mine->fed = true; return; } // (the host ingest reads the file inside arriba_workflow_sample)
@@ -1540,6 +1569,12 @@ int arriba_workflow_sorted_bam_compression(arriba_workflow_session* session, int
 	if (!session) { g_error = "ERROR: null argument"; return -1; }
 	if (level != 0 && level != 1) { g_error = "ERROR: the compression level of a sorted BAM file is 0 (stored) or 1"; return -1; }
 	session->sorted_bam_level = level;
+	return 0;
+}
+
+int arriba_workflow_sorted_bam_mark_duplicates(arriba_workflow_session* session, int on) {
+	if (!session) { g_error = "ERROR: null argument"; return -1; }
+	session->mark_duplicates = on != 0;
 	return 0;
 }
 
@@ -1619,6 +1654,7 @@ int arriba_workflow_sample(arriba_workflow_session* session, const char* chimeri
 		const std::string behind = session->queue.empty() ? std::string() : session->queue.front()->bam;
 		const std::string behind_sorted_bam = session->queue.empty() ? std::string() : session->queue.front()->sorted_bam, again_sorted_bam = lane->sorted_bam_path;
 		const int behind_level = session->queue.empty() ? 0 : session->queue.front()->sorted_bam_level, again_level = lane->options.sorted_bam_compression, session_level = session->sorted_bam_level;
+		const int behind_marks = session->queue.empty() ? 0 : session->queue.front()->mark_duplicates, again_marks = lane->options.mark_duplicates, session_marks = session->mark_duplicates;
 		const std::string behind_supporting = session->queue.empty() ? std::string() : session->queue.front()->supporting, again_supporting = lane->supporting_prefix;
 		const std::string behind_virus = session->queue.empty() ? std::string() : session->queue.front()->virus_expression, again_virus = lane->virus_expression_path;
 		const std::string behind_coverage = session->queue.empty() ? std::string() : session->queue.front()->coverage, again_coverage = lane->coverage_path;
@@ -1630,14 +1666,14 @@ int arriba_workflow_sample(arriba_workflow_session* session, const char* chimeri
 		delete session->lanes[1]; session->lanes[1] = nullptr; session->processed_lane = 0;
 		fprintf(stderr, "arriba_workflow_sample: %s -- with two samples in flight; '%s' is run again with the device to itself\n", first_error.c_str(), chimeric_bam_file);
 		session->retrying = true;
-		session->next_sorted_bam = again_sorted_bam; session->next_supporting = again_supporting; session->next_virus_expression = again_virus; session->next_coverage = again_coverage; session->sorted_bam_level = again_level;
+		session->next_sorted_bam = again_sorted_bam; session->next_supporting = again_supporting; session->next_virus_expression = again_virus; session->next_coverage = again_coverage; session->sorted_bam_level = again_level; session->mark_duplicates = again_marks;
 		status = arriba_workflow_sample(session, chimeric_bam_file, output_file, discarded_output_file, report, timing);
 		session->retrying = false;
 		if (status == 0 && !behind.empty()) { // (as its caller submitted it: a failure to feed it is reported by the call that asks for it)
-			try { session->next_sorted_bam = behind_sorted_bam; session->next_supporting = behind_supporting; session->next_virus_expression = behind_virus; session->next_coverage = behind_coverage; session->sorted_bam_level = behind_level; session->submit(behind.c_str()); }
+			try { session->next_sorted_bam = behind_sorted_bam; session->next_supporting = behind_supporting; session->next_virus_expression = behind_virus; session->next_coverage = behind_coverage; session->sorted_bam_level = behind_level; session->mark_duplicates = behind_marks; session->submit(behind.c_str()); }
 			catch (const Failure&) {} catch (const std::exception&) {}
 		}
-		session->sorted_bam_level = session_level;
+		session->sorted_bam_level = session_level; session->mark_duplicates = session_marks;
 	}
 	return status;
 }

@@ -42,6 +42,13 @@ def depth_stats_of(stats):
     return out
 
 
+def markdup_counts_of(counts):
+    """agpu_markdup_counts (the device's or the host's) as a dict"""
+    out = {name: int(getattr(counts, name)) for name in ("templates", "pairs", "fragments", "duplicate_pairs", "duplicate_fragments", "records_flagged", "records_changed", "peak_bytes")}
+    out["seconds"] = dict(zip(("name_ids", "ends", "selection"), counts.seconds))
+    return out
+
+
 class ArribaError(RuntimeError):
     pass
 
@@ -188,11 +195,18 @@ class WorkflowSession(object):
         if self._lib.arriba_workflow_sorted_bam_compression(self._session, int(level)) != 0:
             raise ArribaError(self._lib.arriba_workflow_last_error().decode())
 
-    def submit(self, bam, sorted_bam_file=None, supporting_alignments_prefix=None, sorted_bam_compression=None, virus_expression_file=None, coverage_file=None):
+    def sorted_bam_mark_duplicates(self, on):
+        """--mark-duplicates of the samples submitted from now on: their --sorted-bam files leave with flag 0x400 set on duplicate templates and cleared on all others"""
+        if self._lib.arriba_workflow_sorted_bam_mark_duplicates(self._session, int(bool(on))) != 0:
+            raise ArribaError(self._lib.arriba_workflow_last_error().decode())
+
+    def submit(self, bam, sorted_bam_file=None, supporting_alignments_prefix=None, sorted_bam_compression=None, virus_expression_file=None, coverage_file=None, mark_duplicates=None):
         """the sample that comes after the one `sample` is called for next: its file is fed (PCIe, the front of read_chimeric_alignments) while the stages of that one run;
         sorted_bam_file: its records in coordinate order with their index (--sorted-bam), written when its ingest is finished; sorted_bam_compression: its level (None: as it is)"""
         if sorted_bam_compression is not None:
             self.sorted_bam_compression(sorted_bam_compression)
+        if mark_duplicates is not None:  # (--mark-duplicates: None leaves it as it is)
+            self.sorted_bam_mark_duplicates(mark_duplicates)
         self._lib.arriba_workflow_sorted_bam(self._session, sorted_bam_file.encode() if sorted_bam_file else None)
         self._lib.arriba_workflow_supporting_alignments(self._session, supporting_alignments_prefix.encode() if supporting_alignments_prefix else None)  # (--supporting-alignments: PREFIX_ID.bam per row of its fusions file)
         self._lib.arriba_workflow_virus_expression(self._session, virus_expression_file.encode() if virus_expression_file else None)  # (--virus-expression: its table, written when its ingest is finished)
@@ -291,12 +305,14 @@ class WorkflowSession(object):
     def _lane_contexts(self):
         return [ctx for ctx in (self._lib.arriba_workflow_lane_device(self._session, lane) for lane in (0, 1)) if ctx]
 
-    def sample(self, bam, output_file, discarded_output_file=None, sorted_bam_file=None, supporting_alignments_prefix=None, sorted_bam_compression=None, virus_expression_file=None, coverage_file=None):
+    def sample(self, bam, output_file, discarded_output_file=None, sorted_bam_file=None, supporting_alignments_prefix=None, sorted_bam_compression=None, virus_expression_file=None, coverage_file=None, mark_duplicates=None):
         """one sample, BAM file -> fusions.tsv (and discarded.tsv); returns the stages with their "(remaining=N)" counts.  sorted_bam_file (--sorted-bam): for a sample that was
         not submitted ahead; one that was says it to `submit`"""
         report, timing = _capi.WorkflowReport(), _capi.WorkflowTiming()
         if sorted_bam_compression is not None:  # (as sorted_bam_file: for a sample that was not submitted ahead)
             self.sorted_bam_compression(sorted_bam_compression)
+        if mark_duplicates is not None:  # (likewise)
+            self.sorted_bam_mark_duplicates(mark_duplicates)
         if sorted_bam_file:
             self._lib.arriba_workflow_sorted_bam(self._session, sorted_bam_file.encode())
         if supporting_alignments_prefix:  # (as sorted_bam_file: for a sample that was not submitted ahead)
@@ -509,8 +525,9 @@ class DevicePipeline(object):
 
     MAX_BAI_REFERENCE = 1 << 29
 
-    def write_sorted_bam(self, path, compression=0):
-        """compression (--sorted-bam-compression): 0 stored blocks; 1 every record block deflated on the device (agpu_sorted_bam_set_compression), "file_bytes" is then what the
+    def write_sorted_bam(self, path, compression=0, mark_duplicates=False):
+        """mark_duplicates (--mark-duplicates): flag 0x400 of every record set or cleared on the device by the rule of DESIGN.md 4.14 (agpu_sorted_bam_set_mark_duplicates); the counts
+        are in self.markdup_counts afterwards.  compression (--sorted-bam-compression): 0 stored blocks; 1 every record block deflated on the device (agpu_sorted_bam_set_compression), "file_bytes" is then what the
         blocks really take.  The records of the file of the last read_chimeric_alignments in coordinate order as `path` (BAM of stored BGZF blocks) and `path`.bai -- what run_arriba.sh:47-51 gets
         from `samtools sort` / `samtools index` -- from the record stream that is still in HBM (agpu_sorted_bam_*).  Valid after read_chimeric_alignments and before the next one.
         Written through `path`.tmp / `path`.bai.tmp; returns {"records", "uncompressed_bytes", "file_bytes", "windows", "indexed"}; the seconds of its parts: self.sorted_bam_seconds."""
@@ -524,7 +541,13 @@ class DevicePipeline(object):
         info = _capi.SortedBamInfo()
         if compression != 0:
             self._check(self.api.sorted_bam_set_compression(self.ctx, int(compression)))  # (0: the call is not made, as before the level existed)
+        if mark_duplicates:
+            self._check(self.api.sorted_bam_set_mark_duplicates(self.ctx, 1))  # (off: the call is not made, as before the option existed)
         self._check(self.api.sorted_bam_begin(self.ctx, byref(info)))  # (refused before anything is written: the stream given back, another ingest begun, a part of a sample)
+        if mark_duplicates:
+            counts = _capi.MarkdupCounts()
+            self._check(self.api.markdup_stats(self.ctx, byref(counts)))
+            self.markdup_counts = markdup_counts_of(counts)
         sorted_at = time.perf_counter()
         seconds = {"sort": sorted_at - started, "gather_and_copy": 0.0, "write": 0.0, "index": 0.0}
         temporaries = [path + ".tmp", path + ".bai.tmp"]
@@ -691,6 +714,12 @@ class DevicePipeline(object):
 
     def release_support_pool(self):
         self._check(self.api.support_pool_release(self.ctx))
+
+    def markdup_allocated_bytes(self):
+        """bytes of the "markdup.*" buffers of the context: 0 outside write_sorted_bam, and always when --mark-duplicates is off"""
+        count = c_uint64()
+        self._check(self.api.markdup_allocated_bytes(self.ctx, byref(count)))
+        return int(count.value)
 
     def sorted_bam_compression_allocated_bytes(self):
         """bytes of the device buffers that only --sorted-bam-compression 1 has: 0 as long as it was never used"""
@@ -942,13 +971,15 @@ class DevicePipeline(object):
                      max_genomic_breakpoint_distance=100000, strandedness=None, evalue_cutoff=0.3,
                      min_itd_support=10, min_itd_allele_fraction=0.07, high_expression_quantile=0.998, min_spliced_events=4, min_anchor_length=23,
                      max_homolog_identity=0.3, max_itd_length=100, fill_sequence_gaps=False, top_viral_contigs=5, viral_contig_min_covered_fraction=0.05,
-                     print_extra_info_for_discarded_fusions=False, log=None, sorted_bam_file=None, supporting_alignments_prefix=None, supporting_alignments_window=1000000, virus_expression_file=None, coverage_file=None):
+                     print_extra_info_for_discarded_fusions=False, log=None, sorted_bam_file=None, supporting_alignments_prefix=None, supporting_alignments_window=1000000, virus_expression_file=None, coverage_file=None, mark_duplicates=False):
         """The reference's main() behind read_chimeric_alignments (source/arriba.cpp:119-610) with its default parameters: the read-level cascade, find_fusions,
         every candidate-level filter in the reference's order, assign_confidence, and the two output files.  `log` receives (stage, remaining) pairs --
         the numbers the reference prints as "(remaining=N)".  Filters switched off with -f are skipped by the stages themselves (agpu_params.filter_enabled)."""
         note = log if log is not None else (lambda stage, remaining: None)
         if sorted_bam_file:  # first: the record stream is still in HBM (it is given back when the stages need the memory)
-            self.write_sorted_bam(sorted_bam_file)
+            self.write_sorted_bam(sorted_bam_file, mark_duplicates=mark_duplicates)
+        elif mark_duplicates:
+            raise ArribaError("ERROR: --mark-duplicates needs --sorted-bam: the marks are written into the sorted BAM file")
         if virus_expression_file:  # (--virus-expression: likewise from the stream)
             self.write_virus_expression(virus_expression_file)
         if coverage_file:  # (--coverage: likewise)

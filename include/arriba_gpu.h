@@ -439,6 +439,26 @@ int agpu_depth_begin(agpu_ctx* ctx, const uint32_t* ref_length, const char* name
 int agpu_depth_next(agpu_ctx* ctx, void* pinned, uint64_t capacity, uint64_t* bytes);
 int agpu_depth_end(agpu_ctx* ctx, agpu_depth_stats* stats);
 int agpu_depth_allocated_bytes(agpu_ctx* ctx, uint64_t* bytes); /* of the "depth.*" buffers of the context: 0 outside agpu_depth_begin ... agpu_depth_end */
+/* --mark-duplicates: bit 0x400 of every record of the file of agpu_sorted_bam_* set or cleared on the device, by Picard's rule for one library without optical duplicates and UMIs
+ * (arriba_amd/csrc/device/agpu_markdup.hip, markdup_core.hpp).  The record stream in HBM is not written: the bit is patched in the image of a block while it is gathered.
+ *   agpu_sorted_bam_set_mark_duplicates   before agpu_sorted_bam_begin, for that one begin ... end (the one after it is without marks again), as agpu_sorted_bam_set_compression.
+ *                                         on != 0: the begin finds the duplicate templates (read names -> templates, the ends of their slots, pairs and fragments grouped by
+ *                                         sorted end keys) and keeps one byte per record until agpu_sorted_bam_end; the file is the one ahost_sorted_bam_file_marked gives.
+ *   agpu_markdup_stats                    the counts of the last begin that marked (zeros if none did)
+ *   agpu_markdup_allocated_bytes          of the "markdup.*" buffers of the context: 0 outside agpu_sorted_bam_begin ... agpu_sorted_bam_end, and inside it when the option is off
+ * ARRIBA_MARKDUP_HASH_BITS (a test knob): the low bits of the hash of a read name that are kept. */
+typedef struct {
+	uint64_t templates;            /* distinct read names */
+	uint64_t pairs, fragments;     /* templates with two mapped ends / with one */
+	uint64_t duplicate_pairs, duplicate_fragments;
+	uint64_t records_flagged;      /* records that leave with 0x400 set */
+	uint64_t records_changed;      /* records whose bit 0x400 differs from the input's */
+	uint64_t peak_bytes;           /* of the "markdup.*" buffers (0 on the host) */
+	double seconds[3];             /* name ids and claims; ends; selection and the per-record bytes (device: from HIP events, 0 on the host) */
+} agpu_markdup_counts;
+int agpu_sorted_bam_set_mark_duplicates(agpu_ctx* ctx, int on);
+int agpu_markdup_stats(agpu_ctx* ctx, agpu_markdup_counts* counts);
+int agpu_markdup_allocated_bytes(agpu_ctx* ctx, uint64_t* bytes);
 /* what the host's sequential stages and its output writer need from a batch that lives on the device:
  *   agpu_get_viral_read_counts   mapped_viral_reads_by_contig (source/read_chimeric_alignments.cpp:735-739)
  *   agpu_get_coverage            coverage_t as the reference holds it (16-bit saturating windows, start/end flags); sizes by coverage_window_offset

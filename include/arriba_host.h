@@ -99,6 +99,15 @@ int ahost_sorted_bam_write(const void* input_header, size_t header_size, const v
 int ahost_sorted_bam_level(const void* records, size_t size, uint64_t first_block_file_offset, const uint32_t* ref_length, uint32_t n_ref, int level, const uint8_t** blocks, agpu_sorted_bam_info* info, agpu_sorted_bam_index_arrays* index);
 int ahost_sorted_bam_file_level(const char* input_path, const char* path, int level, agpu_sorted_bam_info* info /* may be NULL */);
 int ahost_sorted_bam_write_level(const void* input_header, size_t header_size, const void* records, size_t size, const char* path, int level, agpu_sorted_bam_info* info /* may be NULL */);
+/* --mark-duplicates: arriba_amd/csrc/device/markdup_core.hpp stepped sequentially on the host (the rule: DESIGN.md 4.14) -- the comparator of agpu_markdup.hip, what --host-ingest runs.
+ *   ahost_markdup                        flag[r], r < n_records (the records the stream holds, else an error): 0x04 -- the mask of 0x400 in byte 19 of a record -- if record r
+ *                                        belongs to a duplicate template, else 0; counts (may be NULL): as agpu_markdup_stats reports them
+ *   ahost_sorted_bam_file_marked         ahost_sorted_bam_file_level; with mark_duplicates != 0 every record is copied with bit 0x400 set or cleared by those bytes -- the file that
+ *                                        agpu_sorted_bam_* writes behind agpu_sorted_bam_set_mark_duplicates.  ahost_sorted_bam_file_level keeps its behaviour.
+ *   ahost_sorted_bam_file_marked_counts  the same, and the counts */
+int ahost_markdup(const void* records, size_t size, uint8_t* flag, uint64_t n_records, agpu_markdup_counts* counts /* may be NULL */);
+int ahost_sorted_bam_file_marked(const char* input_path, const char* path, int level, int mark_duplicates, agpu_sorted_bam_info* info /* may be NULL */);
+int ahost_sorted_bam_file_marked_counts(const char* input_path, const char* path, int level, int mark_duplicates, agpu_sorted_bam_info* info /* may be NULL */, agpu_markdup_counts* counts /* may be NULL */);
 /* ---- --supporting-alignments: the host side of agpu_support_pool_build / agpu_supporting_* (include/arriba_gpu.h) -- one sorted, indexed BAM file per row of fusions.tsv with
  * the alignments of the row's read_identifiers near its breakpoints (the reference's scripts/extract_fusion-supporting_alignments.sh), PREFIX_ID.bam and PREFIX_ID.bam.bai, ID = 1-based
  * rank of the row ----

@@ -64,6 +64,11 @@ typedef struct {
 	                                         NAME START END DEPTH per run of equal depth > 0, contigs in header order --, computed and formatted behind read_chimeric_alignments from the record
 	                                         stream in HBM (include/arriba_gpu.h: agpu_depth_begin).  Of arriba_workflow_run's sample; the samples of a session say theirs with
 	                                         arriba_workflow_coverage.  Not for one sample over several ranks. */
+	int mark_duplicates;                  /* --mark-duplicates: 0 (and a zero-initialised struct) = the records of sorted_bam_file are those of the input; 1 = bit 0x400 of every record is set if its
+	                                         template is a duplicate and cleared if not -- Picard's rule for one library without optical duplicates and UMIs, found on the device from the record
+	                                         stream in HBM (include/arriba_gpu.h: agpu_sorted_bam_set_mark_duplicates; with host_ingest: the same code stepped on the host).
+	                                         Refused without sorted_bam_file and together with device.external_duplicate_marking (-u).  Fusion calling does not see the marks; the files of
+	                                         supporting_alignments_prefix keep the flags of the input. */
 } arriba_workflow_options;
 
 /* what the reference prints as "(remaining=N)" / "(total=N)" / "(marked=N)", in the order of the stages; stage names as in the reference's source */
@@ -123,6 +128,9 @@ int arriba_workflow_sorted_bam(arriba_workflow_session* session, const char* sor
 /* --sorted-bam-compression of the samples that are submitted FROM NOW ON (until the next call; at first options.sorted_bam_compression of arriba_workflow_open): 0 or 1, anything
  * else is refused with a message. */
 int arriba_workflow_sorted_bam_compression(arriba_workflow_session* session, int level);
+/* --mark-duplicates of the samples that are submitted FROM NOW ON, in the same way (at first options.mark_duplicates of arriba_workflow_open).  A sample that has it on without a
+ * --sorted-bam file of its own, or in a session opened with -u, fails with a message before anything is launched for the option. */
+int arriba_workflow_sorted_bam_mark_duplicates(arriba_workflow_session* session, int on);
 /* --supporting-alignments of the sample that is submitted NEXT, in the same way; NULL: none.  The pool of its supporting alignments is built by the thread that finishes its ingest and
  * belongs to its lane until its fusions file is written; the window is options.supporting_alignments_window of arriba_workflow_open. */
 int arriba_workflow_supporting_alignments(arriba_workflow_session* session, const char* prefix);
