@@ -153,6 +153,15 @@ struct MarkdupState {
 	bool next = false, on = false; // agpu_sorted_bam_set_mark_duplicates: of the next agpu_sorted_bam_begin; of the begin ... end under way
 	agpu_markdup_counts counts = {};
 };
+// --gene-counts (agpu_genecount.hip): the "genecount.*" buffers are the context's own and live inside one agpu_gene_counts
+struct GenecountState {
+	std::map<std::string, DeviceBuffer> buffers;
+	DeviceBuffer& buffer(const char* name) { return buffers[name]; }
+	void release_all() { for (std::map<std::string, DeviceBuffer>::iterator b = buffers.begin(); b != buffers.end(); ++b) b->second.release(); }
+	uint64_t allocated() const { uint64_t sum = 0; for (std::map<std::string, DeviceBuffer>::const_iterator b = buffers.begin(); b != buffers.end(); ++b) sum += b->second.capacity; return sum; }
+	bool active = false;
+	agpu_gene_count_stats stats = {};
+};
 }
 struct agpu_ctx {
 	explicit agpu_ctx(std::shared_ptr<agpu::ScratchPool> shared = std::shared_ptr<agpu::ScratchPool>()) : pool(shared ? shared : std::make_shared<agpu::ScratchPool>()),
@@ -243,6 +252,7 @@ struct agpu_ctx {
 	agpu::VirusState virus;     // --virus-expression (agpu_virus.hip)
 	agpu::DepthState depth;     // --coverage (agpu_depth.hip)
 	agpu::MarkdupState markdup; // --mark-duplicates (agpu_markdup.hip)
+	agpu::GenecountState genecount; // --gene-counts (agpu_genecount.hip)
 	// A pushed piece: copied on the context's stream (piece_copied: the caller's buffer is free), unwrapped and CRC-checked on a stream of its own (piece_stream; piece_ready: its
 	// bytes are in the stream, piece_done: the raw bytes are not needed any more), so that the copy of the next piece never waits for a kernel; AGPU_PIECE_SLOTS raw buffers in turn
 	hipStream_t piece_stream = nullptr, piece_stream2 = nullptr /* deflated pieces take the two in turn */; hipEvent_t piece_copied[AGPU_PIECE_SLOTS] = {}, piece_ready[AGPU_PIECE_SLOTS] = {}, piece_done[AGPU_PIECE_SLOTS] = {};

@@ -11,6 +11,7 @@
 #include <cstdint>
 #include "../../../include/arriba_host.h"
 #include "../device/sam_core.hpp"
+#include "../device/views.hpp"
 #include <cstdio>
 #include <functional>
 #include <map>
@@ -289,6 +290,12 @@ struct DepthContigs { std::vector<uint32_t> length; std::string names; std::vect
 void depth_contigs_of(const uint8_t* input, size_t size, DepthContigs& contigs);
 void depth_track(const uint8_t* records, uint64_t size, const ahost_depth_contigs& contigs, std::string& text, agpu_depth_stats& stats);
 std::string depth_line_text(const std::string& name, uint32_t start, uint32_t end, uint32_t depth);
+// --gene-counts on the host (gene_counts.cpp): arriba_amd/csrc/device/genecount_core.hpp stepped over records in host memory against the exon index, exon_gene and gene_bits of a
+// session (view: pointers into the session) -- the comparator of agpu_genecount.hip, and what --host-ingest and the CPU tier run; and the text of the file
+struct GeneCountAnnotation { agpu::AnnotationView view; };
+void gene_counts_of(const GeneCountAnnotation& annotation, const std::vector<uint32_t>& tid_to_contig, const std::vector<uint32_t>& ref_length, const uint8_t* records, uint64_t size, std::vector<uint64_t>& counts,
+                    agpu_gene_count_stats& stats); // counts: [3][n_genes + 4]
+std::string gene_counts_text(const std::vector<std::string>& gene_ids, const uint64_t* counts);
 const std::vector<uint8_t>& bam_feed_header_bytes(BamFeed* feed); // the head of the uncompressed input as the feed read it: the BAM header, or the '@' lines of SAM text
 
 // reference: source/read_chimeric_alignments.cpp:560-773 with separate_chimeric_bam_file=false, is_rna_bam_file=true

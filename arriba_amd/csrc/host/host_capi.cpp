@@ -874,6 +874,82 @@ int ahost_depth_file(const char* input_path, const char* path, agpu_depth_stats*
 	} catch (const std::exception& e) { g_error = e.what(); return -1; }
 }
 
+// ---- --gene-counts (include/arriba_host.h) ----
+namespace {
+thread_local std::string g_gene_count_text, g_gene_ids;
+GeneCountAnnotation gene_count_annotation(ahost_session* session) {
+	if (session->annotation.real_genes == 0) throw std::runtime_error("gene counts need the annotation of the session");
+	if (session->gene_bits.size() < session->annotation.real_genes || session->exon_gene.size() != session->annotation.exons.size()) throw std::runtime_error("gene counts: the views of the annotation are not built");
+	GeneCountAnnotation annotation; annotation.view = agpu::AnnotationView(); // (every pointer null)
+	agpu::AnnotationView& v = annotation.view;
+	v.n_genes = (uint32_t) session->annotation.real_genes; v.n_dummy = (uint32_t) (session->annotation.genes.size() - session->annotation.real_genes);
+	v.gene_bits = session->gene_bits.data(); v.n_exons = (uint32_t) session->exon_gene.size(); v.exon_gene = session->exon_gene.data();
+	const FlatIndex& index = session->exon_index;
+	v.exon_index.n_contigs = (uint32_t) index.n_contigs(); v.exon_index.contig_offset = index.contig_offset.data(); v.exon_index.keys = index.keys.data();
+	v.exon_index.member_offset = index.member_offset.data(); v.exon_index.members = index.members.data(); v.exon_index.bins = nullptr;
+	return annotation;
+}
+std::vector<std::string> gene_count_ids(ahost_session* session) {
+	std::vector<std::string> ids;
+	for (size_t g = 0; g < session->annotation.real_genes; ++g) ids.push_back(session->annotation.genes[g].gene_id);
+	return ids;
+}
+// the references of a header against the contigs of the session (which is not changed: a name it does not know gets no contig, and so no exon)
+void gene_count_references(ahost_session* session, const uint8_t* header, size_t size, std::vector<uint32_t>& tid_to_contig, std::vector<uint32_t>& ref_length) {
+	std::vector<std::string> names;
+	header_contigs(header, size, names, ref_length);
+	tid_to_contig.assign(names.size(), 0xFFFFFFFFu);
+	for (size_t t = 0; t < names.size(); ++t) { std::map<std::string, contig_t>::const_iterator known = session->contigs.by_name.find(remove_chr(names[t])); if (known != session->contigs.by_name.end()) tid_to_contig[t] = known->second; }
+}
+void gene_counts_checked(ahost_session* session, const uint64_t* counts, uint64_t n_counts) {
+	if (n_counts != 3 * ((uint64_t) session->annotation.real_genes + 4)) throw std::runtime_error("gene counts: the table has 3 x (n_genes + 4) numbers, n_genes = " + std::to_string(session->annotation.real_genes));
+}
+}
+int ahost_gene_counts_genes(ahost_session* session, uint32_t* n_genes, const char** ids, uint64_t* bytes) {
+	if (!session || !n_genes) { g_error = "null argument"; return -1; }
+	*n_genes = (uint32_t) session->annotation.real_genes;
+	g_gene_ids.clear();
+	for (size_t g = 0; g < session->annotation.real_genes; ++g) { g_gene_ids += session->annotation.genes[g].gene_id; g_gene_ids += '\n'; }
+	if (ids) *ids = g_gene_ids.data();
+	if (bytes) *bytes = g_gene_ids.size();
+	return 0;
+}
+int ahost_gene_counts_of(ahost_session* session, const void* input_header, size_t header_size, const void* records, size_t size, uint64_t* counts, uint64_t n_counts, agpu_gene_count_stats* stats) {
+	if (!session || (!input_header && header_size > 0) || (!records && size > 0) || !counts) { g_error = "null argument"; return -1; }
+	try {
+		gene_counts_checked(session, counts, n_counts);
+		std::vector<uint32_t> tid_to_contig, ref_length; std::vector<uint64_t> counted; agpu_gene_count_stats counted_stats;
+		gene_count_references(session, (const uint8_t*) input_header, header_size, tid_to_contig, ref_length);
+		gene_counts_of(gene_count_annotation(session), tid_to_contig, ref_length, (const uint8_t*) records, size, counted, counted_stats);
+		memcpy(counts, counted.data(), counted.size() * 8);
+		if (stats) *stats = counted_stats;
+		return 0;
+	} catch (const std::exception& e) { g_error = e.what(); return -1; }
+}
+int ahost_gene_counts_text(ahost_session* session, const uint64_t* counts, uint64_t n_counts, const char** text, uint64_t* bytes) {
+	if (!session || !counts || !text || !bytes) { g_error = "null argument"; return -1; }
+	try { gene_counts_checked(session, counts, n_counts); g_gene_count_text = gene_counts_text(gene_count_ids(session), counts); *text = g_gene_count_text.data(); *bytes = g_gene_count_text.size(); return 0; }
+	catch (const std::exception& e) { g_error = e.what(); return -1; }
+}
+int ahost_gene_counts_write(ahost_session* session, const uint64_t* counts, uint64_t n_counts, const char* path) {
+	if (!session || !counts || !path) { g_error = "null argument"; return -1; }
+	try { gene_counts_checked(session, counts, n_counts); virus_expression_write(gene_counts_text(gene_count_ids(session), counts), path); return 0; } // (the writer of a text through path.tmp)
+	catch (const std::exception& e) { g_error = e.what(); return -1; }
+}
+int ahost_gene_counts_file(ahost_session* session, const char* input_path, const char* path, agpu_gene_count_stats* stats) {
+	if (!session || !input_path || !path) { g_error = "null argument"; return -1; }
+	try {
+		std::vector<uint8_t> stream;
+		const uint64_t at = read_whole_bam(input_path, stream); // (SAM text comes out as the BAM stream of its alignments, behind a BAM header)
+		std::vector<uint32_t> tid_to_contig, ref_length; std::vector<uint64_t> counted; agpu_gene_count_stats counted_stats;
+		gene_count_references(session, stream.data(), at, tid_to_contig, ref_length);
+		gene_counts_of(gene_count_annotation(session), tid_to_contig, ref_length, stream.data() + at, stream.size() - at, counted, counted_stats);
+		virus_expression_write(gene_counts_text(gene_count_ids(session), counted.data()), path);
+		if (stats) *stats = counted_stats;
+		return 0;
+	} catch (const std::exception& e) { g_error = e.what(); return -1; }
+}
+
 void ahost_bam_close(ahost_session* session) { if (session && session->feed) { close_bam_feed(session->feed); session->feed = nullptr; } }
 
 int ahost_adopt_device_ingest(ahost_session* session, const agpu_ingest_result* result, const uint64_t* viral_read_counts, const uint16_t* coverage, const uint8_t* fragment_starts, const uint8_t* fragment_ends) {

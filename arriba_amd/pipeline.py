@@ -49,6 +49,13 @@ def markdup_counts_of(counts):
     return out
 
 
+def gene_count_stats_of(stats):
+    """agpu_gene_count_stats (the device's or the host's) as a dict"""
+    out = {name: int(getattr(stats, name)) for name in ("records", "templates", "without_primary", "ends", "blocks", "peak_bytes")}
+    out["seconds"] = dict(zip(("names", "assign"), stats.seconds))
+    return out
+
+
 class ArribaError(RuntimeError):
     pass
 
@@ -200,7 +207,7 @@ class WorkflowSession(object):
         if self._lib.arriba_workflow_sorted_bam_mark_duplicates(self._session, int(bool(on))) != 0:
             raise ArribaError(self._lib.arriba_workflow_last_error().decode())
 
-    def submit(self, bam, sorted_bam_file=None, supporting_alignments_prefix=None, sorted_bam_compression=None, virus_expression_file=None, coverage_file=None, mark_duplicates=None):
+    def submit(self, bam, sorted_bam_file=None, supporting_alignments_prefix=None, sorted_bam_compression=None, virus_expression_file=None, coverage_file=None, mark_duplicates=None, gene_counts_file=None):
         """the sample that comes after the one `sample` is called for next: its file is fed (PCIe, the front of read_chimeric_alignments) while the stages of that one run;
         sorted_bam_file: its records in coordinate order with their index (--sorted-bam), written when its ingest is finished; sorted_bam_compression: its level (None: as it is)"""
         if sorted_bam_compression is not None:
@@ -211,6 +218,7 @@ class WorkflowSession(object):
         self._lib.arriba_workflow_supporting_alignments(self._session, supporting_alignments_prefix.encode() if supporting_alignments_prefix else None)  # (--supporting-alignments: PREFIX_ID.bam per row of its fusions file)
         self._lib.arriba_workflow_virus_expression(self._session, virus_expression_file.encode() if virus_expression_file else None)  # (--virus-expression: its table, written when its ingest is finished)
         self._lib.arriba_workflow_coverage(self._session, coverage_file.encode() if coverage_file else None)  # (--coverage: its depth track, written when its ingest is finished)
+        self._lib.arriba_workflow_gene_counts(self._session, gene_counts_file.encode() if gene_counts_file else None)  # (--gene-counts: its reads per gene, likewise)
         if self._lib.arriba_workflow_submit(self._session, bam.encode()) != 0:
             raise ArribaError(self._lib.arriba_workflow_last_error().decode())
         if self._profiling_on:
@@ -305,7 +313,7 @@ class WorkflowSession(object):
     def _lane_contexts(self):
         return [ctx for ctx in (self._lib.arriba_workflow_lane_device(self._session, lane) for lane in (0, 1)) if ctx]
 
-    def sample(self, bam, output_file, discarded_output_file=None, sorted_bam_file=None, supporting_alignments_prefix=None, sorted_bam_compression=None, virus_expression_file=None, coverage_file=None, mark_duplicates=None):
+    def sample(self, bam, output_file, discarded_output_file=None, sorted_bam_file=None, supporting_alignments_prefix=None, sorted_bam_compression=None, virus_expression_file=None, coverage_file=None, mark_duplicates=None, gene_counts_file=None):
         """one sample, BAM file -> fusions.tsv (and discarded.tsv); returns the stages with their "(remaining=N)" counts.  sorted_bam_file (--sorted-bam): for a sample that was
         not submitted ahead; one that was says it to `submit`"""
         report, timing = _capi.WorkflowReport(), _capi.WorkflowTiming()
@@ -321,6 +329,8 @@ class WorkflowSession(object):
             self._lib.arriba_workflow_virus_expression(self._session, virus_expression_file.encode())
         if coverage_file:  # (likewise)
             self._lib.arriba_workflow_coverage(self._session, coverage_file.encode())
+        if gene_counts_file:  # (likewise)
+            self._lib.arriba_workflow_gene_counts(self._session, gene_counts_file.encode())
         if self._lib.arriba_workflow_sample(self._session, bam.encode(), output_file.encode(), discarded_output_file.encode() if discarded_output_file else None, byref(report), byref(timing)) != 0:
             raise ArribaError(self._lib.arriba_workflow_last_error().decode())
         self.ctx = self._lib.arriba_workflow_device(self._session)  # (the lane that worked on this sample)
@@ -695,6 +705,34 @@ class DevicePipeline(object):
             raise
         return depth_stats_of(stats)
 
+    def gene_counts(self):
+        """--gene-counts: reads per gene of the records of the last read_chimeric_alignments, counted on the device from the record stream that is still in HBM (agpu_gene_counts;
+        DESIGN.md 4.15).  Valid after read_chimeric_alignments and before the next one.  Returns (counts, stats): counts[c][row], a uint64 array of shape (3, n_genes + 4) -- rows 0 .. 3
+        are N_unmapped, N_multimapping, N_noFeature, N_ambiguous, row 4 + g is gene g of the session's table --, and {"records", "templates", "without_primary", "ends", "blocks",
+        "peak_bytes", "seconds"}."""
+        if not self.device_ingest or not hasattr(self.api, "gene_counts"):
+            raise ArribaError("ERROR: gene counts need the record stream of an ingest on the device (DevicePipeline(bam=...))")
+        lib, handle = self.session._lib, self.session._session
+        contigs, n_genes = _capi.DepthContigs(), ctypes.c_uint32()
+        if lib.ahost_depth_contigs_of_session(handle, byref(contigs)) != 0 or lib.ahost_gene_counts_genes(handle, byref(n_genes), None, None) != 0:
+            raise ArribaError("ERROR: " + lib.ahost_last_error().decode())
+        counts, stats = np.zeros((3, n_genes.value + 4), dtype=np.uint64), _capi.GeneCountStats()
+        self._check(self.api.gene_counts(self.ctx, contigs.length, contigs.n_ref, counts.ctypes.data, byref(stats)))
+        return counts, gene_count_stats_of(stats)
+
+    def write_gene_counts(self, path):
+        """--gene-counts: the table of `gene_counts` as the text of STAR's ReadsPerGene.out.tab, written through `path`.tmp; returns the statistics"""
+        lib, handle = self.session._lib, self.session._session
+        counts, stats = self.gene_counts()  # (refused before anything is written)
+        if lib.ahost_gene_counts_write(handle, counts.ctypes.data, counts.size, path.encode()) != 0:
+            raise ArribaError("ERROR: " + lib.ahost_last_error().decode())
+        return stats
+
+    def gene_counts_allocated_bytes(self):
+        count = c_uint64()
+        self._check(self.api.gene_counts_allocated_bytes(self.ctx, byref(count)))
+        return int(count.value)
+
     def _free_depth_windows(self):
         if getattr(self, "_depth_windows", None) is not None:
             for buffer in self._depth_windows[1]:
@@ -971,7 +1009,7 @@ class DevicePipeline(object):
                      max_genomic_breakpoint_distance=100000, strandedness=None, evalue_cutoff=0.3,
                      min_itd_support=10, min_itd_allele_fraction=0.07, high_expression_quantile=0.998, min_spliced_events=4, min_anchor_length=23,
                      max_homolog_identity=0.3, max_itd_length=100, fill_sequence_gaps=False, top_viral_contigs=5, viral_contig_min_covered_fraction=0.05,
-                     print_extra_info_for_discarded_fusions=False, log=None, sorted_bam_file=None, supporting_alignments_prefix=None, supporting_alignments_window=1000000, virus_expression_file=None, coverage_file=None, mark_duplicates=False):
+                     print_extra_info_for_discarded_fusions=False, log=None, sorted_bam_file=None, supporting_alignments_prefix=None, supporting_alignments_window=1000000, virus_expression_file=None, coverage_file=None, mark_duplicates=False, gene_counts_file=None):
         """The reference's main() behind read_chimeric_alignments (source/arriba.cpp:119-610) with its default parameters: the read-level cascade, find_fusions,
         every candidate-level filter in the reference's order, assign_confidence, and the two output files.  `log` receives (stage, remaining) pairs --
         the numbers the reference prints as "(remaining=N)".  Filters switched off with -f are skipped by the stages themselves (agpu_params.filter_enabled)."""
@@ -984,6 +1022,8 @@ class DevicePipeline(object):
             self.write_virus_expression(virus_expression_file)
         if coverage_file:  # (--coverage: likewise)
             self.write_coverage(coverage_file)
+        if gene_counts_file:  # (--gene-counts: likewise)
+            self.write_gene_counts(gene_counts_file)
         if supporting_alignments_prefix:  # (--supporting-alignments, phase 1: the records of the names of the batch leave the stream while it is there)
             self.build_support_pool()
         self.run_read_level(strandedness, top_viral_contigs, viral_contig_min_covered_fraction)

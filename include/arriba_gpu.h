@@ -459,6 +459,26 @@ typedef struct {
 int agpu_sorted_bam_set_mark_duplicates(agpu_ctx* ctx, int on);
 int agpu_markdup_stats(agpu_ctx* ctx, agpu_markdup_counts* counts);
 int agpu_markdup_allocated_bytes(agpu_ctx* ctx, uint64_t* bytes);
+/* --gene-counts: reads per gene of the records of the last ingest, the numbers of STAR's ReadsPerGene.out.tab (htseq-count -m union with -s no / yes / reverse), counted on the device
+ * while the stream is in HBM (arriba_amd/csrc/device/agpu_genecount.hip, genecount_core.hpp).
+ *   agpu_gene_counts   behind agpu_ingest_finish, before the next agpu_ingest_begin on this context or its sibling (the refusals of agpu_depth_begin).  ref_length: LN of every
+ *                      reference of the header of that ingest (n_ref of them: ahost_depth_contigs_of_session), to which blocks are clipped.  counts[c * (n_genes + 4) + row],
+ *                      c < 3 (unstranded, read strand = gene strand, read strand != gene strand): rows 0 .. 3 are N_unmapped, N_multimapping, N_noFeature, N_ambiguous, row 4 + g is
+ *                      gene g of the annotation uploaded last (n_genes: its GTF genes).  The "genecount.*" buffers are freed before the call returns.
+ *   agpu_gene_counts_allocated_bytes   of those buffers: 0 outside the call
+ * ARRIBA_GENECOUNT_HASH_BITS (a test knob): the low bits of the hash of a read name that are kept.  ARRIBA_GENECOUNT_PLAIN_ATOMICS=1 (a measuring knob): one atomic per lane for the
+ * gene rows instead of one per wavefront and gene. */
+typedef struct {
+	uint64_t records;              /* of the stream */
+	uint64_t templates;            /* distinct read names */
+	uint64_t without_primary;      /* templates that have no primary record: counted nowhere in the table */
+	uint64_t ends;                 /* mapped ends of the other templates */
+	uint64_t blocks;               /* blocks of the ends of the templates that are neither unmapped nor multimapping */
+	uint64_t peak_bytes;           /* of the "genecount.*" buffers (0 on the host) */
+	double seconds[2];             /* name ids and claims; the rows and the adds (device: from HIP events, 0 on the host) */
+} agpu_gene_count_stats;
+int agpu_gene_counts(agpu_ctx* ctx, const uint32_t* ref_length, uint32_t n_ref, uint64_t* counts /* [3][n_genes + 4] */, agpu_gene_count_stats* stats /* may be NULL */);
+int agpu_gene_counts_allocated_bytes(agpu_ctx* ctx, uint64_t* bytes);
 /* what the host's sequential stages and its output writer need from a batch that lives on the device:
  *   agpu_get_viral_read_counts   mapped_viral_reads_by_contig (source/read_chimeric_alignments.cpp:735-739)
  *   agpu_get_coverage            coverage_t as the reference holds it (16-bit saturating windows, start/end flags); sizes by coverage_window_offset

@@ -174,6 +174,22 @@ int ahost_depth_track(const void* records, size_t size, const ahost_depth_contig
 int ahost_depth_line(const char* name, uint32_t start, uint32_t end, uint32_t depth, char* out, uint32_t capacity, uint32_t* bytes);
 int ahost_depth_write(const void* text, uint64_t bytes, const char* path);
 int ahost_depth_file(const char* input_path, const char* path, agpu_depth_stats* stats);
+/* ---- --gene-counts: the host side of agpu_gene_counts (include/arriba_gpu.h) -- reads per gene in three columns, the file STAR writes as ReadsPerGene.out.tab (the rule: DESIGN.md
+ * 4.15).  A table is counts[c * (n_genes + 4) + row] as agpu_gene_counts fills it; n_counts = 3 * (n_genes + 4) is checked against the session ----
+ *   ahost_gene_counts_genes   n_genes of the session's gene table (its GTF genes) and their gene_ids as loaded, each followed by "\n", in table order (ids, bytes: may be NULL; valid
+ *                             until the next call on the thread)
+ *   ahost_gene_counts_of      arriba_amd/csrc/device/genecount_core.hpp stepped on the host over BAM records in host memory (the device's comparator; the CPU tier).  input_header:
+ *                             the head of the input the records come from (a BAM header, or the '@' lines of SAM text): its references are looked up among the contigs of the
+ *                             session by name, their LN clips the blocks
+ *   ahost_gene_counts_text    a table and the session's gene ids -> the text of the file: N_unmapped, N_multimapping, N_noFeature, N_ambiguous, then ID\tc0\tc1\tc2\n per gene; valid
+ *                             until the next call on the thread
+ *   ahost_gene_counts_write   that text into `path`, through path.tmp; on a failure nothing is left behind
+ *   ahost_gene_counts_file    all of it for a file (BAM in BGZF, gzip or raw; SAM text): what --host-ingest runs; stats may be NULL */
+int ahost_gene_counts_genes(ahost_session* session, uint32_t* n_genes, const char** ids, uint64_t* bytes);
+int ahost_gene_counts_of(ahost_session* session, const void* input_header, size_t header_size, const void* records, size_t size, uint64_t* counts, uint64_t n_counts, agpu_gene_count_stats* stats /* may be NULL */);
+int ahost_gene_counts_text(ahost_session* session, const uint64_t* counts, uint64_t n_counts, const char** text, uint64_t* bytes);
+int ahost_gene_counts_write(ahost_session* session, const uint64_t* counts, uint64_t n_counts, const char* path);
+int ahost_gene_counts_file(ahost_session* session, const char* input_path, const char* path, agpu_gene_count_stats* stats);
 int ahost_adopt_device_ingest(ahost_session* session, const agpu_ingest_result* result, const uint64_t* viral_read_counts, const uint16_t* coverage, const uint8_t* fragment_starts, const uint8_t* fragment_ends);
 int ahost_set_batch_rows(ahost_session* session, const agpu_batch_rows* rows, const uint32_t* fragments /* [rows->n] ascending: the fragment every row holds; NULL: row k holds the fragment
                          of entry k of the read lists of the table the next ahost_write_fusions writes (the reads of a candidate next to each other; the table then carries read_filter_of_rows) */);

@@ -69,6 +69,11 @@ typedef struct {
 	                                         stream in HBM (include/arriba_gpu.h: agpu_sorted_bam_set_mark_duplicates; with host_ingest: the same code stepped on the host).
 	                                         Refused without sorted_bam_file and together with device.external_duplicate_marking (-u).  Fusion calling does not see the marks; the files of
 	                                         supporting_alignments_prefix keep the flags of the input. */
+	const char* gene_counts_file;         /* --gene-counts; NULL (and a zero-initialised struct) = none.  Reads per gene of the records of chimeric_bam_file in three columns (unstranded, read
+	                                         strand = gene strand, read strand != gene strand) behind N_unmapped, N_multimapping, N_noFeature and N_ambiguous -- the file STAR writes as
+	                                         ReadsPerGene.out.tab, htseq-count -m union with -s no / yes / reverse --, counted behind read_chimeric_alignments from the record stream in HBM
+	                                         (include/arriba_gpu.h: agpu_gene_counts; with host_ingest: the same code stepped on the host).  Of arriba_workflow_run's sample;
+	                                         the samples of a session say theirs with arriba_workflow_gene_counts.  Not for one sample over several ranks. */
 } arriba_workflow_options;
 
 /* what the reference prints as "(remaining=N)" / "(total=N)" / "(marked=N)", in the order of the stages; stage names as in the reference's source */
@@ -110,6 +115,7 @@ typedef struct { /* seconds of one sample, by part (wall clock of the calling th
 	double supporting_alignments; /* --supporting-alignments: the pool behind the ingest (name table, marks, compaction) and the files behind fusions.tsv (join, gather, copy back, files, indexes) */
 	double virus_expression; /* --virus-expression: scan, candidates, k-mer sets, copies, the table (inside `ingest`; beside the sample in front when the ingest was finished ahead) */
 	double coverage;         /* --coverage: marks, scan, runs, text, copies, the file (inside `ingest`; beside the sample in front when the ingest was finished ahead) */
+	double gene_counts;      /* --gene-counts: name ids and claims, rows and adds, the copy, the file (inside `ingest`; beside the sample in front when the ingest was finished ahead) */
 } arriba_workflow_timing;
 /* options->chimeric_bam_file, output_file and discarded_output_file are not used by open (they belong to a sample); NULL + arriba_workflow_last_error() on failure */
 arriba_workflow_session* arriba_workflow_open(const arriba_workflow_options* options);
@@ -138,6 +144,8 @@ int arriba_workflow_supporting_alignments(arriba_workflow_session* session, cons
 int arriba_workflow_virus_expression(arriba_workflow_session* session, const char* path);
 /* --coverage of the sample that is submitted NEXT, in the same way; NULL: none.  The track is written by the thread that finishes its ingest. */
 int arriba_workflow_coverage(arriba_workflow_session* session, const char* path);
+/* --gene-counts of the sample that is submitted NEXT, in the same way; NULL: none.  The table is written by the thread that finishes its ingest. */
+int arriba_workflow_gene_counts(arriba_workflow_session* session, const char* path);
 /* (If the device runs out of memory while two samples are in flight, arriba_workflow_sample throws away what was fed ahead, closes the second lane, runs its sample again with the device
  * to itself and submits the other sample again behind it -- once; a sample that does not fit the device alone fails the call.  INTEGRATION.md, "Memory".) */
 /* on: arriba_workflow_sample returns when the last output file of the sample (-O if given, else -o) has everything it needs off the device; the file is formatted and written
