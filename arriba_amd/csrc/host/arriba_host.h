@@ -296,6 +296,13 @@ struct GeneCountAnnotation { agpu::AnnotationView view; };
 void gene_counts_of(const GeneCountAnnotation& annotation, const std::vector<uint32_t>& tid_to_contig, const std::vector<uint32_t>& ref_length, const uint8_t* records, uint64_t size, std::vector<uint64_t>& counts,
                     agpu_gene_count_stats& stats); // counts: [3][n_genes + 4]
 std::string gene_counts_text(const std::vector<std::string>& gene_ids, const uint64_t* counts);
+// --splice-junctions on the host (splice_junctions.cpp): arriba_amd/csrc/device/junction_core.hpp stepped over records in host memory against the exon chains, gene_contig and
+// gene_bits and the assembly of a session (view, genome: pointers into the session) -- the comparator of agpu_junctions.hip, and what --host-ingest and the CPU tier run; and the
+// text of the file from a row table, the host's or the device's
+struct JunctionReferences { agpu::AnnotationView view; agpu::GenomeView genome; };
+void splice_junctions_of(const JunctionReferences& references, const std::vector<uint32_t>& tid_to_contig, const std::vector<uint32_t>& ref_length, const uint8_t* records, uint64_t size, std::vector<agpu_junction_row>& rows,
+                         agpu_junction_stats& stats);
+std::string splice_junctions_text(const ahost_depth_contigs& contigs, const agpu_junction_row* rows, uint64_t n_rows);
 const std::vector<uint8_t>& bam_feed_header_bytes(BamFeed* feed); // the head of the uncompressed input as the feed read it: the BAM header, or the '@' lines of SAM text
 
 // reference: source/read_chimeric_alignments.cpp:560-773 with separate_chimeric_bam_file=false, is_rna_bam_file=true

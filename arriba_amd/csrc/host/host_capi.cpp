@@ -950,6 +950,63 @@ int ahost_gene_counts_file(ahost_session* session, const char* input_path, const
 	} catch (const std::exception& e) { g_error = e.what(); return -1; }
 }
 
+// ---- --splice-junctions (include/arriba_host.h) ----
+namespace {
+thread_local std::vector<agpu_junction_row> g_junction_rows; thread_local std::string g_junction_text;
+JunctionReferences junction_references(ahost_session* session) {
+	if (session->gene_bits.size() < session->annotation.real_genes || session->gene_contig.size() < session->annotation.real_genes || session->exon_gene.size() != session->annotation.exons.size()
+	    || session->exon_next.size() != session->annotation.exons.size()) throw std::runtime_error("splice junctions: the views of the annotation are not built");
+	JunctionReferences references; references.view = agpu::AnnotationView(); // (every pointer null)
+	agpu::AnnotationView& v = references.view;
+	v.n_genes = (uint32_t) session->annotation.real_genes; v.n_dummy = (uint32_t) (session->annotation.genes.size() - session->annotation.real_genes);
+	v.gene_bits = session->gene_bits.data(); v.gene_contig = session->gene_contig.data();
+	v.n_exons = (uint32_t) session->exon_gene.size(); v.exon_gene = session->exon_gene.data(); v.exon_start = session->exon_start.data(); v.exon_end = session->exon_end.data(); v.exon_next = session->exon_next.data();
+	// the assembly as the genome view holds it: the contigs the view was built with (a contig the session learnt of later has no bases)
+	agpu::GenomeView& g = references.genome;
+	g.n_contigs = session->genome_offset.empty() ? 0 : (uint32_t) (session->genome_offset.size() - 1); g.contig_offset = session->genome_offset.data(); g.contig_bits = session->contig_bits.data(); g.bases = session->genome_bases.data();
+	return references;
+}
+void splice_junctions_with_header(ahost_session* session, const uint8_t* header, size_t header_size, const uint8_t* records, size_t size, std::vector<agpu_junction_row>& rows, agpu_junction_stats& stats) {
+	std::vector<uint32_t> tid_to_contig, ref_length;
+	gene_count_references(session, header, header_size, tid_to_contig, ref_length);
+	splice_junctions_of(junction_references(session), tid_to_contig, ref_length, records, size, rows, stats);
+}
+}
+int ahost_splice_junctions_of(ahost_session* session, const void* input_header, size_t header_size, const void* records, size_t size, const agpu_junction_row** rows, uint64_t* n_rows, agpu_junction_stats* stats) {
+	if (!session || (!input_header && header_size > 0) || (!records && size > 0) || !rows || !n_rows) { g_error = "null argument"; return -1; }
+	try {
+		agpu_junction_stats counted;
+		splice_junctions_with_header(session, (const uint8_t*) input_header, header_size, (const uint8_t*) records, size, g_junction_rows, counted);
+		*rows = g_junction_rows.data(); *n_rows = g_junction_rows.size();
+		if (stats) *stats = counted;
+		return 0;
+	} catch (const std::exception& e) { g_error = e.what(); return -1; }
+}
+int ahost_splice_junctions_text(const ahost_depth_contigs* contigs, const agpu_junction_row* rows, uint64_t n_rows, const char** text, uint64_t* bytes) {
+	if (!contigs || (!rows && n_rows > 0) || !text || !bytes) { g_error = "null argument"; return -1; }
+	try { g_junction_text = splice_junctions_text(*contigs, rows, n_rows); *text = g_junction_text.data(); *bytes = g_junction_text.size(); return 0; }
+	catch (const std::exception& e) { g_error = e.what(); return -1; }
+}
+int ahost_splice_junctions_write(const ahost_depth_contigs* contigs, const agpu_junction_row* rows, uint64_t n_rows, const char* path) {
+	if (!contigs || (!rows && n_rows > 0) || !path) { g_error = "null argument"; return -1; }
+	try { virus_expression_write(splice_junctions_text(*contigs, rows, n_rows), path); return 0; } // (the writer of a text through path.tmp)
+	catch (const std::exception& e) { g_error = e.what(); return -1; }
+}
+int ahost_splice_junctions_file(ahost_session* session, const char* input_path, const char* path, agpu_junction_stats* stats) {
+	if (!session || !input_path || !path) { g_error = "null argument"; return -1; }
+	try {
+		std::vector<uint8_t> stream;
+		const uint64_t at = read_whole_bam(input_path, stream); // (SAM text comes out as the BAM stream of its alignments, behind a BAM header)
+		std::vector<agpu_junction_row> rows; agpu_junction_stats counted;
+		splice_junctions_with_header(session, stream.data(), at, stream.data() + at, stream.size() - at, rows, counted);
+		DepthContigs contigs;
+		depth_contigs_of(stream.data(), at, contigs);
+		virus_expression_write(splice_junctions_text(contigs.view(), rows.data(), rows.size()), path);
+		if (stats) *stats = counted;
+		return 0;
+	} catch (const std::exception& e) { g_error = e.what(); return -1; }
+}
+
 void ahost_bam_close(ahost_session* session) { if (session && session->feed) { close_bam_feed(session->feed); session->feed = nullptr; } }
 
 int ahost_adopt_device_ingest(ahost_session* session, const agpu_ingest_result* result, const uint64_t* viral_read_counts, const uint16_t* coverage, const uint8_t* fragment_starts, const uint8_t* fragment_ends) {

@@ -73,7 +73,9 @@ void usage() {
 	             " --mark-duplicates  the records of --sorted-bam leave with flag 0x400 set on duplicate templates and cleared on all others (what samtools markdup or Picard make of the sorted\n"
 	             "                    file: one library, no optical duplicates, no UMIs); not together with -u, whose input marks it would overwrite\n"
 	             " --gene-counts FILE  reads per gene of -x in three columns (unstranded, read strand = gene strand, the reverse) behind N_unmapped, N_multimapping, N_noFeature and\n"
-	             "                    N_ambiguous: STAR's ReadsPerGene.out.tab, htseq-count -m union with -s no / yes / reverse\n";
+	             "                    N_ambiguous: STAR's ReadsPerGene.out.tab, htseq-count -m union with -s no / yes / reverse\n"
+	             " --splice-junctions FILE  the splice junctions of -x, a line per junction: contig, first and last base of the intron, strand, intron motif, annotated, uniquely and\n"
+	             "                    multiply mapping templates that cross it, maximum overhang: STAR's SJ.out.tab\n";
 }
 
 }
@@ -107,6 +109,7 @@ int main(int argc, char** argv) {
 		else if (strcmp(argv[a], "--mark-duplicates") == 0) options.mark_duplicates = 1;
 		else if (strcmp(argv[a], "--coverage") == 0 && a + 1 < argc) { options.coverage_file = argv[++a]; parent_exists(options.coverage_file); }
 		else if (strcmp(argv[a], "--gene-counts") == 0 && a + 1 < argc) { options.gene_counts_file = argv[++a]; parent_exists(options.gene_counts_file); }
+		else if (strcmp(argv[a], "--splice-junctions") == 0 && a + 1 < argc) { options.splice_junctions_file = argv[++a]; parent_exists(options.splice_junctions_file); }
 		else if (strcmp(argv[a], "--supporting-window") == 0 && a + 1 < argc) { long window; require(parse_int(argv[++a], window) && window > 0 && window <= 0x7FFFFFFFl, "invalid argument to --supporting-window"); options.supporting_alignments_window = window; }
 		else if (strcmp(argv[a], "--device") == 0 && a + 1 < argc) { long device; require(parse_int(argv[++a], device) && device >= 0, "invalid argument to --device"); options.device_index = (int) device; }
 		else arguments.push_back(argv[a]);

@@ -56,6 +56,13 @@ def gene_count_stats_of(stats):
     return out
 
 
+def junction_stats_of(stats):
+    """agpu_junction_stats (the device's or the host's) as a dict"""
+    out = {name: int(getattr(stats, name)) for name in ("records", "contributing", "crossings", "pairs", "junctions", "annotated", "peak_bytes")}
+    out["seconds"] = dict(zip(("count", "names", "emit", "order", "classify"), stats.seconds))
+    return out
+
+
 class ArribaError(RuntimeError):
     pass
 
@@ -207,7 +214,7 @@ class WorkflowSession(object):
         if self._lib.arriba_workflow_sorted_bam_mark_duplicates(self._session, int(bool(on))) != 0:
             raise ArribaError(self._lib.arriba_workflow_last_error().decode())
 
-    def submit(self, bam, sorted_bam_file=None, supporting_alignments_prefix=None, sorted_bam_compression=None, virus_expression_file=None, coverage_file=None, mark_duplicates=None, gene_counts_file=None):
+    def submit(self, bam, sorted_bam_file=None, supporting_alignments_prefix=None, sorted_bam_compression=None, virus_expression_file=None, coverage_file=None, mark_duplicates=None, gene_counts_file=None, splice_junctions_file=None):
         """the sample that comes after the one `sample` is called for next: its file is fed (PCIe, the front of read_chimeric_alignments) while the stages of that one run;
         sorted_bam_file: its records in coordinate order with their index (--sorted-bam), written when its ingest is finished; sorted_bam_compression: its level (None: as it is)"""
         if sorted_bam_compression is not None:
@@ -219,6 +226,7 @@ class WorkflowSession(object):
         self._lib.arriba_workflow_virus_expression(self._session, virus_expression_file.encode() if virus_expression_file else None)  # (--virus-expression: its table, written when its ingest is finished)
         self._lib.arriba_workflow_coverage(self._session, coverage_file.encode() if coverage_file else None)  # (--coverage: its depth track, written when its ingest is finished)
         self._lib.arriba_workflow_gene_counts(self._session, gene_counts_file.encode() if gene_counts_file else None)  # (--gene-counts: its reads per gene, likewise)
+        self._lib.arriba_workflow_splice_junctions(self._session, splice_junctions_file.encode() if splice_junctions_file else None)  # (--splice-junctions: its junction table, likewise)
         if self._lib.arriba_workflow_submit(self._session, bam.encode()) != 0:
             raise ArribaError(self._lib.arriba_workflow_last_error().decode())
         if self._profiling_on:
@@ -313,7 +321,7 @@ class WorkflowSession(object):
     def _lane_contexts(self):
         return [ctx for ctx in (self._lib.arriba_workflow_lane_device(self._session, lane) for lane in (0, 1)) if ctx]
 
-    def sample(self, bam, output_file, discarded_output_file=None, sorted_bam_file=None, supporting_alignments_prefix=None, sorted_bam_compression=None, virus_expression_file=None, coverage_file=None, mark_duplicates=None, gene_counts_file=None):
+    def sample(self, bam, output_file, discarded_output_file=None, sorted_bam_file=None, supporting_alignments_prefix=None, sorted_bam_compression=None, virus_expression_file=None, coverage_file=None, mark_duplicates=None, gene_counts_file=None, splice_junctions_file=None):
         """one sample, BAM file -> fusions.tsv (and discarded.tsv); returns the stages with their "(remaining=N)" counts.  sorted_bam_file (--sorted-bam): for a sample that was
         not submitted ahead; one that was says it to `submit`"""
         report, timing = _capi.WorkflowReport(), _capi.WorkflowTiming()
@@ -331,6 +339,8 @@ class WorkflowSession(object):
             self._lib.arriba_workflow_coverage(self._session, coverage_file.encode())
         if gene_counts_file:  # (likewise)
             self._lib.arriba_workflow_gene_counts(self._session, gene_counts_file.encode())
+        if splice_junctions_file:  # (likewise)
+            self._lib.arriba_workflow_splice_junctions(self._session, splice_junctions_file.encode())
         if self._lib.arriba_workflow_sample(self._session, bam.encode(), output_file.encode(), discarded_output_file.encode() if discarded_output_file else None, byref(report), byref(timing)) != 0:
             raise ArribaError(self._lib.arriba_workflow_last_error().decode())
         self.ctx = self._lib.arriba_workflow_device(self._session)  # (the lane that worked on this sample)
@@ -733,6 +743,37 @@ class DevicePipeline(object):
         self._check(self.api.gene_counts_allocated_bytes(self.ctx, byref(count)))
         return int(count.value)
 
+    def splice_junctions(self):
+        """--splice-junctions: the splice junctions of the records of the last read_chimeric_alignments, made on the device from the record stream that is still in HBM
+        (agpu_splice_junctions).  Valid after read_chimeric_alignments and before the next one.  Returns (rows, stats): rows a ctypes array of _capi.JunctionRow (a copy),
+        ordered by (ref, start, end), and {"records", "contributing", "crossings", "pairs", "junctions", "annotated", "peak_bytes", "seconds"}."""
+        if not self.device_ingest or not hasattr(self.api, "splice_junctions"):
+            raise ArribaError("ERROR: splice junctions need the record stream of an ingest on the device (DevicePipeline(bam=...))")
+        lib, handle = self.session._lib, self.session._session
+        contigs = _capi.DepthContigs()
+        if lib.ahost_depth_contigs_of_session(handle, byref(contigs)) != 0:
+            raise ArribaError("ERROR: " + lib.ahost_last_error().decode())
+        rows, n_rows, stats = ctypes.POINTER(_capi.JunctionRow)(), c_uint64(), _capi.JunctionStats()
+        self._check(self.api.splice_junctions(self.ctx, contigs.length, contigs.n_ref, byref(rows), byref(n_rows), byref(stats)))
+        copy = (_capi.JunctionRow * n_rows.value)()
+        if n_rows.value:
+            ctypes.memmove(copy, rows, ctypes.sizeof(copy))
+        return copy, junction_stats_of(stats)
+
+    def write_splice_junctions(self, path):
+        """--splice-junctions: the rows of `splice_junctions` as the text of STAR's SJ.out.tab, written through `path`.tmp; returns the statistics"""
+        lib, handle = self.session._lib, self.session._session
+        rows, stats = self.splice_junctions()  # (refused before anything is written)
+        contigs = _capi.DepthContigs()
+        if lib.ahost_depth_contigs_of_session(handle, byref(contigs)) != 0 or lib.ahost_splice_junctions_write(byref(contigs), rows, len(rows), path.encode()) != 0:
+            raise ArribaError("ERROR: " + lib.ahost_last_error().decode())
+        return stats
+
+    def splice_junctions_allocated_bytes(self):
+        count = c_uint64()
+        self._check(self.api.splice_junctions_allocated_bytes(self.ctx, byref(count)))
+        return int(count.value)
+
     def _free_depth_windows(self):
         if getattr(self, "_depth_windows", None) is not None:
             for buffer in self._depth_windows[1]:
@@ -1009,7 +1050,7 @@ class DevicePipeline(object):
                      max_genomic_breakpoint_distance=100000, strandedness=None, evalue_cutoff=0.3,
                      min_itd_support=10, min_itd_allele_fraction=0.07, high_expression_quantile=0.998, min_spliced_events=4, min_anchor_length=23,
                      max_homolog_identity=0.3, max_itd_length=100, fill_sequence_gaps=False, top_viral_contigs=5, viral_contig_min_covered_fraction=0.05,
-                     print_extra_info_for_discarded_fusions=False, log=None, sorted_bam_file=None, supporting_alignments_prefix=None, supporting_alignments_window=1000000, virus_expression_file=None, coverage_file=None, mark_duplicates=False, gene_counts_file=None):
+                     print_extra_info_for_discarded_fusions=False, log=None, sorted_bam_file=None, supporting_alignments_prefix=None, supporting_alignments_window=1000000, virus_expression_file=None, coverage_file=None, mark_duplicates=False, gene_counts_file=None, splice_junctions_file=None):
         """The reference's main() behind read_chimeric_alignments (source/arriba.cpp:119-610) with its default parameters: the read-level cascade, find_fusions,
         every candidate-level filter in the reference's order, assign_confidence, and the two output files.  `log` receives (stage, remaining) pairs --
         the numbers the reference prints as "(remaining=N)".  Filters switched off with -f are skipped by the stages themselves (agpu_params.filter_enabled)."""
@@ -1024,6 +1065,8 @@ class DevicePipeline(object):
             self.write_coverage(coverage_file)
         if gene_counts_file:  # (--gene-counts: likewise)
             self.write_gene_counts(gene_counts_file)
+        if splice_junctions_file:  # (--splice-junctions: likewise)
+            self.write_splice_junctions(splice_junctions_file)
         if supporting_alignments_prefix:  # (--supporting-alignments, phase 1: the records of the names of the batch leave the stream while it is there)
             self.build_support_pool()
         self.run_read_level(strandedness, top_viral_contigs, viral_contig_min_covered_fraction)

@@ -479,6 +479,37 @@ typedef struct {
 } agpu_gene_count_stats;
 int agpu_gene_counts(agpu_ctx* ctx, const uint32_t* ref_length, uint32_t n_ref, uint64_t* counts /* [3][n_genes + 4] */, agpu_gene_count_stats* stats /* may be NULL */);
 int agpu_gene_counts_allocated_bytes(agpu_ctx* ctx, uint64_t* bytes);
+/* --splice-junctions: the splice junctions of the records of the last ingest, the rows of STAR's SJ.out.tab, made on the device while the stream is in HBM (DESIGN.md 4.16;
+ * arriba_amd/csrc/device/agpu_junctions.hip, junction_core.hpp).
+ *   agpu_splice_junctions   behind agpu_ingest_finish, before the next agpu_ingest_begin on this context or its sibling (the refusals of agpu_gene_counts, and the genome must be
+ *                           uploaded: the motif is read from it).  ref_length: LN of every reference of the header of that ingest (n_ref of them: ahost_depth_contigs_of_session).
+ *                           rows: one per junction that at least one template crosses, ordered by (ref, start, end); they belong to the context and are valid until the next call
+ *                           on it.  The "junction.*" buffers are freed before the call returns.
+ *   agpu_splice_junctions_allocated_bytes   of those buffers: 0 outside the call
+ * ARRIBA_JUNCTION_HASH_BITS (a test knob): the low bits of the hash of a read name that are kept. */
+typedef struct {
+	uint32_t ref;                  /* index of the reference in the header */
+	int32_t start, end;            /* the intron, 0-based inclusive (the file prints both + 1) */
+	uint8_t strand;                /* 0: undefined, 1: +, 2: - */
+	uint8_t motif;                 /* 0: none of them, 1: GT/AG, 2: CT/AC, 3: GC/AG, 4: CT/GC, 5: AT/AC, 6: GT/AT */
+	uint8_t annotated;             /* 1: an exon and its next exon in the annotation leave exactly this intron between them */
+	uint8_t reserved;
+	uint32_t unique;               /* templates that cross it, none of whose crossings is multimapping (NH > 1) */
+	uint32_t multimapping;         /* the other templates that cross it */
+	uint32_t overhang;             /* the largest min(left, right) of M / = / X bases beside it over all crossings */
+} agpu_junction_row;
+typedef struct {
+	uint64_t records;              /* of the stream */
+	uint64_t contributing;         /* mapped, on a reference of the header, pos >= 0, not supplementary */
+	uint64_t crossings;            /* kept introns over all contributing records */
+	uint64_t pairs;                /* distinct (junction, template) */
+	uint64_t junctions;            /* rows */
+	uint64_t annotated;            /* rows with annotated = 1 */
+	uint64_t peak_bytes;           /* of the "junction.*" buffers (0 on the host) */
+	double seconds[5];             /* count and offsets; name ids; emit; order and reduce; annotated introns and classes (device: from HIP events, 0 on the host) */
+} agpu_junction_stats;
+int agpu_splice_junctions(agpu_ctx* ctx, const uint32_t* ref_length, uint32_t n_ref, const agpu_junction_row** rows, uint64_t* n_rows, agpu_junction_stats* stats /* may be NULL */);
+int agpu_splice_junctions_allocated_bytes(agpu_ctx* ctx, uint64_t* bytes);
 /* what the host's sequential stages and its output writer need from a batch that lives on the device:
  *   agpu_get_viral_read_counts   mapped_viral_reads_by_contig (source/read_chimeric_alignments.cpp:735-739)
  *   agpu_get_coverage            coverage_t as the reference holds it (16-bit saturating windows, start/end flags); sizes by coverage_window_offset

@@ -190,6 +190,20 @@ int ahost_gene_counts_of(ahost_session* session, const void* input_header, size_
 int ahost_gene_counts_text(ahost_session* session, const uint64_t* counts, uint64_t n_counts, const char** text, uint64_t* bytes);
 int ahost_gene_counts_write(ahost_session* session, const uint64_t* counts, uint64_t n_counts, const char* path);
 int ahost_gene_counts_file(ahost_session* session, const char* input_path, const char* path, agpu_gene_count_stats* stats);
+/* ---- --splice-junctions: the host side of agpu_splice_junctions (include/arriba_gpu.h) -- the table of splice junctions, the file STAR writes as SJ.out.tab (the rule: DESIGN.md
+ * 4.16).  A row table is what agpu_splice_junctions gives: agpu_junction_row, ordered by (ref, start, end) ----
+ *   ahost_splice_junctions_of      arriba_amd/csrc/device/junction_core.hpp stepped on the host over BAM records in host memory (the device's comparator; the CPU tier).
+ *                                  input_header: the head of the input the records come from (a BAM header, or the '@' lines of SAM text): its references are looked up among the
+ *                                  contigs of the session by name (motif from its assembly, annotated from its exon chains), their LN bounds the introns.  The rows are valid until
+ *                                  the next call on the thread
+ *   ahost_splice_junctions_text    a row table and the names of the references (ahost_depth_contigs_of / _of_session) -> the text of the file:
+ *                                  NAME\ts+1\te+1\tstrand\tmotif\tannotated\tunique\tmultimapping\toverhang\n per row; valid until the next call on the thread
+ *   ahost_splice_junctions_write   that text into `path`, through path.tmp; on a failure nothing is left behind
+ *   ahost_splice_junctions_file    all of it for a file (BAM in BGZF, gzip or raw; SAM text): what --host-ingest runs; stats may be NULL */
+int ahost_splice_junctions_of(ahost_session* session, const void* input_header, size_t header_size, const void* records, size_t size, const agpu_junction_row** rows, uint64_t* n_rows, agpu_junction_stats* stats /* may be NULL */);
+int ahost_splice_junctions_text(const ahost_depth_contigs* contigs, const agpu_junction_row* rows, uint64_t n_rows, const char** text, uint64_t* bytes);
+int ahost_splice_junctions_write(const ahost_depth_contigs* contigs, const agpu_junction_row* rows, uint64_t n_rows, const char* path);
+int ahost_splice_junctions_file(ahost_session* session, const char* input_path, const char* path, agpu_junction_stats* stats);
 int ahost_adopt_device_ingest(ahost_session* session, const agpu_ingest_result* result, const uint64_t* viral_read_counts, const uint16_t* coverage, const uint8_t* fragment_starts, const uint8_t* fragment_ends);
 int ahost_set_batch_rows(ahost_session* session, const agpu_batch_rows* rows, const uint32_t* fragments /* [rows->n] ascending: the fragment every row holds; NULL: row k holds the fragment
                          of entry k of the read lists of the table the next ahost_write_fusions writes (the reads of a candidate next to each other; the table then carries read_filter_of_rows) */);

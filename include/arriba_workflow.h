@@ -74,6 +74,11 @@ typedef struct {
 	                                         ReadsPerGene.out.tab, htseq-count -m union with -s no / yes / reverse --, counted behind read_chimeric_alignments from the record stream in HBM
 	                                         (include/arriba_gpu.h: agpu_gene_counts; with host_ingest: the same code stepped on the host).  Of arriba_workflow_run's sample;
 	                                         the samples of a session say theirs with arriba_workflow_gene_counts.  Not for one sample over several ranks. */
+	const char* splice_junctions_file;    /* --splice-junctions; NULL (and a zero-initialised struct) = none.  The splice junctions of the records of chimeric_bam_file, a line per junction that
+	                                         at least one template crosses: name, first and last base of the intron (1-based), strand, intron motif, annotated, uniquely and multiply mapping
+	                                         templates, maximum overhang -- the file STAR writes as SJ.out.tab --, made behind read_chimeric_alignments from the record stream in HBM
+	                                         (include/arriba_gpu.h: agpu_splice_junctions; with host_ingest: the same code stepped on the host).  Of arriba_workflow_run's
+	                                         sample; the samples of a session say theirs with arriba_workflow_splice_junctions.  Not for one sample over several ranks. */
 } arriba_workflow_options;
 
 /* what the reference prints as "(remaining=N)" / "(total=N)" / "(marked=N)", in the order of the stages; stage names as in the reference's source */
@@ -116,6 +121,7 @@ typedef struct { /* seconds of one sample, by part (wall clock of the calling th
 	double virus_expression; /* --virus-expression: scan, candidates, k-mer sets, copies, the table (inside `ingest`; beside the sample in front when the ingest was finished ahead) */
 	double coverage;         /* --coverage: marks, scan, runs, text, copies, the file (inside `ingest`; beside the sample in front when the ingest was finished ahead) */
 	double gene_counts;      /* --gene-counts: name ids and claims, rows and adds, the copy, the file (inside `ingest`; beside the sample in front when the ingest was finished ahead) */
+	double splice_junctions; /* --splice-junctions: counts, name ids, crossings, sorts, rows, classes, the copy, the file (inside `ingest`; beside the sample in front when the ingest was finished ahead) */
 } arriba_workflow_timing;
 /* options->chimeric_bam_file, output_file and discarded_output_file are not used by open (they belong to a sample); NULL + arriba_workflow_last_error() on failure */
 arriba_workflow_session* arriba_workflow_open(const arriba_workflow_options* options);
@@ -146,6 +152,8 @@ int arriba_workflow_virus_expression(arriba_workflow_session* session, const cha
 int arriba_workflow_coverage(arriba_workflow_session* session, const char* path);
 /* --gene-counts of the sample that is submitted NEXT, in the same way; NULL: none.  The table is written by the thread that finishes its ingest. */
 int arriba_workflow_gene_counts(arriba_workflow_session* session, const char* path);
+/* --splice-junctions of the sample that is submitted NEXT, in the same way; NULL: none.  The table is written by the thread that finishes its ingest. */
+int arriba_workflow_splice_junctions(arriba_workflow_session* session, const char* path);
 /* (If the device runs out of memory while two samples are in flight, arriba_workflow_sample throws away what was fed ahead, closes the second lane, runs its sample again with the device
  * to itself and submits the other sample again behind it -- once; a sample that does not fit the device alone fails the call.  INTEGRATION.md, "Memory".) */
 /* on: arriba_workflow_sample returns when the last output file of the sample (-O if given, else -o) has everything it needs off the device; the file is formatted and written
