@@ -1,0 +1,246 @@
+// arriba_amd/csrc/device/agpu_alleles.hip -- --allele-counts on the MI355X: the bases the records of the last ingest show at a list of known positions
+// (include/arriba_gpu.h: agpu_allele_counts).  What decides a number is allele_core.hpp, which the host steps as well (arriba_amd/csrc/host/allele_counts.cpp); the rule is
+// DESIGN.md 4.17.  Here are
+//   rocPRIM radix sort      the placed sites by (reference, position), each with its line: duplicate lines become neighbours
+//   allele_bitmap_kernel    one lane per sorted site: the bit of its 64-base window of the concatenated references (6 MB at the size of hg38: it stays in L2 / Infinity Cache)
+//   allele_count_kernel     one lane per record through ingest.record_offset: the filter, then the walk of allele_core.hpp as an iterator.  A block of the CIGAR whose windows
+//                           hold no site costs one probe of the bitmap: no binary search, no SEQ and no QUAL byte.  Every step of the loop, each lane brings at most one
+//                           (site slot, column); the lanes of the wavefront that bring the same one merge into one atomic add of their number (the leader loop of
+//                           agpu_genecount.hip: __ballot over the distinct values), so a SNP in a highly expressed gene costs one atomic per wavefront and column, not one per read.
+//                           The loop ends when no lane has a hit left; no lane leaves before that
+//   allele_rows_kernel      one lane per sorted site: its eight counters into the row of its line
+//   allele_ref_kernel       one lane per line: REF from the assembly through tid_to_contig, '.' for an unplaced line
+// Counters are unsigned sums: the rows are the same under every schedule.  The stream is only read.
+// Integer work bound by dependent loads: record_offset -> the head of the record -> its CIGAR words -> (only where a window holds a site) the sorted keys, one SEQ and one QUAL
+// byte.  No MFMA, no LDS.
+#include <hip/hip_runtime.h>
+#include <algorithm>
+#include <cstdlib>
+#include <cstring>
+#include <string>
+#include <vector>
+#include <rocprim/rocprim.hpp>
+#include "agpu_context.hpp"
+#include "device_utils.hpp"
+#include "allele_core.hpp"
+
+using namespace agpu;
+
+namespace {
+
+const int BLOCK = 256;
+const uint64_t LAUNCH_ITEMS = 1ull << 30; // one lane per record, launched in pieces that stay below 2^32 work-items
+
+#define HIP_CHECK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { set_last_error(std::string(#call) + ": " + hipGetErrorString(e_)); return AGPU_ERR_DEVICE; } } while (0)
+#define ALLOC(buffer, bytes) do { if (!(buffer).allocate(bytes)) { set_last_error("--allele-counts: hipMalloc failed (" #buffer ")"); return AGPU_ERR_NO_MEMORY; } state.note_peak(); } while (0)
+
+inline unsigned int grid_for(uint64_t n) { return (unsigned int) std::max<uint64_t>((n + BLOCK - 1) / BLOCK, 1); }
+
+enum { PASS_SITES = 0, PASS_COUNT = 1, PASS_ROWS = 2, PASSES = 3 };
+
+__device__ __forceinline__ unsigned int wave_sum(unsigned int mine) {
+	for (int offset = 32; offset > 0; offset >>= 1) mine += __shfl_down(mine, offset);
+	return mine; // (of lane 0)
+}
+
+// keys: the sorted placed sites.  The bitmap has a word for every 32 windows of window_offset[n_ref] and is zero before.
+__global__ void __launch_bounds__(BLOCK) allele_bitmap_kernel(const uint64_t* __restrict__ keys, uint64_t placed, const uint64_t* __restrict__ window_offset, uint32_t n_ref, uint32_t* bitmap) {
+	const uint64_t k = (uint64_t) blockIdx.x * BLOCK + threadIdx.x;
+	if (k >= placed) return;
+	const uint64_t key = keys[k];
+	const uint32_t ref = (uint32_t) (key >> 32);
+	if (ref >= n_ref) return; // (agpu_allele_counts admits no such site)
+	const uint64_t window = allele_window(window_offset, ref, (uint32_t) key);
+	if (window >= window_offset[n_ref]) return; // (likewise: pos < LN)
+	atomicOr(&bitmap[window >> 5], 1u << (window & 31u));
+}
+
+// counts: [sites.n][ALLELE_COLUMNS].  No lane leaves before the loop ends for the whole wavefront.
+template <bool LEADER> __global__ void __launch_bounds__(BLOCK) allele_count_kernel(const uint8_t* __restrict__ stream, uint64_t stream_size, const uint64_t* __restrict__ record_offset, uint64_t n, uint64_t first,
+		const uint32_t* __restrict__ ref_length, uint32_t n_ref, AlleleSites sites, uint32_t min_mapq, uint32_t min_baseq, uint32_t* counts, unsigned long long* contributing) {
+	const uint64_t r = first + (uint64_t) blockIdx.x * BLOCK + threadIdx.x;
+	const uint32_t lane = threadIdx.x & 63u;
+	AlleleWalk walk = {};
+	bool live = false;
+	if (r < n) {
+		AlleleRecord record;
+		if (allele_record(stream, record_offset[r], stream_size, n_ref, min_mapq, record)) { live = true; allele_walk_begin(walk, record, ref_length[record.ref]); }
+	}
+	{ const unsigned int sum = wave_sum(live ? 1u : 0u);
+	  if (lane == 0 && sum != 0) atomicAdd(contributing, (unsigned long long) sum); }
+	for (;;) {
+		uint32_t slot = 0, column = 0;
+		const bool hit = live && allele_walk_next(walk, stream, sites, min_baseq, slot, column);
+		live = hit;
+		unsigned long long todo = __ballot(hit);
+		if (todo == 0) break; // (the same in every lane)
+		const uint32_t value = slot << 3 | column; // (slot < 2^29)
+		if (LEADER) {
+			while (todo != 0) {
+				const int leader = __ffsll((long long) todo) - 1;
+				const uint32_t theirs = __shfl(value, leader);
+				const unsigned long long same = __ballot(hit && value == theirs);
+				if (lane == (uint32_t) leader) atomicAdd(&counts[theirs], (uint32_t) __popcll(same));
+				todo &= ~same;
+			}
+		} else if (hit) atomicAdd(&counts[value], 1u);
+	}
+}
+
+__global__ void __launch_bounds__(BLOCK) allele_rows_kernel(const uint32_t* __restrict__ counts, const uint32_t* __restrict__ line_of, uint64_t placed, uint64_t n_sites, agpu_allele_row* rows) {
+	const uint64_t k = (uint64_t) blockIdx.x * BLOCK + threadIdx.x;
+	if (k >= placed) return;
+	const uint32_t line = line_of[k];
+	if (line >= n_sites) return;
+	const uint32_t* mine = counts + k * ALLELE_COLUMNS;
+	agpu_allele_row& row = rows[line];
+	row.a = mine[ALLELE_A]; row.c = mine[ALLELE_C]; row.g = mine[ALLELE_G]; row.t = mine[ALLELE_T]; row.n = mine[ALLELE_N]; row.del = mine[ALLELE_DEL]; row.skip = mine[ALLELE_SKIP]; row.lowq = mine[ALLELE_LOWQ];
+}
+
+__global__ void __launch_bounds__(BLOCK) allele_ref_kernel(const agpu_allele_site* __restrict__ sites, uint64_t n_sites, const uint32_t* __restrict__ tid_to_contig, uint32_t n_ref, GenomeView genome, agpu_allele_row* rows) {
+	const uint64_t line = (uint64_t) blockIdx.x * BLOCK + threadIdx.x;
+	if (line >= n_sites) return;
+	const agpu_allele_site site = sites[line];
+	rows[line].ref_base = site.ref < n_ref && site.pos >= 0 ? allele_ref_base(genome, tid_to_contig[site.ref], (uint32_t) site.pos) : (uint8_t) '.';
+}
+
+bool knob(const char* name) { const char* value = getenv(name); return value != nullptr && value[0] == '1'; } // (for the measurements of DESIGN.md 4.17)
+
+unsigned int bits_of(uint64_t below) { unsigned int bits = 1; while (bits < 32 && (1ull << bits) < below) ++bits; return bits; } // enough for every value < below
+
+int count(agpu_ctx* ctx, const agpu_allele_site* sites, uint64_t n_sites, const uint32_t* ref_length, uint32_t n_ref, uint32_t min_mapq, uint32_t min_baseq, hipEvent_t* events) {
+	AlleleState& state = ctx->allele;
+	hipStream_t s = ctx->stream;
+	const uint64_t size = ctx->last_ingest_stream_size, n = ctx->last_ingest_records;
+	state.stats.records = n; state.stats.sites = n_sites;
+	// the placed sites as keys with their lines; the first window of every reference
+	std::vector<uint64_t> keys; std::vector<uint32_t> lines; std::vector<uint64_t> window_offset((size_t) n_ref + 1, 0);
+	for (uint64_t line = 0; line < n_sites; ++line) {
+		const agpu_allele_site& site = sites[line];
+		if (site.ref == ALLELE_UNPLACED) continue;
+		if (site.ref >= n_ref || site.pos < 0 || (uint32_t) site.pos >= ref_length[site.ref]) { set_last_error("agpu_allele_counts: site " + std::to_string(line) + " lies on no reference of the header or beyond its length (unplaced sites have ref 0xFFFFFFFF)"); return AGPU_ERR_INVALID; }
+		keys.push_back(allele_key(site.ref, (uint32_t) site.pos)); lines.push_back((uint32_t) line);
+	}
+	for (uint32_t t = 0; t < n_ref; ++t) window_offset[t + 1] = window_offset[t] + allele_windows_of(ref_length[t]);
+	const uint64_t placed = keys.size(), words = window_offset[n_ref] / 32 + 1;
+	state.stats.placed = placed;
+	state.rows.assign(n_sites, agpu_allele_row());
+	if (n_sites == 0 && n == 0) { for (int k = 0; k <= PASSES; ++k) HIP_CHECK(hipEventRecord(events[k], s)); return AGPU_OK; }
+	const bool with_bitmap = !knob("ARRIBA_ALLELE_NO_BITMAP");
+	DeviceBuffer& lengths = state.buffer("allele.ref_length"); DeviceBuffer& windows = state.buffer("allele.window_offset"); DeviceBuffer& contributing = state.buffer("allele.contributing");
+	DeviceBuffer& keys_in = state.buffer("allele.keys_in"); DeviceBuffer& lines_in = state.buffer("allele.lines_in"); DeviceBuffer& sorted_keys = state.buffer("allele.keys"); DeviceBuffer& sorted_lines = state.buffer("allele.lines");
+	DeviceBuffer& temporary_storage = state.buffer("allele.rocprim"); DeviceBuffer& bitmap = state.buffer("allele.bitmap"); DeviceBuffer& counts = state.buffer("allele.counts");
+	DeviceBuffer& device_sites = state.buffer("allele.sites"); DeviceBuffer& rows = state.buffer("allele.rows");
+	ALLOC(lengths, std::max<size_t>(n_ref, 1) * 4); ALLOC(windows, ((size_t) n_ref + 1) * 8); ALLOC(contributing, 8);
+	ALLOC(device_sites, std::max<size_t>(n_sites, 1) * sizeof(agpu_allele_site)); ALLOC(rows, std::max<size_t>(n_sites, 1) * sizeof(agpu_allele_row)); ALLOC(counts, std::max<size_t>(placed, 1) * ALLELE_COLUMNS * 4);
+	HIP_CHECK(hipMemsetAsync(contributing.ptr, 0, 8, s));
+	HIP_CHECK(hipMemsetAsync(rows.ptr, 0, std::max<size_t>(n_sites, 1) * sizeof(agpu_allele_row), s));
+	HIP_CHECK(hipMemsetAsync(counts.ptr, 0, std::max<size_t>(placed, 1) * ALLELE_COLUMNS * 4, s));
+	if (with_bitmap) { ALLOC(bitmap, words * 4); HIP_CHECK(hipMemsetAsync(bitmap.ptr, 0, words * 4, s)); }
+	if (n_ref > 0) HIP_CHECK(hipMemcpyAsync(lengths.ptr, ref_length, (size_t) n_ref * 4, hipMemcpyHostToDevice, s));
+	HIP_CHECK(hipMemcpyAsync(windows.ptr, window_offset.data(), window_offset.size() * 8, hipMemcpyHostToDevice, s));
+	if (n_sites > 0) HIP_CHECK(hipMemcpyAsync(device_sites.ptr, sites, n_sites * sizeof(agpu_allele_site), hipMemcpyHostToDevice, s));
+	if (placed > 0) {
+		ALLOC(keys_in, placed * 8); ALLOC(lines_in, placed * 4); ALLOC(sorted_keys, placed * 8); ALLOC(sorted_lines, placed * 4);
+		HIP_CHECK(hipMemcpyAsync(keys_in.ptr, keys.data(), placed * 8, hipMemcpyHostToDevice, s));
+		HIP_CHECK(hipMemcpyAsync(lines_in.ptr, lines.data(), placed * 4, hipMemcpyHostToDevice, s));
+	}
+	HIP_CHECK(hipStreamSynchronize(s)); // (the sources are pageable memory of the caller and of this function)
+	// sorted sites and window bitmap
+	HIP_CHECK(hipEventRecord(events[PASS_SITES], s));
+	if (placed > 0) {
+		const unsigned int key_bits = 32 + bits_of(n_ref);
+		size_t temporary = 0;
+		HIP_CHECK(rocprim::radix_sort_pairs(nullptr, temporary, keys_in.as<uint64_t>(), sorted_keys.as<uint64_t>(), lines_in.as<uint32_t>(), sorted_lines.as<uint32_t>(), (size_t) placed, 0u, key_bits, s));
+		ALLOC(temporary_storage, std::max<size_t>(temporary, 4));
+		{ KernelTimer timer(ctx, "allele rocprim::radix_sort_pairs(sites)", placed * 24);
+		  HIP_CHECK(rocprim::radix_sort_pairs(temporary_storage.ptr, temporary, keys_in.as<uint64_t>(), sorted_keys.as<uint64_t>(), lines_in.as<uint32_t>(), sorted_lines.as<uint32_t>(), (size_t) placed, 0u, key_bits, s)); }
+		if (with_bitmap) { KernelTimer timer(ctx, "allele_bitmap_kernel", placed * 12);
+		  allele_bitmap_kernel<<<grid_for(placed), BLOCK, 0, s>>>(sorted_keys.as<uint64_t>(), placed, windows.as<uint64_t>(), n_ref, bitmap.as<uint32_t>()); }
+	}
+	// the count over the records
+	HIP_CHECK(hipEventRecord(events[PASS_COUNT], s));
+	if (n > 0) { // (also without a placed site: `contributing` is the number of records that pass the filter, whatever the sites are)
+		const uint8_t* stream = ctx->ingest_stream.as<uint8_t>();
+		const uint64_t* record_offset = ctx->scratch("ingest.record_offset").as<uint64_t>();
+		const AlleleSites view = { placed > 0 ? sorted_keys.as<uint64_t>() : nullptr, placed, with_bitmap ? bitmap.as<uint32_t>() : nullptr, windows.as<uint64_t>() };
+		const bool plain = knob("ARRIBA_ALLELE_PLAIN_ATOMICS");
+		KernelTimer timer(ctx, "allele_count_kernel", n * 72);
+		for (uint64_t first = 0; first < n; first += LAUNCH_ITEMS) {
+			const unsigned int grid = grid_for(std::min(LAUNCH_ITEMS, n - first));
+			if (plain) allele_count_kernel<false><<<grid, BLOCK, 0, s>>>(stream, size, record_offset, n, first, lengths.as<uint32_t>(), n_ref, view, min_mapq, min_baseq, counts.as<uint32_t>(), contributing.as<unsigned long long>());
+			else allele_count_kernel<true><<<grid, BLOCK, 0, s>>>(stream, size, record_offset, n, first, lengths.as<uint32_t>(), n_ref, view, min_mapq, min_baseq, counts.as<uint32_t>(), contributing.as<unsigned long long>());
+		}
+	}
+	// REF and the rows in the order of the lines
+	HIP_CHECK(hipEventRecord(events[PASS_ROWS], s));
+	if (placed > 0) { KernelTimer timer(ctx, "allele_rows_kernel", placed * 68);
+	  allele_rows_kernel<<<grid_for(placed), BLOCK, 0, s>>>(counts.as<uint32_t>(), sorted_lines.as<uint32_t>(), placed, n_sites, rows.as<agpu_allele_row>()); }
+	if (n_sites > 0) { KernelTimer timer(ctx, "allele_ref_kernel", n_sites * 16);
+	  allele_ref_kernel<<<grid_for(n_sites), BLOCK, 0, s>>>(device_sites.as<agpu_allele_site>(), n_sites, ctx->ingest_tid_to_contig.as<uint32_t>(), n_ref, ctx->genome, rows.as<agpu_allele_row>()); }
+	HIP_CHECK(hipEventRecord(events[PASSES], s));
+	unsigned long long host_contributing = 0;
+	if (n_sites > 0) HIP_CHECK(hipMemcpyAsync(state.rows.data(), rows.ptr, n_sites * sizeof(agpu_allele_row), hipMemcpyDeviceToHost, s));
+	HIP_CHECK(hipMemcpyAsync(&host_contributing, contributing.ptr, 8, hipMemcpyDeviceToHost, s));
+	HIP_CHECK(hipStreamSynchronize(s));
+	HIP_CHECK(hipGetLastError());
+	state.stats.contributing = host_contributing;
+	for (uint64_t line = 0; line < n_sites; ++line) {
+		const agpu_allele_row& row = state.rows[line];
+		const uint64_t sum = (uint64_t) row.a + row.c + row.g + row.t + row.n + row.del + row.skip + row.lowq;
+		state.stats.hits += sum; if (sum != 0) ++state.stats.covered;
+	}
+	return AGPU_OK;
+}
+
+}
+
+extern "C" {
+
+int agpu_allele_counts(agpu_ctx* ctx, const agpu_allele_site* sites, uint64_t n_sites, const uint32_t* ref_length, uint32_t n_ref, uint32_t min_mapq, uint32_t min_baseq, const agpu_allele_row** rows, agpu_allele_stats* stats) {
+	if (!ctx || !rows || (n_sites > 0 && !sites) || (n_ref > 0 && !ref_length)) { set_last_error("null argument"); return AGPU_ERR_INVALID; }
+	*rows = nullptr;
+	if (stats) memset(stats, 0, sizeof(*stats));
+	if (min_mapq > 255 || min_baseq > 255) { set_last_error("agpu_allele_counts: a threshold above 255"); return AGPU_ERR_INVALID; }
+	if (n_sites > ALLELE_MAX_SITES) { set_last_error("agpu_allele_counts: more than 2^29-1 sites"); return AGPU_ERR_INVALID; }
+	if (ctx->ingest_active) { set_last_error("agpu_allele_counts: an ingest is under way on this context (it comes behind agpu_ingest_finish)"); return AGPU_ERR_INVALID; }
+	if (ctx->last_ingest_part_of_sample) { set_last_error("allele counts of one sample over several GPUs are not supported"); return AGPU_ERR_INVALID; }
+	const uint64_t size = ctx->last_ingest_stream_size, base = ctx->last_ingest_first_record, n = ctx->last_ingest_records;
+	DeviceBuffer& record_offset = ctx->scratch("ingest.record_offset");
+	if (!ctx->batch_from_ingest || !ctx->last_ingest_kept || ctx->ingest_stream.ptr == nullptr || record_offset.ptr == nullptr || ctx->ingest_stream.capacity < (size + 3) / 4 * 4 || record_offset.capacity < n * 8) {
+		set_last_error("agpu_allele_counts: the record stream of the last ingest is not on the device any more (it was given back under memory pressure, another ingest has begun, or there was no ingest)");
+		return AGPU_ERR_INVALID;
+	}
+	if (n >= 0xFFFFFFF0ull || base > size) { set_last_error("agpu_allele_counts: more than 2^32-16 alignment records"); return AGPU_ERR_INVALID; }
+	if (!ctx->have_genome) { set_last_error("agpu_allele_counts: agpu_upload_genome must run first"); return AGPU_ERR_INVALID; }
+	if (n_ref != ctx->ingest_n_targets || (n_ref > 0 && ctx->ingest_tid_to_contig.ptr == nullptr)) { set_last_error("agpu_allele_counts: the lengths are not those of the references of the last ingest"); return AGPU_ERR_INVALID; }
+	HIP_CHECK(hipSetDevice(ctx->device));
+	AlleleState& state = ctx->allele;
+	state.active = true; // (the stream is read from here on: nothing of this context is given back when an allocation fails)
+	memset(&state.stats, 0, sizeof(state.stats));
+	state.rows.clear(); state.peak = 0;
+	hipEvent_t events[PASSES + 1] = {};
+	int status = AGPU_OK;
+	for (int k = 0; k <= PASSES && status == AGPU_OK; ++k) if (hipEventCreate(&events[k]) != hipSuccess) { set_last_error("--allele-counts: hipEventCreate failed"); status = AGPU_ERR_DEVICE; }
+	if (status == AGPU_OK) status = count(ctx, sites, n_sites, ref_length, n_ref, min_mapq, min_baseq, events);
+	(void) hipStreamSynchronize(ctx->stream); // (nothing of a failed call is in flight when its buffers go)
+	if (status == AGPU_OK) for (int k = 0; k < PASSES; ++k) { float ms = 0; if (hipEventElapsedTime(&ms, events[k], events[k + 1]) == hipSuccess) state.stats.seconds[k] = ms / 1000.0; }
+	for (int k = 0; k <= PASSES; ++k) if (events[k]) (void) hipEventDestroy(events[k]);
+	state.stats.peak_bytes = state.peak;
+	state.release_all();
+	state.active = false;
+	collect_kernel_samples(ctx);
+	if (status != AGPU_OK) { state.rows.clear(); return status; }
+	{ std::lock_guard<std::mutex> lock(ctx->profile_mutex); if (!ctx->failed_launch.empty()) { state.rows.clear(); set_last_error("agpu_allele_counts: " + ctx->failed_launch); return AGPU_ERR_DEVICE; } }
+	*rows = state.rows.data();
+	if (stats) *stats = state.stats;
+	return AGPU_OK;
+}
+
+int agpu_allele_counts_allocated_bytes(agpu_ctx* ctx, uint64_t* bytes) {
+	if (!ctx || !bytes) { set_last_error("null argument"); return AGPU_ERR_INVALID; }
+	*bytes = ctx->allele.allocated();
+	return AGPU_OK;
+}
+
+}

@@ -174,6 +174,18 @@ struct JunctionState {
 	agpu_junction_stats stats = {};
 	std::vector<agpu_junction_row> rows;
 };
+// --allele-counts (agpu_alleles.hip): the "allele.*" buffers are the context's own and live inside one agpu_allele_counts; the rows stay until the next call
+struct AlleleState {
+	std::map<std::string, DeviceBuffer> buffers;
+	DeviceBuffer& buffer(const char* name) { return buffers[name]; }
+	void release_all() { for (std::map<std::string, DeviceBuffer>::iterator b = buffers.begin(); b != buffers.end(); ++b) b->second.release(); }
+	uint64_t allocated() const { uint64_t sum = 0; for (std::map<std::string, DeviceBuffer>::const_iterator b = buffers.begin(); b != buffers.end(); ++b) sum += b->second.capacity; return sum; }
+	bool active = false;
+	uint64_t peak = 0;
+	void note_peak() { const uint64_t now = allocated(); if (now > peak) peak = now; }
+	agpu_allele_stats stats = {};
+	std::vector<agpu_allele_row> rows;
+};
 }
 struct agpu_ctx {
 	explicit agpu_ctx(std::shared_ptr<agpu::ScratchPool> shared = std::shared_ptr<agpu::ScratchPool>()) : pool(shared ? shared : std::make_shared<agpu::ScratchPool>()),
@@ -266,6 +278,7 @@ struct agpu_ctx {
 	agpu::MarkdupState markdup; // --mark-duplicates (agpu_markdup.hip)
 	agpu::GenecountState genecount; // --gene-counts (agpu_genecount.hip)
 	agpu::JunctionState junction;   // --splice-junctions (agpu_junctions.hip)
+	agpu::AlleleState allele;       // --allele-counts (agpu_alleles.hip)
 	// A pushed piece: copied on the context's stream (piece_copied: the caller's buffer is free), unwrapped and CRC-checked on a stream of its own (piece_stream; piece_ready: its
 	// bytes are in the stream, piece_done: the raw bytes are not needed any more), so that the copy of the next piece never waits for a kernel; AGPU_PIECE_SLOTS raw buffers in turn
 	hipStream_t piece_stream = nullptr, piece_stream2 = nullptr /* deflated pieces take the two in turn */; hipEvent_t piece_copied[AGPU_PIECE_SLOTS] = {}, piece_ready[AGPU_PIECE_SLOTS] = {}, piece_done[AGPU_PIECE_SLOTS] = {};

@@ -303,6 +303,17 @@ struct JunctionReferences { agpu::AnnotationView view; agpu::GenomeView genome; 
 void splice_junctions_of(const JunctionReferences& references, const std::vector<uint32_t>& tid_to_contig, const std::vector<uint32_t>& ref_length, const uint8_t* records, uint64_t size, std::vector<agpu_junction_row>& rows,
                          agpu_junction_stats& stats);
 std::string splice_junctions_text(const ahost_depth_contigs& contigs, const agpu_junction_row* rows, uint64_t n_rows);
+// --allele-counts on the host (allele_counts.cpp): the lines of a sites file (contig as spelled, 0-based position, the reference of a header it is placed on),
+// arriba_amd/csrc/device/allele_core.hpp stepped over records in host memory with REF from the assembly of a session (genome: pointers into the session) -- the comparator of
+// agpu_alleles.hip, and what --host-ingest and the CPU tier run; and the text of the file from a row table, the host's or the device's
+struct AlleleSiteList {
+	std::vector<agpu_allele_site> sites; std::string names; std::vector<uint64_t> name_offset; uint64_t placed = 0;
+	void place(const uint8_t* header, size_t header_size); // every line on the references of a BAM header or of the '@' lines of SAM text (none: every line unplaced)
+};
+void allele_sites_parse(const std::string& path, AlleleSiteList& list); // refusals name the line
+void allele_counts_of(const agpu::GenomeView& genome, const std::vector<uint32_t>& tid_to_contig, const std::vector<uint32_t>& ref_length, const agpu_allele_site* sites, uint64_t n_sites, const uint8_t* records, uint64_t size,
+                      uint32_t min_mapq, uint32_t min_baseq, std::vector<agpu_allele_row>& rows, agpu_allele_stats& stats);
+std::string allele_counts_text(const AlleleSiteList& list, const agpu_allele_row* rows, uint64_t n_rows);
 const std::vector<uint8_t>& bam_feed_header_bytes(BamFeed* feed); // the head of the uncompressed input as the feed read it: the BAM header, or the '@' lines of SAM text
 
 // reference: source/read_chimeric_alignments.cpp:560-773 with separate_chimeric_bam_file=false, is_rna_bam_file=true

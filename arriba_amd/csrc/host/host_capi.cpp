@@ -1007,6 +1007,83 @@ int ahost_splice_junctions_file(ahost_session* session, const char* input_path, 
 	} catch (const std::exception& e) { g_error = e.what(); return -1; }
 }
 
+// ---- --allele-counts (include/arriba_host.h) ----
+namespace {
+thread_local std::vector<agpu_allele_row> g_allele_rows; thread_local std::string g_allele_text;
+agpu::GenomeView allele_genome(ahost_session* session) { // the assembly as the genome view holds it (a contig the session learnt of later has no bases)
+	agpu::GenomeView g;
+	g.n_contigs = session->genome_offset.empty() ? 0 : (uint32_t) (session->genome_offset.size() - 1); g.contig_offset = session->genome_offset.data(); g.contig_bits = session->contig_bits.data(); g.bases = session->genome_bases.data();
+	return g;
+}
+void allele_sites_view(AlleleSiteList* list, ahost_allele_sites* sites) {
+	sites->n_sites = list->sites.size(); sites->placed = list->placed; sites->sites = list->sites.data(); sites->names = list->names.data(); sites->name_offset = list->name_offset.data(); sites->owner = list;
+}
+const AlleleSiteList& allele_list_of(const ahost_allele_sites* sites) {
+	if (!sites->owner) throw std::runtime_error("allele counts: the list of sites was not loaded by ahost_allele_sites_load");
+	return *(const AlleleSiteList*) sites->owner;
+}
+void allele_counts_with_header(ahost_session* session, const uint8_t* header, size_t header_size, const uint8_t* records, size_t size, const AlleleSiteList& list, uint32_t min_mapq, uint32_t min_baseq,
+                               std::vector<agpu_allele_row>& rows, agpu_allele_stats& stats) {
+	std::vector<uint32_t> tid_to_contig, ref_length;
+	if (header_size > 0) gene_count_references(session, header, header_size, tid_to_contig, ref_length);
+	allele_counts_of(allele_genome(session), tid_to_contig, ref_length, list.sites.data(), list.sites.size(), records, size, min_mapq, min_baseq, rows, stats);
+}
+}
+int ahost_allele_sites_load(const char* path, const void* input_header, size_t header_size, ahost_allele_sites* sites) {
+	if (!path || !sites || (!input_header && header_size > 0)) { g_error = "null argument"; return -1; }
+	memset(sites, 0, sizeof(*sites));
+	try {
+		std::unique_ptr<AlleleSiteList> list(new AlleleSiteList());
+		allele_sites_parse(path, *list);
+		list->place((const uint8_t*) input_header, header_size);
+		allele_sites_view(list.release(), sites);
+		return 0;
+	} catch (const std::exception& e) { g_error = e.what(); return -1; }
+}
+int ahost_allele_sites_place_session(ahost_session* session, ahost_allele_sites* sites) {
+	if (!session || !sites || !sites->owner) { g_error = "null argument"; return -1; }
+	if (session->input_header.empty()) { g_error = "ahost_bam_open must run first"; return -1; }
+	try { AlleleSiteList* list = (AlleleSiteList*) sites->owner; list->place(session->input_header.data(), session->input_header.size()); allele_sites_view(list, sites); return 0; }
+	catch (const std::exception& e) { g_error = e.what(); return -1; }
+}
+void ahost_allele_sites_free(ahost_allele_sites* sites) { if (sites) { delete (AlleleSiteList*) sites->owner; memset(sites, 0, sizeof(*sites)); } }
+int ahost_allele_counts_of(ahost_session* session, const void* input_header, size_t header_size, const void* records, size_t size, const ahost_allele_sites* sites, uint32_t min_mapq, uint32_t min_baseq,
+                           const agpu_allele_row** rows, agpu_allele_stats* stats) {
+	if (!session || (!input_header && header_size > 0) || (!records && size > 0) || !sites || !rows) { g_error = "null argument"; return -1; }
+	try {
+		agpu_allele_stats counted;
+		allele_counts_with_header(session, (const uint8_t*) input_header, header_size, (const uint8_t*) records, size, allele_list_of(sites), min_mapq, min_baseq, g_allele_rows, counted);
+		*rows = g_allele_rows.data();
+		if (stats) *stats = counted;
+		return 0;
+	} catch (const std::exception& e) { g_error = e.what(); return -1; }
+}
+int ahost_allele_counts_text(const ahost_allele_sites* sites, const agpu_allele_row* rows, uint64_t n_rows, const char** text, uint64_t* bytes) {
+	if (!sites || (!rows && n_rows > 0) || !text || !bytes) { g_error = "null argument"; return -1; }
+	try { g_allele_text = allele_counts_text(allele_list_of(sites), rows, n_rows); *text = g_allele_text.data(); *bytes = g_allele_text.size(); return 0; }
+	catch (const std::exception& e) { g_error = e.what(); return -1; }
+}
+int ahost_allele_counts_write(const ahost_allele_sites* sites, const agpu_allele_row* rows, uint64_t n_rows, const char* path) {
+	if (!sites || (!rows && n_rows > 0) || !path) { g_error = "null argument"; return -1; }
+	try { virus_expression_write(allele_counts_text(allele_list_of(sites), rows, n_rows), path); return 0; } // (the writer of a text through path.tmp)
+	catch (const std::exception& e) { g_error = e.what(); return -1; }
+}
+int ahost_allele_counts_file(ahost_session* session, const char* input_path, const char* sites_path, const char* path, uint32_t min_mapq, uint32_t min_baseq, agpu_allele_stats* stats) {
+	if (!session || !input_path || !sites_path || !path) { g_error = "null argument"; return -1; }
+	try {
+		AlleleSiteList list;
+		allele_sites_parse(sites_path, list); // (refused before the input is read)
+		std::vector<uint8_t> stream;
+		const uint64_t at = read_whole_bam(input_path, stream); // (SAM text comes out as the BAM stream of its alignments, behind a BAM header)
+		list.place(stream.data(), at);
+		std::vector<agpu_allele_row> rows; agpu_allele_stats counted;
+		allele_counts_with_header(session, stream.data(), at, stream.data() + at, stream.size() - at, list, min_mapq, min_baseq, rows, counted);
+		virus_expression_write(allele_counts_text(list, rows.data(), rows.size()), path);
+		if (stats) *stats = counted;
+		return 0;
+	} catch (const std::exception& e) { g_error = e.what(); return -1; }
+}
+
 void ahost_bam_close(ahost_session* session) { if (session && session->feed) { close_bam_feed(session->feed); session->feed = nullptr; } }
 
 int ahost_adopt_device_ingest(ahost_session* session, const agpu_ingest_result* result, const uint64_t* viral_read_counts, const uint16_t* coverage, const uint8_t* fragment_starts, const uint8_t* fragment_ends) {

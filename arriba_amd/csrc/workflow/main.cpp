@@ -75,7 +75,11 @@ void usage() {
 	             " --gene-counts FILE  reads per gene of -x in three columns (unstranded, read strand = gene strand, the reverse) behind N_unmapped, N_multimapping, N_noFeature and\n"
 	             "                    N_ambiguous: STAR's ReadsPerGene.out.tab, htseq-count -m union with -s no / yes / reverse\n"
 	             " --splice-junctions FILE  the splice junctions of -x, a line per junction: contig, first and last base of the intron, strand, intron motif, annotated, uniquely and\n"
-	             "                    multiply mapping templates that cross it, maximum overhang: STAR's SJ.out.tab\n";
+	             "                    multiply mapping templates that cross it, maximum overhang: STAR's SJ.out.tab\n"
+	             " --allele-sites FILE --allele-counts FILE  the bases the records of -x show at known positions: FILE of --allele-sites has a line per site, contig and 1-based position\n"
+	             "                    separated by a tab (the body of a VCF is one); --allele-counts gets CONTIG POS REF A C G T N DEL SKIP LOWQ per site in that order: what samtools mpileup\n"
+	             "                    -B -x -d 0 -q MAPQ -Q BASEQ -l sites piles up, counted per base\n"
+	             " --allele-min-mapq N  records with a smaller MAPQ do not count (default 0)    --allele-min-baseq N  bases with a smaller quality go to LOWQ (default 13)\n";
 }
 
 }
@@ -110,6 +114,10 @@ int main(int argc, char** argv) {
 		else if (strcmp(argv[a], "--coverage") == 0 && a + 1 < argc) { options.coverage_file = argv[++a]; parent_exists(options.coverage_file); }
 		else if (strcmp(argv[a], "--gene-counts") == 0 && a + 1 < argc) { options.gene_counts_file = argv[++a]; parent_exists(options.gene_counts_file); }
 		else if (strcmp(argv[a], "--splice-junctions") == 0 && a + 1 < argc) { options.splice_junctions_file = argv[++a]; parent_exists(options.splice_junctions_file); }
+		else if (strcmp(argv[a], "--allele-sites") == 0 && a + 1 < argc) options.allele_sites_file = argv[++a];
+		else if (strcmp(argv[a], "--allele-counts") == 0 && a + 1 < argc) { options.allele_counts_file = argv[++a]; parent_exists(options.allele_counts_file); }
+		else if (strcmp(argv[a], "--allele-min-mapq") == 0 && a + 1 < argc) { long value; require(parse_int(argv[++a], value) && value >= 0 && value <= 0xFFFFFFFFl, "invalid argument to --allele-min-mapq"); options.allele_min_mapq = (uint32_t) value; }
+		else if (strcmp(argv[a], "--allele-min-baseq") == 0 && a + 1 < argc) { long value; require(parse_int(argv[++a], value) && value >= 0 && value <= 0xFFFFFFFFl, "invalid argument to --allele-min-baseq"); options.allele_min_baseq = (uint32_t) value; }
 		else if (strcmp(argv[a], "--supporting-window") == 0 && a + 1 < argc) { long window; require(parse_int(argv[++a], window) && window > 0 && window <= 0x7FFFFFFFl, "invalid argument to --supporting-window"); options.supporting_alignments_window = window; }
 		else if (strcmp(argv[a], "--device") == 0 && a + 1 < argc) { long device; require(parse_int(argv[++a], device) && device >= 0, "invalid argument to --device"); options.device_index = (int) device; }
 		else arguments.push_back(argv[a]);

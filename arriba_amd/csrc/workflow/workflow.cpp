@@ -54,6 +54,9 @@ extern "C" int agpu_depth_end(agpu_ctx* ctx, agpu_depth_stats* stats) __attribut
 extern "C" int agpu_gene_counts(agpu_ctx* ctx, const uint32_t* ref_length, uint32_t n_ref, uint64_t* counts, agpu_gene_count_stats* stats) __attribute__((weak));
 // ... and the one of --splice-junctions
 extern "C" int agpu_splice_junctions(agpu_ctx* ctx, const uint32_t* ref_length, uint32_t n_ref, const agpu_junction_row** rows, uint64_t* n_rows, agpu_junction_stats* stats) __attribute__((weak));
+// ... and the one of --allele-counts
+extern "C" int agpu_allele_counts(agpu_ctx* ctx, const agpu_allele_site* sites, uint64_t n_sites, const uint32_t* ref_length, uint32_t n_ref, uint32_t min_mapq, uint32_t min_baseq, const agpu_allele_row** rows,
+                                  agpu_allele_stats* stats) __attribute__((weak));
 
 namespace {
 
@@ -104,12 +107,14 @@ struct Run {
 	// read_chimeric_alignments in two halves (feed_file: the bytes of the file into HBM, on a thread of its own when the sample was submitted ahead; finish_device_ingest: what is
 	// left behind the last piece): what the first half leaves for the second
 	bool bam_open = false; uint64_t coverage_windows = 0; uint32_t bam_contigs = 0; double feed_started = 0, feed_finished = 0, feed_reading = 0, feed_pushing = 0;
-	std::string bam_path, output_path, discarded_path, sorted_bam_path, supporting_prefix, virus_expression_path, coverage_path, gene_counts_path, splice_junctions_path; // of the sample this lane works on (options.* point at them)
+	std::string bam_path, output_path, discarded_path, sorted_bam_path, supporting_prefix, virus_expression_path, coverage_path, gene_counts_path, splice_junctions_path, allele_sites_path, allele_counts_path; // of the sample this lane works on (options.* point at them)
 	double sorted_bam_seconds = 0; // --sorted-bam of the sample at work
 	double virus_expression_seconds = 0; // --virus-expression of the sample at work
 	double coverage_seconds = 0; // --coverage of the sample at work
 	double gene_counts_seconds = 0; // --gene-counts of the sample at work
 	double splice_junctions_seconds = 0; // --splice-junctions of the sample at work
+	double allele_counts_seconds = 0; // --allele-counts of the sample at work
+	ahost_allele_sites allele_sites = {}; // --allele-sites of the sample at work: read (and refused) before the feed, placed on the references of the header behind it
 	double supporting_seconds = 0; bool support_pool_built = false; // --supporting-alignments of the sample at work: the pool behind the ingest and the files behind fusions.tsv
 	std::function<void()> after_ingest; // a session with two lanes: the stream and the tables of the ingest are free for the feed of the next sample
 	// arriba_workflow_finish_ahead: the second half ran on the feeder thread, before the caller asked for the sample; what it found is noted (report, timing) when the caller does
@@ -147,12 +152,13 @@ struct Run {
 	Run(const arriba_workflow_options& o): options(o), report(nullptr), timing(nullptr), host(nullptr), device(nullptr), dummy_genes(0), n_candidates(0), n_fragments(0), mapped_reads(0), device_ingest(false) {
 		for (int k = 0; k < FEED_BUFFERS; ++k) { pieces[k] = nullptr; tables[k] = nullptr; }
 		const char** texts[] = { &options.assembly_file, &options.gene_annotation_file, &options.chimeric_bam_file, &options.output_file, &options.discarded_output_file, &options.blacklist_file, &options.known_fusions_file,
-		                         &options.tags_file, &options.protein_domains_file, &options.genomic_breakpoints_file, &options.interesting_contigs, &options.viral_contigs, &options.gtf_features, &options.sorted_bam_file, &options.supporting_alignments_prefix, &options.virus_expression_file, &options.coverage_file, &options.gene_counts_file, &options.splice_junctions_file };
+		                         &options.tags_file, &options.protein_domains_file, &options.genomic_breakpoints_file, &options.interesting_contigs, &options.viral_contigs, &options.gtf_features, &options.sorted_bam_file, &options.supporting_alignments_prefix, &options.virus_expression_file, &options.coverage_file, &options.gene_counts_file, &options.splice_junctions_file, &options.allele_sites_file, &options.allele_counts_file };
 		strings.reserve(sizeof(texts) / sizeof(texts[0]));
 		for (size_t k = 0; k < sizeof(texts) / sizeof(texts[0]); ++k) if (*texts[k] != nullptr) { strings.push_back(*texts[k]); *texts[k] = strings.back().c_str(); }
 	}
 	~Run() {
 		join_writer();
+		ahost_allele_sites_free(&allele_sites);
 		for (int k = 0; k < FEED_BUFFERS; ++k) { if (pieces[k]) agpu_host_free(pieces[k]); if (tables[k]) agpu_host_free(tables[k]); }
 		for (std::map<std::string, Staged>::iterator buffer = staged.begin(); buffer != staged.end(); ++buffer) if (buffer->second.pointer) agpu_host_free(buffer->second.pointer);
 		if (device) agpu_destroy(device); if (host) ahost_close(host);
@@ -244,6 +250,21 @@ std::string splice_junctions_line(const agpu_junction_stats& c) {
 	text << "Finding splice junctions (records=" << c.records << ", contributing=" << c.contributing << ", crossings=" << c.crossings << ", pairs=" << c.pairs << ", junctions=" << c.junctions << ", annotated=" << c.annotated << ")";
 	return text.str();
 }
+std::string allele_counts_line(const agpu_allele_stats& c) {
+	std::ostringstream text;
+	text << "Counting alleles at known sites (records=" << c.records << ", contributing=" << c.contributing << ", hits=" << c.hits << ", sites=" << c.sites << ", placed=" << c.placed << ", covered=" << c.covered << ")";
+	return text.str();
+}
+// --allele-sites / --allele-counts: what can be refused without the input; true if the option is on
+bool check_allele_counts(const Run& run) {
+	const arriba_workflow_options& o = run.options;
+	if (o.allele_sites_file == nullptr && o.allele_counts_file == nullptr) return false;
+	if (o.allele_sites_file == nullptr || o.allele_counts_file == nullptr) throw Failure{ "ERROR: --allele-sites and --allele-counts need each other: the sites to count at and the file the counts go to" };
+	if (o.allele_min_mapq > 255) throw Failure{ "ERROR: --allele-min-mapq is at most 255 (MAPQ is a byte)" };
+	if (o.allele_min_baseq > 255) throw Failure{ "ERROR: --allele-min-baseq is at most 255 (a base quality is a byte)" };
+	if (run.ranks != nullptr) throw Failure{ "ERROR: allele counts of one sample over several GPUs are not supported" };
+	return true;
+}
 
 void feed_file(Run& run) {
 	const arriba_workflow_options& o = run.options;
@@ -261,6 +282,11 @@ void feed_file(Run& run) {
 	if (run.ranks != nullptr && o.splice_junctions_file != nullptr) throw Failure{ "ERROR: splice junctions of one sample over several GPUs are not supported" };
 	if (o.splice_junctions_file != nullptr && !agpu_splice_junctions) throw Failure{ "ERROR: --splice-junctions needs the device library (agpu_splice_junctions), which this build is not linked with" }; // (likewise)
 	if (o.virus_expression_file != nullptr && !agpu_virus_expression) throw Failure{ "ERROR: --virus-expression needs the device library (agpu_virus_expression), which this build is not linked with" }; // (before the feed, not behind it)
+	ahost_allele_sites_free(&run.allele_sites); // (of a sample that failed between its feed and its counts)
+	if (check_allele_counts(run)) {
+		if (!agpu_allele_counts) throw Failure{ "ERROR: --allele-counts needs the device library (agpu_allele_counts), which this build is not linked with" }; // (likewise)
+		host_check(ahost_allele_sites_load(o.allele_sites_file, nullptr, 0, &run.allele_sites)); // (a sites file that does not parse is refused here; its lines are placed when the header is known)
+	}
 	agpu_ingest_config config;
 	if (run.ranks != nullptr) host_check(ahost_bam_open_part(run.host, o.chimeric_bam_file, o.device.external_duplicate_marking, o.device.max_itd_length, run.ranks->rank, run.ranks->size, &config)); // this rank's part of the records
 	else host_check(ahost_bam_open(run.host, o.chimeric_bam_file, o.device.external_duplicate_marking, o.device.max_itd_length, &config));
@@ -628,6 +654,27 @@ void write_splice_junctions(Run& run) {
 	run.splice_junctions_seconds = now_seconds() - started;
 }
 
+// --allele-counts: behind the ingest, while the stream is in HBM, the base counts at the sites of --allele-sites (include/arriba_gpu.h: agpu_allele_counts).  The
+// lines of the sites file, read before the feed, are placed on the references of the header; the device counts; the host writes the text with the contigs as the sites file spells
+// them, through FILE.tmp.  On a failure nothing is left and the sample fails with the message.
+void write_allele_counts(Run& run) {
+	if (!agpu_allele_counts) throw Failure{ "ERROR: --allele-counts needs the device library (agpu_allele_counts), which this build is not linked with" };
+	const double started = now_seconds();
+	struct Free { ahost_allele_sites& sites; ~Free() { ahost_allele_sites_free(&sites); } } free_sites = { run.allele_sites };
+	if (run.allele_sites.owner == nullptr) host_check(ahost_allele_sites_load(run.options.allele_sites_file, nullptr, 0, &run.allele_sites)); // (a sample that was not fed through feed_file)
+	host_check(ahost_allele_sites_place_session(run.host, &run.allele_sites));
+	ahost_depth_contigs contigs;
+	host_check(ahost_depth_contigs_of_session(run.host, &contigs)); // (LN of the references of the header)
+	const agpu_allele_row* rows = nullptr;
+	agpu_allele_stats stats;
+	const int status = agpu_allele_counts(run.device, run.allele_sites.sites, run.allele_sites.n_sites, contigs.length, contigs.n_ref, run.options.allele_min_mapq, run.options.allele_min_baseq, &rows, &stats);
+	if (status == AGPU_ERR_NO_MEMORY) throw Failure{ std::string("ERROR: --allele-counts: ") + agpu_last_error(), status };
+	device_check(status);
+	host_check(ahost_allele_counts_write(&run.allele_sites, rows, run.allele_sites.n_sites, run.options.allele_counts_file));
+	run.say(allele_counts_line(stats));
+	run.allele_counts_seconds = now_seconds() - started;
+}
+
 // --supporting-alignments, phase 1: behind the ingest, while the stream is in HBM, the records of the read names of the batch go into a pool of this lane's context
 // (include/arriba_gpu.h: agpu_support_pool_build).  Phase 2 follows when the rows of fusions.tsv are fixed (write_supporting_alignments).
 void build_support_pool(Run& run) {
@@ -712,6 +759,8 @@ void finish_device_ingest(Run& run, double waited_since) {
 	if (run.options.gene_counts_file != nullptr) write_gene_counts(run); // (likewise)
 	run.splice_junctions_seconds = 0;
 	if (run.options.splice_junctions_file != nullptr) write_splice_junctions(run); // (likewise)
+	run.allele_counts_seconds = 0;
+	if (run.options.allele_counts_file != nullptr) write_allele_counts(run); // (likewise)
 	run.supporting_seconds = 0; run.support_pool_built = false;
 	if (run.options.supporting_alignments_prefix != nullptr) build_support_pool(run); // (before after_ingest as well; the pool is this lane's own and outlives the hand-over of the stream)
 	run.sharded = false; run.first_rank = 0; run.exchanged_bytes = 0;
@@ -743,6 +792,7 @@ void note_device_ingest(Run& run, double waited_since) {
 	if (run.timing) run.timing->coverage = run.coverage_seconds;
 	if (run.timing) run.timing->gene_counts = run.gene_counts_seconds;
 	if (run.timing) run.timing->splice_junctions = run.splice_junctions_seconds;
+	if (run.timing) run.timing->allele_counts = run.allele_counts_seconds;
 	run.note("bam_records", run.ingest_records); // (for the report only: no line of the reference's log)
 	run.note("bam_stream_bytes", run.ingest_stream_bytes);
 }
@@ -1311,6 +1361,7 @@ void run_sample(Run& run, bool already_fed, double sample_started) {
 	else {
 		if (run.ranks != nullptr) throw Failure{ "ERROR: one sample over several ranks needs read_chimeric_alignments on the device (host_ingest = 0): the parts of the batch are exchanged in device format" };
 		check_mark_duplicates(o);
+		if (check_allele_counts(run)) { ahost_allele_sites checked; host_check(ahost_allele_sites_load(o.allele_sites_file, nullptr, 0, &checked)); ahost_allele_sites_free(&checked); } // (refused before the input is read)
 		host_check(ahost_ingest_bam_file(run.host, o.chimeric_bam_file, o.device.external_duplicate_marking, o.device.max_itd_length));
 		if (o.sorted_bam_file != nullptr) { // (the host's stepping of the same code)
 			const double before = now_seconds();
@@ -1334,6 +1385,13 @@ void run_sample(Run& run, bool already_fed, double sample_started) {
 			host_check(ahost_splice_junctions_file(run.host, o.chimeric_bam_file, o.splice_junctions_file, &stats));
 			run.say(splice_junctions_line(stats));
 			if (run.timing) run.timing->splice_junctions = now_seconds() - before;
+		}
+		if (o.allele_counts_file != nullptr) { // (likewise)
+			const double before = now_seconds();
+			agpu_allele_stats stats;
+			host_check(ahost_allele_counts_file(run.host, o.chimeric_bam_file, o.allele_sites_file, o.allele_counts_file, o.allele_min_mapq, o.allele_min_baseq, &stats));
+			run.say(allele_counts_line(stats));
+			if (run.timing) run.timing->allele_counts = now_seconds() - before;
 		}
 		device_check(agpu_upload_genome(run.device, ahost_genome_view(run.host)));
 		device_check(agpu_upload_batch(run.device, ahost_batch_view(run.host)));
@@ -1492,6 +1550,7 @@ void arriba_workflow_default_options(arriba_workflow_options* options) {
 	options->device.strandedness = 3; // -s auto
 	options->min_itd_support = 10; options->min_itd_allele_fraction = 0.07f; options->high_expression_quantile = 0.998f; options->min_spliced_events = 4; options->min_anchor_length = 23;
 	options->max_homolog_identity = 0.3f; options->top_viral_contigs = 5; options->viral_contig_min_covered_fraction = 0.05f; options->max_genomic_breakpoint_distance = 100000;
+	options->allele_min_baseq = 13; // (--allele-min-baseq: samtools mpileup's -Q)
 }
 
 const char* arriba_workflow_last_error(void) { return g_error.c_str(); }
@@ -1519,7 +1578,7 @@ int arriba_workflow_run(const arriba_workflow_options* options, arriba_workflow_
 struct arriba_workflow_session {
 	Run* lanes[2];
 	int processed_lane = 0; // of the sample arriba_workflow_sample worked on last
-	struct Submitted { std::string bam, sorted_bam, supporting, virus_expression, coverage, gene_counts, splice_junctions; int sorted_bam_level = 0, mark_duplicates = 0; int lane = 0; std::thread feeder; bool fed = false, ingest_finished = false, started = false; std::string error; int error_code = 0; };
+	struct Submitted { std::string bam, sorted_bam, supporting, virus_expression, coverage, gene_counts, splice_junctions, allele_sites, allele_counts; uint32_t allele_min_mapq = 0, allele_min_baseq = 0; int sorted_bam_level = 0, mark_duplicates = 0; int lane = 0; std::thread feeder; bool fed = false, ingest_finished = false, started = false; std::string error; int error_code = 0; };
 	std::deque<std::unique_ptr<Submitted>> queue; // oldest first; at most two
 	std::mutex mutex; std::condition_variable changed;
 	bool ingest_busy = false; // a lane is between agpu_ingest_begin and agpu_ingest_finish
@@ -1529,6 +1588,7 @@ struct arriba_workflow_session {
 	std::string next_coverage; // arriba_workflow_coverage: likewise
 	std::string next_gene_counts; // arriba_workflow_gene_counts: likewise
 	std::string next_splice_junctions; // arriba_workflow_splice_junctions: likewise
+	std::string next_allele_sites, next_allele_counts; uint32_t next_allele_min_mapq = 0, next_allele_min_baseq = 13; // arriba_workflow_allele_counts: likewise
 	int mark_duplicates = 0;  // arriba_workflow_sorted_bam_mark_duplicates: of the samples submitted from now on (at first: options.mark_duplicates of arriba_workflow_open)
 	int sorted_bam_level = 0; // arriba_workflow_sorted_bam_compression: of the samples submitted from now on (at first: options.sorted_bam_compression of arriba_workflow_open)
 	bool defer_output = false;
@@ -1601,10 +1661,13 @@ struct arriba_workflow_session {
 		run.coverage_path.swap(next_coverage); next_coverage.clear(); run.options.coverage_file = run.coverage_path.empty() ? nullptr : run.coverage_path.c_str();
 		run.gene_counts_path.swap(next_gene_counts); next_gene_counts.clear(); run.options.gene_counts_file = run.gene_counts_path.empty() ? nullptr : run.gene_counts_path.c_str();
 		run.splice_junctions_path.swap(next_splice_junctions); next_splice_junctions.clear(); run.options.splice_junctions_file = run.splice_junctions_path.empty() ? nullptr : run.splice_junctions_path.c_str();
+		run.allele_sites_path.swap(next_allele_sites); next_allele_sites.clear(); run.options.allele_sites_file = run.allele_sites_path.empty() ? nullptr : run.allele_sites_path.c_str();
+		run.allele_counts_path.swap(next_allele_counts); next_allele_counts.clear(); run.options.allele_counts_file = run.allele_counts_path.empty() ? nullptr : run.allele_counts_path.c_str();
+		run.options.allele_min_mapq = next_allele_min_mapq; run.options.allele_min_baseq = next_allele_min_baseq; next_allele_min_mapq = 0; next_allele_min_baseq = 13;
 		run.timing = nullptr; run.report = nullptr;
 		prepare_sample(run);
 		std::unique_ptr<Submitted> sample(new Submitted());
-		sample->bam = bam; sample->sorted_bam = run.sorted_bam_path; sample->supporting = run.supporting_prefix; sample->virus_expression = run.virus_expression_path; sample->coverage = run.coverage_path; sample->gene_counts = run.gene_counts_path; sample->splice_junctions = run.splice_junctions_path; sample->sorted_bam_level = sorted_bam_level; sample->mark_duplicates = mark_duplicates; sample->lane = lane;
+		sample->bam = bam; sample->sorted_bam = run.sorted_bam_path; sample->supporting = run.supporting_prefix; sample->virus_expression = run.virus_expression_path; sample->coverage = run.coverage_path; sample->gene_counts = run.gene_counts_path; sample->splice_junctions = run.splice_junctions_path; sample->allele_sites = run.allele_sites_path; sample->allele_counts = run.allele_counts_path; sample->allele_min_mapq = run.options.allele_min_mapq; sample->allele_min_baseq = run.options.allele_min_baseq; sample->sorted_bam_level = sorted_bam_level; sample->mark_duplicates = mark_duplicates; sample->lane = lane;
 		Submitted* mine = sample.get();
 		{ std::lock_guard<std::mutex> lock(mutex); queue.push_back(std::move(sample)); }
 		if (!run.device_ingest) { join_writer_of(lane); std::lock_guard<std::mutex> lock(mutex); mine->fed = true; return; } // (the host ingest reads the file inside arriba_workflow_sample)
@@ -1689,6 +1752,13 @@ int arriba_workflow_splice_junctions(arriba_workflow_session* session, const cha
 	return 0;
 }
 
+int arriba_workflow_allele_counts(arriba_workflow_session* session, const char* sites_path, const char* output_path, uint32_t min_mapq, uint32_t min_baseq) {
+	if (!session) { g_error = "ERROR: null argument"; return -1; }
+	session->next_allele_sites = sites_path ? sites_path : ""; session->next_allele_counts = output_path ? output_path : "";
+	session->next_allele_min_mapq = min_mapq; session->next_allele_min_baseq = min_baseq;
+	return 0;
+}
+
 int arriba_workflow_submit(arriba_workflow_session* session, const char* chimeric_bam_file) {
 	if (!session || !chimeric_bam_file) { g_error = "ERROR: null argument"; return -1; }
 	try { session->submit(chimeric_bam_file); return 0; }
@@ -1737,7 +1807,7 @@ int arriba_workflow_sample(arriba_workflow_session* session, const char* chimeri
 	}
 	catch (const Failure& failure) { g_error = failure.text; g_error_code = failure.code; status = -1; }
 	catch (const std::exception& e) { g_error = std::string("ERROR: ") + e.what(); g_error_code = 0; status = -1; }
-	if (lane) { lane->after_ingest = nullptr; lane->before_host_writer = nullptr; lane->options.chimeric_bam_file = nullptr; lane->options.sorted_bam_file = nullptr; lane->options.supporting_alignments_prefix = nullptr; lane->options.virus_expression_file = nullptr; lane->options.coverage_file = nullptr; lane->options.gene_counts_file = nullptr; lane->options.splice_junctions_file = nullptr; lane->options.output_file = nullptr; lane->options.discarded_output_file = nullptr; lane->report = nullptr; lane->timing = nullptr; session->processed_lane = (int) (lane == session->lanes[1]); }
+	if (lane) { lane->after_ingest = nullptr; lane->before_host_writer = nullptr; lane->options.chimeric_bam_file = nullptr; lane->options.sorted_bam_file = nullptr; lane->options.supporting_alignments_prefix = nullptr; lane->options.virus_expression_file = nullptr; lane->options.coverage_file = nullptr; lane->options.gene_counts_file = nullptr; lane->options.splice_junctions_file = nullptr; lane->options.allele_sites_file = nullptr; lane->options.allele_counts_file = nullptr; lane->options.output_file = nullptr; lane->options.discarded_output_file = nullptr; lane->report = nullptr; lane->timing = nullptr; session->processed_lane = (int) (lane == session->lanes[1]); }
 	// The device ran out of memory while the session had two lanes (advisor, round 4): their contexts share one pool of scratch buffers, of which nothing is idle while one lane
 	// feeds and the other runs its stages, so the device library gives nothing back by itself (DeviceBuffer::release_idle_buffers).  The session does what INTEGRATION.md ("Memory")
 	// used to ask of the caller: what was fed ahead is thrown away, the second lane is closed -- the pool belongs to one context again, which gives back what it keeps for its next
@@ -1753,6 +1823,10 @@ int arriba_workflow_sample(arriba_workflow_session* session, const char* chimeri
 		const std::string behind_coverage = session->queue.empty() ? std::string() : session->queue.front()->coverage, again_coverage = lane->coverage_path;
 		const std::string behind_gene_counts = session->queue.empty() ? std::string() : session->queue.front()->gene_counts, again_gene_counts = lane->gene_counts_path;
 		const std::string behind_splice_junctions = session->queue.empty() ? std::string() : session->queue.front()->splice_junctions, again_splice_junctions = lane->splice_junctions_path;
+		const std::string behind_allele_sites = session->queue.empty() ? std::string() : session->queue.front()->allele_sites, again_allele_sites = lane->allele_sites_path;
+		const std::string behind_allele_counts = session->queue.empty() ? std::string() : session->queue.front()->allele_counts, again_allele_counts = lane->allele_counts_path;
+		const uint32_t behind_allele_mapq = session->queue.empty() ? 0 : session->queue.front()->allele_min_mapq, again_allele_mapq = lane->options.allele_min_mapq;
+		const uint32_t behind_allele_baseq = session->queue.empty() ? 13 : session->queue.front()->allele_min_baseq, again_allele_baseq = lane->options.allele_min_baseq;
 		session->drain();
 		session->join_writer_of(0); session->join_writer_of(1);
 		// (an I/O error on the deferred file of an EARLIER sample stays noted -- advisor, round 5: it was dropped here, and the caller never learnt that the file is incomplete -- and is
@@ -1761,11 +1835,11 @@ int arriba_workflow_sample(arriba_workflow_session* session, const char* chimeri
 		delete session->lanes[1]; session->lanes[1] = nullptr; session->processed_lane = 0;
 		fprintf(stderr, "arriba_workflow_sample: %s -- with two samples in flight; '%s' is run again with the device to itself\n", first_error.c_str(), chimeric_bam_file);
 		session->retrying = true;
-		session->next_sorted_bam = again_sorted_bam; session->next_supporting = again_supporting; session->next_virus_expression = again_virus; session->next_coverage = again_coverage; session->next_gene_counts = again_gene_counts; session->next_splice_junctions = again_splice_junctions; session->sorted_bam_level = again_level; session->mark_duplicates = again_marks;
+		session->next_sorted_bam = again_sorted_bam; session->next_supporting = again_supporting; session->next_virus_expression = again_virus; session->next_coverage = again_coverage; session->next_gene_counts = again_gene_counts; session->next_splice_junctions = again_splice_junctions; session->next_allele_sites = again_allele_sites; session->next_allele_counts = again_allele_counts; session->next_allele_min_mapq = again_allele_mapq; session->next_allele_min_baseq = again_allele_baseq; session->sorted_bam_level = again_level; session->mark_duplicates = again_marks;
 		status = arriba_workflow_sample(session, chimeric_bam_file, output_file, discarded_output_file, report, timing);
 		session->retrying = false;
 		if (status == 0 && !behind.empty()) { // (as its caller submitted it: a failure to feed it is reported by the call that asks for it)
-			try { session->next_sorted_bam = behind_sorted_bam; session->next_supporting = behind_supporting; session->next_virus_expression = behind_virus; session->next_coverage = behind_coverage; session->next_gene_counts = behind_gene_counts; session->next_splice_junctions = behind_splice_junctions; session->sorted_bam_level = behind_level; session->mark_duplicates = behind_marks; session->submit(behind.c_str()); }
+			try { session->next_sorted_bam = behind_sorted_bam; session->next_supporting = behind_supporting; session->next_virus_expression = behind_virus; session->next_coverage = behind_coverage; session->next_gene_counts = behind_gene_counts; session->next_splice_junctions = behind_splice_junctions; session->next_allele_sites = behind_allele_sites; session->next_allele_counts = behind_allele_counts; session->next_allele_min_mapq = behind_allele_mapq; session->next_allele_min_baseq = behind_allele_baseq; session->sorted_bam_level = behind_level; session->mark_duplicates = behind_marks; session->submit(behind.c_str()); }
 			catch (const Failure&) {} catch (const std::exception&) {}
 		}
 		session->sorted_bam_level = session_level; session->mark_duplicates = session_marks;

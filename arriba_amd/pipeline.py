@@ -63,6 +63,13 @@ def junction_stats_of(stats):
     return out
 
 
+def allele_stats_of(stats):
+    """agpu_allele_stats (the device's or the host's) as a dict"""
+    out = {name: int(getattr(stats, name)) for name in ("records", "contributing", "hits", "sites", "placed", "covered", "peak_bytes")}
+    out["seconds"] = dict(zip(("sites", "count", "rows"), stats.seconds))
+    return out
+
+
 class ArribaError(RuntimeError):
     pass
 
@@ -214,7 +221,7 @@ class WorkflowSession(object):
         if self._lib.arriba_workflow_sorted_bam_mark_duplicates(self._session, int(bool(on))) != 0:
             raise ArribaError(self._lib.arriba_workflow_last_error().decode())
 
-    def submit(self, bam, sorted_bam_file=None, supporting_alignments_prefix=None, sorted_bam_compression=None, virus_expression_file=None, coverage_file=None, mark_duplicates=None, gene_counts_file=None, splice_junctions_file=None):
+    def submit(self, bam, sorted_bam_file=None, supporting_alignments_prefix=None, sorted_bam_compression=None, virus_expression_file=None, coverage_file=None, mark_duplicates=None, gene_counts_file=None, splice_junctions_file=None, allele_sites_file=None, allele_counts_file=None, allele_min_mapq=0, allele_min_baseq=13):
         """the sample that comes after the one `sample` is called for next: its file is fed (PCIe, the front of read_chimeric_alignments) while the stages of that one run;
         sorted_bam_file: its records in coordinate order with their index (--sorted-bam), written when its ingest is finished; sorted_bam_compression: its level (None: as it is)"""
         if sorted_bam_compression is not None:
@@ -227,6 +234,7 @@ class WorkflowSession(object):
         self._lib.arriba_workflow_coverage(self._session, coverage_file.encode() if coverage_file else None)  # (--coverage: its depth track, written when its ingest is finished)
         self._lib.arriba_workflow_gene_counts(self._session, gene_counts_file.encode() if gene_counts_file else None)  # (--gene-counts: its reads per gene, likewise)
         self._lib.arriba_workflow_splice_junctions(self._session, splice_junctions_file.encode() if splice_junctions_file else None)  # (--splice-junctions: its junction table, likewise)
+        self._lib.arriba_workflow_allele_counts(self._session, allele_sites_file.encode() if allele_sites_file else None, allele_counts_file.encode() if allele_counts_file else None, allele_min_mapq, allele_min_baseq)  # (--allele-counts: likewise)
         if self._lib.arriba_workflow_submit(self._session, bam.encode()) != 0:
             raise ArribaError(self._lib.arriba_workflow_last_error().decode())
         if self._profiling_on:
@@ -321,7 +329,7 @@ class WorkflowSession(object):
     def _lane_contexts(self):
         return [ctx for ctx in (self._lib.arriba_workflow_lane_device(self._session, lane) for lane in (0, 1)) if ctx]
 
-    def sample(self, bam, output_file, discarded_output_file=None, sorted_bam_file=None, supporting_alignments_prefix=None, sorted_bam_compression=None, virus_expression_file=None, coverage_file=None, mark_duplicates=None, gene_counts_file=None, splice_junctions_file=None):
+    def sample(self, bam, output_file, discarded_output_file=None, sorted_bam_file=None, supporting_alignments_prefix=None, sorted_bam_compression=None, virus_expression_file=None, coverage_file=None, mark_duplicates=None, gene_counts_file=None, splice_junctions_file=None, allele_sites_file=None, allele_counts_file=None, allele_min_mapq=0, allele_min_baseq=13):
         """one sample, BAM file -> fusions.tsv (and discarded.tsv); returns the stages with their "(remaining=N)" counts.  sorted_bam_file (--sorted-bam): for a sample that was
         not submitted ahead; one that was says it to `submit`"""
         report, timing = _capi.WorkflowReport(), _capi.WorkflowTiming()
@@ -341,6 +349,8 @@ class WorkflowSession(object):
             self._lib.arriba_workflow_gene_counts(self._session, gene_counts_file.encode())
         if splice_junctions_file:  # (likewise)
             self._lib.arriba_workflow_splice_junctions(self._session, splice_junctions_file.encode())
+        if allele_sites_file or allele_counts_file:  # (likewise; one without the other is refused by the sample)
+            self._lib.arriba_workflow_allele_counts(self._session, allele_sites_file.encode() if allele_sites_file else None, allele_counts_file.encode() if allele_counts_file else None, allele_min_mapq, allele_min_baseq)
         if self._lib.arriba_workflow_sample(self._session, bam.encode(), output_file.encode(), discarded_output_file.encode() if discarded_output_file else None, byref(report), byref(timing)) != 0:
             raise ArribaError(self._lib.arriba_workflow_last_error().decode())
         self.ctx = self._lib.arriba_workflow_device(self._session)  # (the lane that worked on this sample)
@@ -774,6 +784,47 @@ class DevicePipeline(object):
         self._check(self.api.splice_junctions_allocated_bytes(self.ctx, byref(count)))
         return int(count.value)
 
+    def allele_counts(self, sites_file, min_mapq=0, min_baseq=13):
+        """--allele-counts: the bases the records of the last read_chimeric_alignments show at the sites of `sites_file`, counted on the device from the record stream that is still
+        in HBM (agpu_allele_counts).  Valid after read_chimeric_alignments and before the next one.  Returns (rows, stats, sites): rows a ctypes array of
+        _capi.AlleleRow (a copy), one per line of the sites file in its order; {"records", "contributing", "hits", "sites", "placed", "covered", "peak_bytes", "seconds"}; and the
+        list of sites (_capi.AlleleSites), which the caller gives back with ahost_allele_sites_free."""
+        if not self.device_ingest or not hasattr(self.api, "allele_counts"):
+            raise ArribaError("ERROR: allele counts need the record stream of an ingest on the device (DevicePipeline(bam=...))")
+        lib, handle = self.session._lib, self.session._session
+        contigs, sites = _capi.DepthContigs(), _capi.AlleleSites()
+        if lib.ahost_depth_contigs_of_session(handle, byref(contigs)) != 0 or lib.ahost_allele_sites_load(sites_file.encode(), None, 0, byref(sites)) != 0:
+            raise ArribaError("ERROR: " + lib.ahost_last_error().decode())
+        try:
+            if lib.ahost_allele_sites_place_session(handle, byref(sites)) != 0:
+                raise ArribaError("ERROR: " + lib.ahost_last_error().decode())
+            rows, stats = ctypes.POINTER(_capi.AlleleRow)(), _capi.AlleleStats()
+            self._check(self.api.allele_counts(self.ctx, sites.sites, sites.n_sites, contigs.length, contigs.n_ref, min_mapq, min_baseq, byref(rows), byref(stats)))
+            copy = (_capi.AlleleRow * sites.n_sites)()
+            if sites.n_sites:
+                ctypes.memmove(copy, rows, ctypes.sizeof(copy))
+        except Exception:
+            lib.ahost_allele_sites_free(byref(sites))
+            raise
+        return copy, allele_stats_of(stats), sites
+
+    def write_allele_counts(self, sites_file, path, min_mapq=0, min_baseq=13):
+        """--allele-counts: the rows of `allele_counts` as the text of the file (a header line, then CONTIG POS REF A C G T N DEL SKIP LOWQ per line of the sites file), written
+        through `path`.tmp; returns the statistics"""
+        lib = self.session._lib
+        rows, stats, sites = self.allele_counts(sites_file, min_mapq, min_baseq)  # (refused before anything is written)
+        try:
+            if lib.ahost_allele_counts_write(byref(sites), rows, len(rows), path.encode()) != 0:
+                raise ArribaError("ERROR: " + lib.ahost_last_error().decode())
+        finally:
+            lib.ahost_allele_sites_free(byref(sites))
+        return stats
+
+    def allele_counts_allocated_bytes(self):
+        count = c_uint64()
+        self._check(self.api.allele_counts_allocated_bytes(self.ctx, byref(count)))
+        return int(count.value)
+
     def _free_depth_windows(self):
         if getattr(self, "_depth_windows", None) is not None:
             for buffer in self._depth_windows[1]:
@@ -1050,7 +1101,7 @@ class DevicePipeline(object):
                      max_genomic_breakpoint_distance=100000, strandedness=None, evalue_cutoff=0.3,
                      min_itd_support=10, min_itd_allele_fraction=0.07, high_expression_quantile=0.998, min_spliced_events=4, min_anchor_length=23,
                      max_homolog_identity=0.3, max_itd_length=100, fill_sequence_gaps=False, top_viral_contigs=5, viral_contig_min_covered_fraction=0.05,
-                     print_extra_info_for_discarded_fusions=False, log=None, sorted_bam_file=None, supporting_alignments_prefix=None, supporting_alignments_window=1000000, virus_expression_file=None, coverage_file=None, mark_duplicates=False, gene_counts_file=None, splice_junctions_file=None):
+                     print_extra_info_for_discarded_fusions=False, log=None, sorted_bam_file=None, supporting_alignments_prefix=None, supporting_alignments_window=1000000, virus_expression_file=None, coverage_file=None, mark_duplicates=False, gene_counts_file=None, splice_junctions_file=None, allele_sites_file=None, allele_counts_file=None, allele_min_mapq=0, allele_min_baseq=13):
         """The reference's main() behind read_chimeric_alignments (source/arriba.cpp:119-610) with its default parameters: the read-level cascade, find_fusions,
         every candidate-level filter in the reference's order, assign_confidence, and the two output files.  `log` receives (stage, remaining) pairs --
         the numbers the reference prints as "(remaining=N)".  Filters switched off with -f are skipped by the stages themselves (agpu_params.filter_enabled)."""
@@ -1067,6 +1118,10 @@ class DevicePipeline(object):
             self.write_gene_counts(gene_counts_file)
         if splice_junctions_file:  # (--splice-junctions: likewise)
             self.write_splice_junctions(splice_junctions_file)
+        if allele_sites_file or allele_counts_file:  # (--allele-counts: likewise)
+            if not (allele_sites_file and allele_counts_file):
+                raise ArribaError("ERROR: --allele-sites and --allele-counts need each other")
+            self.write_allele_counts(allele_sites_file, allele_counts_file, allele_min_mapq, allele_min_baseq)
         if supporting_alignments_prefix:  # (--supporting-alignments, phase 1: the records of the names of the batch leave the stream while it is there)
             self.build_support_pool()
         self.run_read_level(strandedness, top_viral_contigs, viral_contig_min_covered_fraction)

@@ -510,6 +510,40 @@ typedef struct {
 } agpu_junction_stats;
 int agpu_splice_junctions(agpu_ctx* ctx, const uint32_t* ref_length, uint32_t n_ref, const agpu_junction_row** rows, uint64_t* n_rows, agpu_junction_stats* stats /* may be NULL */);
 int agpu_splice_junctions_allocated_bytes(agpu_ctx* ctx, uint64_t* bytes);
+/* --allele-counts: the bases the records of the last ingest show at a list of known positions, counted on the device while the stream is in HBM (DESIGN.md 4.17;
+ * arriba_amd/csrc/device/agpu_alleles.hip, allele_core.hpp): what `samtools mpileup -B -x -d 0 -q MAPQ -Q BASEQ -l sites` piles up, per base.
+ *   agpu_allele_counts   behind agpu_ingest_finish, before the next agpu_ingest_begin on this context or its sibling (the refusals of agpu_splice_junctions; the genome must be
+ *                        uploaded: REF is read from it).  sites: the lines of the sites file in their order (ahost_allele_sites_load places them); at most 2^29 - 1.  ref_length:
+ *                        LN of every reference of the header of that ingest (n_ref of them).  min_mapq, min_baseq: at most 255.  rows: one per site, in the order of `sites`; they
+ *                        belong to the context and are valid until the next call on it.  The "allele.*" buffers are freed before the call returns.
+ *   agpu_allele_counts_allocated_bytes   of those buffers: 0 outside the call
+ * ARRIBA_ALLELE_PLAIN_ATOMICS=1 (a knob for the measurement): one atomic per lane and hit instead of one per wavefront, site and column.
+ * ARRIBA_ALLELE_NO_BITMAP=1 (likewise): no window bitmap, every aligned block is searched among the sites. */
+typedef struct {
+	uint32_t ref;                  /* index of the reference in the header; 0xFFFFFFFF: unplaced (no such reference, or a position beyond its LN) */
+	int32_t pos;                   /* 0-based (the file prints it + 1); of a placed site: 0 <= pos < LN */
+} agpu_allele_site;
+typedef struct {
+	uint32_t a, c, g, t;           /* bases under M, = or X with a quality of at least min_baseq: SEQ nibble 1, 2, 4, 8 */
+	uint32_t n;                    /* every other nibble there: 15, the ambiguity codes, 0 (=) */
+	uint32_t del, skip;            /* records that span the site with D, with N */
+	uint32_t lowq;                 /* bases under M, = or X with a quality below min_baseq */
+	uint8_t ref_base;              /* the upper-case base of the assembly; 'N': the session holds no sequence there; '.': unplaced */
+	uint8_t reserved[3];
+} agpu_allele_row;
+typedef struct {
+	uint64_t records;              /* of the stream */
+	uint64_t contributing;         /* records that pass the filter */
+	uint64_t hits;                 /* the sum of the eight columns over all rows */
+	uint64_t sites;                /* rows */
+	uint64_t placed;               /* rows on a reference of the header, inside its LN */
+	uint64_t covered;              /* rows with a non-zero column */
+	uint64_t peak_bytes;           /* of the "allele.*" buffers (0 on the host) */
+	double seconds[3];             /* sorted sites and window bitmap; the count over the records; REF and the rows in the order of the lines (device: from HIP events, 0 on the host) */
+} agpu_allele_stats;
+int agpu_allele_counts(agpu_ctx* ctx, const agpu_allele_site* sites, uint64_t n_sites, const uint32_t* ref_length, uint32_t n_ref, uint32_t min_mapq, uint32_t min_baseq, const agpu_allele_row** rows,
+                       agpu_allele_stats* stats /* may be NULL */);
+int agpu_allele_counts_allocated_bytes(agpu_ctx* ctx, uint64_t* bytes);
 /* what the host's sequential stages and its output writer need from a batch that lives on the device:
  *   agpu_get_viral_read_counts   mapped_viral_reads_by_contig (source/read_chimeric_alignments.cpp:735-739)
  *   agpu_get_coverage            coverage_t as the reference holds it (16-bit saturating windows, start/end flags); sizes by coverage_window_offset

@@ -204,6 +204,36 @@ int ahost_splice_junctions_of(ahost_session* session, const void* input_header, 
 int ahost_splice_junctions_text(const ahost_depth_contigs* contigs, const agpu_junction_row* rows, uint64_t n_rows, const char** text, uint64_t* bytes);
 int ahost_splice_junctions_write(const ahost_depth_contigs* contigs, const agpu_junction_row* rows, uint64_t n_rows, const char* path);
 int ahost_splice_junctions_file(ahost_session* session, const char* input_path, const char* path, agpu_junction_stats* stats);
+/* ---- --allele-counts: the host side of agpu_allele_counts (include/arriba_gpu.h) -- the bases the records show at a list of known positions (the rule: DESIGN.md 4.17) ----
+ *   ahost_allele_sites_load        reads a sites file (text; a line per site, cut at tabs: contig, 1-based position in plain decimal, further fields ignored -- the body of a VCF
+ *                                  is one; empty lines and lines that begin with '#' are skipped) and places every line on the references of input_header (a BAM header, or the
+ *                                  '@' lines of SAM text): the name byte for byte, else once more with a leading "chr" removed or added; no such reference, or a position beyond
+ *                                  its LN: unplaced (ref 0xFFFFFFFF).  input_header NULL: every line unplaced (the file is only checked).  A file that cannot be read, a line with
+ *                                  fewer than two fields, an empty position, one with a non-digit, 0 or above 2^31-1: refused, the message names the line.  The list belongs to
+ *                                  the caller until ahost_allele_sites_free
+ *   ahost_allele_sites_place_session   places the lines of a loaded list again, on the references of the file the last ahost_bam_open opened
+ *   ahost_allele_counts_of         arriba_amd/csrc/device/allele_core.hpp stepped on the host over BAM records in host memory (the device's comparator; the CPU tier).  sites: as
+ *                                  placed on input_header; REF comes from the assembly of the session.  The rows (one per site, in their order) are valid until the next call on
+ *                                  the thread
+ *   ahost_allele_counts_text       a row table and the list it belongs to -> the text of the file: "#CONTIG\tPOS\tREF\tA\tC\tG\tT\tN\tDEL\tSKIP\tLOWQ\n", then a line per site with the
+ *                                  contig as the sites file spells it; valid until the next call on the thread
+ *   ahost_allele_counts_write      that text into `path`, through path.tmp; on a failure nothing is left behind
+ *   ahost_allele_counts_file       all of it for a file (BAM in BGZF, gzip or raw; SAM text): what --host-ingest runs; stats may be NULL */
+typedef struct {
+	uint64_t n_sites, placed;
+	const agpu_allele_site* sites;  /* [n_sites], in the order of the lines */
+	const char* names;              /* the contigs as the file spells them, one behind the other */
+	const uint64_t* name_offset;    /* [n_sites + 1] */
+	void* owner;
+} ahost_allele_sites;
+int ahost_allele_sites_load(const char* path, const void* input_header, size_t header_size, ahost_allele_sites* sites);
+int ahost_allele_sites_place_session(ahost_session* session, ahost_allele_sites* sites);
+void ahost_allele_sites_free(ahost_allele_sites* sites);
+int ahost_allele_counts_of(ahost_session* session, const void* input_header, size_t header_size, const void* records, size_t size, const ahost_allele_sites* sites, uint32_t min_mapq, uint32_t min_baseq,
+                           const agpu_allele_row** rows, agpu_allele_stats* stats /* may be NULL */);
+int ahost_allele_counts_text(const ahost_allele_sites* sites, const agpu_allele_row* rows, uint64_t n_rows, const char** text, uint64_t* bytes);
+int ahost_allele_counts_write(const ahost_allele_sites* sites, const agpu_allele_row* rows, uint64_t n_rows, const char* path);
+int ahost_allele_counts_file(ahost_session* session, const char* input_path, const char* sites_path, const char* path, uint32_t min_mapq, uint32_t min_baseq, agpu_allele_stats* stats);
 int ahost_adopt_device_ingest(ahost_session* session, const agpu_ingest_result* result, const uint64_t* viral_read_counts, const uint16_t* coverage, const uint8_t* fragment_starts, const uint8_t* fragment_ends);
 int ahost_set_batch_rows(ahost_session* session, const agpu_batch_rows* rows, const uint32_t* fragments /* [rows->n] ascending: the fragment every row holds; NULL: row k holds the fragment
                          of entry k of the read lists of the table the next ahost_write_fusions writes (the reads of a candidate next to each other; the table then carries read_filter_of_rows) */);

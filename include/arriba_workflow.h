@@ -79,6 +79,15 @@ typedef struct {
 	                                         templates, maximum overhang -- the file STAR writes as SJ.out.tab --, made behind read_chimeric_alignments from the record stream in HBM
 	                                         (include/arriba_gpu.h: agpu_splice_junctions; with host_ingest: the same code stepped on the host).  Of arriba_workflow_run's
 	                                         sample; the samples of a session say theirs with arriba_workflow_splice_junctions.  Not for one sample over several ranks. */
+	const char* allele_sites_file;        /* --allele-sites and --allele-counts; both NULL (and a zero-initialised struct) = none, one without the other is refused.  allele_sites_file: known */
+	const char* allele_counts_file;       /* positions, a line per site, cut at tabs: contig, 1-based position (the body of a VCF is one).  allele_counts_file: a line per site in that order,
+	                                         CONTIG POS REF A C G T N DEL SKIP LOWQ behind a header line: the bases the records of chimeric_bam_file show there -- what samtools mpileup -B -x -d 0
+	                                         -q MAPQ -Q BASEQ -l sites piles up, counted per base --, counted behind read_chimeric_alignments from the record stream in HBM (include/arriba_gpu.h:
+	                                         agpu_allele_counts; with host_ingest: the same code stepped on the host).  A sites file that does not parse is refused before the
+	                                         feed starts.  Of arriba_workflow_run's sample; the samples of a session say theirs with arriba_workflow_allele_counts.  Not for one sample over
+	                                         several ranks. */
+	uint32_t allele_min_mapq;             /* --allele-min-mapq: records with a smaller MAPQ do not count; at most 255 */
+	uint32_t allele_min_baseq;            /* --allele-min-baseq: bases with a smaller quality go to LOWQ; at most 255; arriba_workflow_default_options sets 13 */
 } arriba_workflow_options;
 
 /* what the reference prints as "(remaining=N)" / "(total=N)" / "(marked=N)", in the order of the stages; stage names as in the reference's source */
@@ -122,6 +131,7 @@ typedef struct { /* seconds of one sample, by part (wall clock of the calling th
 	double coverage;         /* --coverage: marks, scan, runs, text, copies, the file (inside `ingest`; beside the sample in front when the ingest was finished ahead) */
 	double gene_counts;      /* --gene-counts: name ids and claims, rows and adds, the copy, the file (inside `ingest`; beside the sample in front when the ingest was finished ahead) */
 	double splice_junctions; /* --splice-junctions: counts, name ids, crossings, sorts, rows, classes, the copy, the file (inside `ingest`; beside the sample in front when the ingest was finished ahead) */
+	double allele_counts;    /* --allele-counts: the sites placed and sorted, the count, the rows, the copy, the file (inside `ingest`; beside the sample in front when the ingest was finished ahead) */
 } arriba_workflow_timing;
 /* options->chimeric_bam_file, output_file and discarded_output_file are not used by open (they belong to a sample); NULL + arriba_workflow_last_error() on failure */
 arriba_workflow_session* arriba_workflow_open(const arriba_workflow_options* options);
@@ -154,6 +164,9 @@ int arriba_workflow_coverage(arriba_workflow_session* session, const char* path)
 int arriba_workflow_gene_counts(arriba_workflow_session* session, const char* path);
 /* --splice-junctions of the sample that is submitted NEXT, in the same way; NULL: none.  The table is written by the thread that finishes its ingest. */
 int arriba_workflow_splice_junctions(arriba_workflow_session* session, const char* path);
+/* --allele-sites, --allele-counts, --allele-min-mapq and --allele-min-baseq of the sample that is submitted NEXT, in the same way; both paths NULL: none.  The sites file is read by
+ * the call that submits the sample; the table is written by the thread that finishes its ingest. */
+int arriba_workflow_allele_counts(arriba_workflow_session* session, const char* sites_path, const char* output_path, uint32_t min_mapq, uint32_t min_baseq);
 /* (If the device runs out of memory while two samples are in flight, arriba_workflow_sample throws away what was fed ahead, closes the second lane, runs its sample again with the device
  * to itself and submits the other sample again behind it -- once; a sample that does not fit the device alone fails the call.  INTEGRATION.md, "Memory".) */
 /* on: arriba_workflow_sample returns when the last output file of the sample (-O if given, else -o) has everything it needs off the device; the file is formatted and written
