@@ -70,6 +70,7 @@ bool DeviceBuffer::release_idle_buffers() {
 		if (ctx->genecount.active) continue; // (agpu_gene_counts reads the stream)
 		if (ctx->junction.active) continue; // (agpu_splice_junctions reads the stream)
 		if (ctx->allele.active) continue; // (agpu_allele_counts reads the stream)
+		if (ctx->realign.active) continue; // (between agpu_realign_begin and _end: the text kernels read the stream)
 		if (ctx->support.active) continue; // (agpu_support_pool_build reads the stream; between agpu_supporting_begin and _end nothing of the context moves either)
 		(void) hipStreamSynchronize(ctx->stream);
 		if (!ctx->ingest_active && !ctx->ingest_finishing) { if (release_ingest_buffers(ctx)) released = true; }

@@ -186,6 +186,20 @@ struct AlleleState {
 	agpu_allele_stats stats = {};
 	std::vector<agpu_allele_row> rows;
 };
+// --realign-reads (agpu_realign.hip): the "realign.*" buffers are the context's own and live between agpu_realign_begin and _end
+struct RealignState {
+	std::map<std::string, DeviceBuffer> buffers;
+	DeviceBuffer& buffer(const char* name) { return buffers[name]; }
+	void release_all() { for (std::map<std::string, DeviceBuffer>::iterator b = buffers.begin(); b != buffers.end(); ++b) b->second.release(); }
+	uint64_t allocated() const { uint64_t sum = 0; for (std::map<std::string, DeviceBuffer>::const_iterator b = buffers.begin(); b != buffers.end(); ++b) sum += b->second.capacity; return sum; }
+	bool active = false;
+	bool paired = false, want_kept = false, wave_form = true;
+	uint32_t n_ref = 0;
+	uint64_t records = 0, window = 0, launch_items = 0; // records of the stream; bytes of a window of text; work-items of a launch
+	uint64_t total[2] = { 0, 0 }, flushed[2] = { 0, 0 }; // bytes of the two files; bytes of them that were fetched
+	agpu_realign_stats stats = {};
+	hipEvent_t events[2] = { nullptr, nullptr };
+};
 }
 struct agpu_ctx {
 	explicit agpu_ctx(std::shared_ptr<agpu::ScratchPool> shared = std::shared_ptr<agpu::ScratchPool>()) : pool(shared ? shared : std::make_shared<agpu::ScratchPool>()),
@@ -279,6 +293,7 @@ struct agpu_ctx {
 	agpu::GenecountState genecount; // --gene-counts (agpu_genecount.hip)
 	agpu::JunctionState junction;   // --splice-junctions (agpu_junctions.hip)
 	agpu::AlleleState allele;       // --allele-counts (agpu_alleles.hip)
+	agpu::RealignState realign;     // --realign-reads (agpu_realign.hip)
 	// A pushed piece: copied on the context's stream (piece_copied: the caller's buffer is free), unwrapped and CRC-checked on a stream of its own (piece_stream; piece_ready: its
 	// bytes are in the stream, piece_done: the raw bytes are not needed any more), so that the copy of the next piece never waits for a kernel; AGPU_PIECE_SLOTS raw buffers in turn
 	hipStream_t piece_stream = nullptr, piece_stream2 = nullptr /* deflated pieces take the two in turn */; hipEvent_t piece_copied[AGPU_PIECE_SLOTS] = {}, piece_ready[AGPU_PIECE_SLOTS] = {}, piece_done[AGPU_PIECE_SLOTS] = {};

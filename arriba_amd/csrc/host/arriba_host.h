@@ -71,6 +71,8 @@ struct Contigs {
 
 struct Assembly {
 	std::vector<std::string> sequence;          // per contig id; empty = not loaded (uninteresting)
+	std::vector<std::string> file_names;        // the contigs of the file in its order, as it spells them, the uninteresting ones included (--realign-kept writes them as @SQ lines)
+	std::vector<uint64_t> file_lengths;         // their bases
 	bool has(contig_t contig) const { return contig < sequence.size() && !sequence[contig].empty(); }
 };
 // reference: source/assembly.cpp:28-58
@@ -314,6 +316,12 @@ void allele_sites_parse(const std::string& path, AlleleSiteList& list); // refus
 void allele_counts_of(const agpu::GenomeView& genome, const std::vector<uint32_t>& tid_to_contig, const std::vector<uint32_t>& ref_length, const agpu_allele_site* sites, uint64_t n_sites, const uint8_t* records, uint64_t size,
                       uint32_t min_mapq, uint32_t min_baseq, std::vector<agpu_allele_row>& rows, agpu_allele_stats& stats);
 std::string allele_counts_text(const AlleleSiteList& list, const agpu_allele_row* rows, uint64_t n_rows);
+// --realign-reads on the host (realign_split.cpp): which references of a header are contigs of the assembly and the header of the file of the kept templates; and
+// arriba_amd/csrc/device/realign_core.hpp stepped over records in host memory -- the comparator of agpu_realign.hip, and what --host-ingest and the CPU tier run.  kept: the lines
+// without the header (empty unless want_kept)
+struct RealignPlan { std::vector<uint8_t> in_assembly; std::string header; };
+void realign_plan_of(const Assembly& assembly, const uint8_t* header, size_t size, RealignPlan& plan);
+void realign_split_of(const uint8_t* in_assembly, const ahost_depth_contigs& contigs, const uint8_t* records, uint64_t size, bool want_kept, std::string& realign, std::string& kept, agpu_realign_stats& stats);
 const std::vector<uint8_t>& bam_feed_header_bytes(BamFeed* feed); // the head of the uncompressed input as the feed read it: the BAM header, or the '@' lines of SAM text
 
 // reference: source/read_chimeric_alignments.cpp:560-773 with separate_chimeric_bam_file=false, is_rna_bam_file=true

@@ -1084,6 +1084,57 @@ int ahost_allele_counts_file(ahost_session* session, const char* input_path, con
 	} catch (const std::exception& e) { g_error = e.what(); return -1; }
 }
 
+// ---- --realign-reads (include/arriba_host.h) ----
+namespace {
+thread_local RealignPlan g_realign_plan; thread_local std::string g_realign_text, g_realign_kept;
+void realign_plan_view(ahost_realign_plan* plan) {
+	plan->n_ref = (uint32_t) g_realign_plan.in_assembly.size(); plan->in_assembly = g_realign_plan.in_assembly.data(); plan->header = g_realign_plan.header.data(); plan->header_bytes = g_realign_plan.header.size();
+}
+// both files of a stream through NAME.tmp: on a failure neither is left behind
+void realign_write(const std::string& realign, const std::string& kept, const char* realign_path, const char* kept_path) {
+	virus_expression_write(realign, realign_path); // (the writer of a text through path.tmp)
+	if (kept_path) { try { virus_expression_write(kept, kept_path); } catch (...) { remove(realign_path); throw; } }
+}
+}
+int ahost_realign_plan_of(ahost_session* session, const void* input_header, size_t header_size, ahost_realign_plan* plan) {
+	if (!session || !plan || (!input_header && header_size > 0)) { g_error = "null argument"; return -1; }
+	try { realign_plan_of(session->assembly, (const uint8_t*) input_header, header_size, g_realign_plan); realign_plan_view(plan); return 0; }
+	catch (const std::exception& e) { g_error = e.what(); return -1; }
+}
+int ahost_realign_plan_of_session(ahost_session* session, ahost_realign_plan* plan) {
+	if (!session || !plan) { g_error = "null argument"; return -1; }
+	if (session->input_header.empty()) { g_error = "ahost_bam_open must run first"; return -1; }
+	return ahost_realign_plan_of(session, session->input_header.data(), session->input_header.size(), plan);
+}
+int ahost_realign_split_of(ahost_session* session, const void* input_header, size_t header_size, const void* records, size_t size, int want_kept, const char** realign, uint64_t* realign_bytes, const char** kept, uint64_t* kept_bytes,
+                           agpu_realign_stats* stats) {
+	if (!session || (!input_header && header_size > 0) || (!records && size > 0) || !realign || !realign_bytes || (want_kept && (!kept || !kept_bytes))) { g_error = "null argument"; return -1; }
+	try {
+		DepthContigs contigs; std::string lines; agpu_realign_stats counted;
+		realign_plan_of(session->assembly, (const uint8_t*) input_header, header_size, g_realign_plan);
+		if (header_size > 0) depth_contigs_of((const uint8_t*) input_header, header_size, contigs); else contigs.name_offset.push_back(0);
+		realign_split_of(g_realign_plan.in_assembly.data(), contigs.view(), (const uint8_t*) records, size, want_kept != 0, g_realign_text, lines, counted);
+		*realign = g_realign_text.data(); *realign_bytes = g_realign_text.size();
+		if (want_kept) { g_realign_kept = g_realign_plan.header + lines; *kept = g_realign_kept.data(); *kept_bytes = g_realign_kept.size(); }
+		if (stats) *stats = counted;
+		return 0;
+	} catch (const std::exception& e) { g_error = e.what(); return -1; }
+}
+int ahost_realign_split_file(ahost_session* session, const char* input_path, const char* realign_path, const char* kept_path, agpu_realign_stats* stats) {
+	if (!session || !input_path || !realign_path) { g_error = "null argument"; return -1; }
+	try {
+		std::vector<uint8_t> stream;
+		const uint64_t at = read_whole_bam(input_path, stream); // (SAM text comes out as the BAM stream of its alignments, behind a BAM header)
+		RealignPlan plan; DepthContigs contigs; std::string realign, kept; agpu_realign_stats counted;
+		realign_plan_of(session->assembly, stream.data(), at, plan);
+		depth_contigs_of(stream.data(), at, contigs);
+		realign_split_of(plan.in_assembly.data(), contigs.view(), stream.data() + at, stream.size() - at, kept_path != nullptr, realign, kept, counted);
+		realign_write(realign, plan.header + kept, realign_path, kept_path);
+		if (stats) *stats = counted;
+		return 0;
+	} catch (const std::exception& e) { g_error = e.what(); return -1; }
+}
+
 void ahost_bam_close(ahost_session* session) { if (session && session->feed) { close_bam_feed(session->feed); session->feed = nullptr; } }
 
 int ahost_adopt_device_ingest(ahost_session* session, const agpu_ingest_result* result, const uint64_t* viral_read_counts, const uint16_t* coverage, const uint8_t* fragment_starts, const uint8_t* fragment_ends) {

@@ -159,6 +159,7 @@ void load_assembly(Assembly& assembly, const std::string& fasta_path, Contigs& c
 	LineReader fasta(fasta_path);
 	std::string line;
 	int current_contig = -1;
+	size_t current_in_file = 0;
 	while (fasta.getline(line)) {
 		if (line.empty())
 			continue;
@@ -166,12 +167,18 @@ void load_assembly(Assembly& assembly, const std::string& fasta_path, Contigs& c
 			std::istringstream header(line.substr(1));
 			std::string contig_name;
 			header >> contig_name;
+			current_in_file = std::find(assembly.file_names.begin(), assembly.file_names.end(), contig_name) - assembly.file_names.begin();
+			if (current_in_file == assembly.file_names.size()) { assembly.file_names.push_back(contig_name); assembly.file_lengths.push_back(0); }
 			current_contig = contigs.add(contig_name);
 			if (!is_interesting_contig(contig_name, interesting_contigs))
 				current_contig = -1; // skip uninteresting contigs
 			else if (assembly.sequence.size() <= (size_t) current_contig)
 				assembly.sequence.resize(current_contig + 1);
-		} else if (current_contig >= 0) {
+		} else {
+			if (current_in_file < assembly.file_lengths.size())
+				assembly.file_lengths[current_in_file] += line.size();
+			if (current_contig < 0)
+				continue;
 			for (size_t i = 0; i < line.size(); ++i)
 				line[i] = toupper((unsigned char) line[i]);
 			assembly.sequence[current_contig] += line;

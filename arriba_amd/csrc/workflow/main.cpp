@@ -79,7 +79,10 @@ void usage() {
 	             " --allele-sites FILE --allele-counts FILE  the bases the records of -x show at known positions: FILE of --allele-sites has a line per site, contig and 1-based position\n"
 	             "                    separated by a tab (the body of a VCF is one); --allele-counts gets CONTIG POS REF A C G T N DEL SKIP LOWQ per site in that order: what samtools mpileup\n"
 	             "                    -B -x -d 0 -q MAPQ -Q BASEQ -l sites piles up, counted per base\n"
-	             " --allele-min-mapq N  records with a smaller MAPQ do not count (default 0)    --allele-min-baseq N  bases with a smaller quality go to LOWQ (default 13)\n";
+	             " --allele-min-mapq N  records with a smaller MAPQ do not count (default 0)    --allele-min-baseq N  bases with a smaller quality go to LOWQ (default 13)\n"
+	             " --realign-reads FILE [--realign-kept FILE]  the templates of -x that must be aligned again -- unmapped, clipped by 10 or more bases at the 5' end, discordant, or on a\n"
+	             "                    contig that -a lacks -- as headerless SAM lines (fields 1-11) for STAR --readFilesType SAM; --realign-kept gets all other templates behind a header\n"
+	             "                    with the contigs of -a: what scripts/run_arriba_on_prealigned_bam.sh of arriba feeds to STAR and passes on\n";
 }
 
 }
@@ -116,6 +119,8 @@ int main(int argc, char** argv) {
 		else if (strcmp(argv[a], "--splice-junctions") == 0 && a + 1 < argc) { options.splice_junctions_file = argv[++a]; parent_exists(options.splice_junctions_file); }
 		else if (strcmp(argv[a], "--allele-sites") == 0 && a + 1 < argc) options.allele_sites_file = argv[++a];
 		else if (strcmp(argv[a], "--allele-counts") == 0 && a + 1 < argc) { options.allele_counts_file = argv[++a]; parent_exists(options.allele_counts_file); }
+		else if (strcmp(argv[a], "--realign-reads") == 0 && a + 1 < argc) { options.realign_reads_file = argv[++a]; parent_exists(options.realign_reads_file); }
+		else if (strcmp(argv[a], "--realign-kept") == 0 && a + 1 < argc) { options.realign_kept_file = argv[++a]; parent_exists(options.realign_kept_file); }
 		else if (strcmp(argv[a], "--allele-min-mapq") == 0 && a + 1 < argc) { long value; require(parse_int(argv[++a], value) && value >= 0 && value <= 0xFFFFFFFFl, "invalid argument to --allele-min-mapq"); options.allele_min_mapq = (uint32_t) value; }
 		else if (strcmp(argv[a], "--allele-min-baseq") == 0 && a + 1 < argc) { long value; require(parse_int(argv[++a], value) && value >= 0 && value <= 0xFFFFFFFFl, "invalid argument to --allele-min-baseq"); options.allele_min_baseq = (uint32_t) value; }
 		else if (strcmp(argv[a], "--supporting-window") == 0 && a + 1 < argc) { long window; require(parse_int(argv[++a], window) && window > 0 && window <= 0x7FFFFFFFl, "invalid argument to --supporting-window"); options.supporting_alignments_window = window; }

@@ -57,6 +57,10 @@ extern "C" int agpu_splice_junctions(agpu_ctx* ctx, const uint32_t* ref_length, 
 // ... and the one of --allele-counts
 extern "C" int agpu_allele_counts(agpu_ctx* ctx, const agpu_allele_site* sites, uint64_t n_sites, const uint32_t* ref_length, uint32_t n_ref, uint32_t min_mapq, uint32_t min_baseq, const agpu_allele_row** rows,
                                   agpu_allele_stats* stats) __attribute__((weak));
+// ... and those of --realign-reads
+extern "C" int agpu_realign_begin(agpu_ctx* ctx, const uint8_t* in_assembly, const char* names, const uint32_t* name_offset, uint32_t n_ref, int want_kept, agpu_realign_info* info) __attribute__((weak));
+extern "C" int agpu_realign_next(agpu_ctx* ctx, int which, void* pinned, uint64_t capacity, uint64_t* bytes) __attribute__((weak));
+extern "C" int agpu_realign_end(agpu_ctx* ctx, agpu_realign_stats* stats) __attribute__((weak));
 
 namespace {
 
@@ -107,13 +111,14 @@ struct Run {
 	// read_chimeric_alignments in two halves (feed_file: the bytes of the file into HBM, on a thread of its own when the sample was submitted ahead; finish_device_ingest: what is
 	// left behind the last piece): what the first half leaves for the second
 	bool bam_open = false; uint64_t coverage_windows = 0; uint32_t bam_contigs = 0; double feed_started = 0, feed_finished = 0, feed_reading = 0, feed_pushing = 0;
-	std::string bam_path, output_path, discarded_path, sorted_bam_path, supporting_prefix, virus_expression_path, coverage_path, gene_counts_path, splice_junctions_path, allele_sites_path, allele_counts_path; // of the sample this lane works on (options.* point at them)
+	std::string bam_path, output_path, discarded_path, sorted_bam_path, supporting_prefix, virus_expression_path, coverage_path, gene_counts_path, splice_junctions_path, allele_sites_path, allele_counts_path, realign_reads_path, realign_kept_path; // of the sample this lane works on (options.* point at them)
 	double sorted_bam_seconds = 0; // --sorted-bam of the sample at work
 	double virus_expression_seconds = 0; // --virus-expression of the sample at work
 	double coverage_seconds = 0; // --coverage of the sample at work
 	double gene_counts_seconds = 0; // --gene-counts of the sample at work
 	double splice_junctions_seconds = 0; // --splice-junctions of the sample at work
 	double allele_counts_seconds = 0; // --allele-counts of the sample at work
+	double realign_seconds = 0; // --realign-reads of the sample at work
 	ahost_allele_sites allele_sites = {}; // --allele-sites of the sample at work: read (and refused) before the feed, placed on the references of the header behind it
 	double supporting_seconds = 0; bool support_pool_built = false; // --supporting-alignments of the sample at work: the pool behind the ingest and the files behind fusions.tsv
 	std::function<void()> after_ingest; // a session with two lanes: the stream and the tables of the ingest are free for the feed of the next sample
@@ -152,7 +157,7 @@ struct Run {
 	Run(const arriba_workflow_options& o): options(o), report(nullptr), timing(nullptr), host(nullptr), device(nullptr), dummy_genes(0), n_candidates(0), n_fragments(0), mapped_reads(0), device_ingest(false) {
 		for (int k = 0; k < FEED_BUFFERS; ++k) { pieces[k] = nullptr; tables[k] = nullptr; }
 		const char** texts[] = { &options.assembly_file, &options.gene_annotation_file, &options.chimeric_bam_file, &options.output_file, &options.discarded_output_file, &options.blacklist_file, &options.known_fusions_file,
-		                         &options.tags_file, &options.protein_domains_file, &options.genomic_breakpoints_file, &options.interesting_contigs, &options.viral_contigs, &options.gtf_features, &options.sorted_bam_file, &options.supporting_alignments_prefix, &options.virus_expression_file, &options.coverage_file, &options.gene_counts_file, &options.splice_junctions_file, &options.allele_sites_file, &options.allele_counts_file };
+		                         &options.tags_file, &options.protein_domains_file, &options.genomic_breakpoints_file, &options.interesting_contigs, &options.viral_contigs, &options.gtf_features, &options.sorted_bam_file, &options.supporting_alignments_prefix, &options.virus_expression_file, &options.coverage_file, &options.gene_counts_file, &options.splice_junctions_file, &options.allele_sites_file, &options.allele_counts_file, &options.realign_reads_file, &options.realign_kept_file };
 		strings.reserve(sizeof(texts) / sizeof(texts[0]));
 		for (size_t k = 0; k < sizeof(texts) / sizeof(texts[0]); ++k) if (*texts[k] != nullptr) { strings.push_back(*texts[k]); *texts[k] = strings.back().c_str(); }
 	}
@@ -265,6 +270,31 @@ bool check_allele_counts(const Run& run) {
 	if (run.ranks != nullptr) throw Failure{ "ERROR: allele counts of one sample over several GPUs are not supported" };
 	return true;
 }
+std::string realign_line(const agpu_realign_stats& c) {
+	std::ostringstream text;
+	text << "Splitting reads for realignment (layout=" << (c.layout ? "PE" : "SE") << ", templates=" << c.templates << ", realign=" << c.realign_templates << ", kept=" << c.kept_templates << ", dropped_secondary=" << c.dropped_secondary
+	     << ", extra=" << c.extra << ", orphans=" << c.orphans << ")";
+	return text.str();
+}
+// --realign-reads / --realign-kept: what can be refused without the input; true if the option is on
+bool check_realign(const Run& run) {
+	const arriba_workflow_options& o = run.options;
+	if (o.realign_reads_file == nullptr && o.realign_kept_file == nullptr) return false;
+	if (o.realign_reads_file == nullptr) throw Failure{ "ERROR: --realign-kept needs --realign-reads: the file of the templates to realign" };
+	const char* const others[] = { o.output_file, o.discarded_output_file, o.sorted_bam_file, o.virus_expression_file, o.coverage_file, o.gene_counts_file, o.splice_junctions_file, o.allele_counts_file, o.chimeric_bam_file };
+	const char* const mine[] = { o.realign_reads_file, o.realign_kept_file };
+	if (o.realign_kept_file != nullptr && strcmp(o.realign_reads_file, o.realign_kept_file) == 0) throw Failure{ "ERROR: --realign-reads and --realign-kept name the same file" };
+	for (size_t m = 0; m < 2; ++m) for (size_t k = 0; k < sizeof(others) / sizeof(others[0]); ++k)
+		if (mine[m] != nullptr && others[k] != nullptr && strcmp(mine[m], others[k]) == 0) throw Failure{ std::string("ERROR: ") + (m == 0 ? "--realign-reads" : "--realign-kept") + " names a file that another option of the run names: '" + mine[m] + "'" };
+	if (run.ranks != nullptr) throw Failure{ "ERROR: a split for realignment of one sample over several GPUs is not supported" };
+	for (size_t m = 0; m < 2; ++m) if (mine[m] != nullptr) { // (the directory must take the file: NAME.tmp is made and removed)
+		const std::string temporary = std::string(mine[m]) + ".tmp";
+		FILE* file = fopen(temporary.c_str(), "wb");
+		if (file == nullptr) throw Failure{ "ERROR: failed to open '" + temporary + "' for writing" };
+		fclose(file); remove(temporary.c_str());
+	}
+	return true;
+}
 
 void feed_file(Run& run) {
 	const arriba_workflow_options& o = run.options;
@@ -282,6 +312,7 @@ void feed_file(Run& run) {
 	if (run.ranks != nullptr && o.splice_junctions_file != nullptr) throw Failure{ "ERROR: splice junctions of one sample over several GPUs are not supported" };
 	if (o.splice_junctions_file != nullptr && !agpu_splice_junctions) throw Failure{ "ERROR: --splice-junctions needs the device library (agpu_splice_junctions), which this build is not linked with" }; // (likewise)
 	if (o.virus_expression_file != nullptr && !agpu_virus_expression) throw Failure{ "ERROR: --virus-expression needs the device library (agpu_virus_expression), which this build is not linked with" }; // (before the feed, not behind it)
+	if (check_realign(run) && (!agpu_realign_begin || !agpu_realign_next || !agpu_realign_end)) throw Failure{ "ERROR: --realign-reads needs the device library (agpu_realign_begin), which this build is not linked with" }; // (likewise)
 	ahost_allele_sites_free(&run.allele_sites); // (of a sample that failed between its feed and its counts)
 	if (check_allele_counts(run)) {
 		if (!agpu_allele_counts) throw Failure{ "ERROR: --allele-counts needs the device library (agpu_allele_counts), which this build is not linked with" }; // (likewise)
@@ -675,6 +706,49 @@ void write_allele_counts(Run& run) {
 	run.allele_counts_seconds = now_seconds() - started;
 }
 
+// --realign-reads: behind the ingest, while the stream is in HBM, the records split into the templates to realign and the templates to keep, as SAM text (include/arriba_gpu.h:
+// agpu_realign_*).  The device decides and formats; the host writes the header of the kept file and appends the windows of text -- through two pinned buffers in
+// turn -- to NAME.tmp, which is renamed when both files are complete.  On a failure both are removed and the sample fails with the message.
+void write_realign(Run& run) {
+	if (!agpu_realign_begin || !agpu_realign_next || !agpu_realign_end) throw Failure{ "ERROR: --realign-reads needs the device library (agpu_realign_begin), which this build is not linked with" };
+	const double started = now_seconds();
+	const char* const paths[2] = { run.options.realign_reads_file, run.options.realign_kept_file };
+	ahost_depth_contigs contigs;
+	host_check(ahost_depth_contigs_of_session(run.host, &contigs)); // (the names of the references of the header)
+	ahost_realign_plan plan;
+	host_check(ahost_realign_plan_of_session(run.host, &plan));
+	agpu_realign_info info;
+	const auto check = [](int status) { if (status == AGPU_ERR_NO_MEMORY) throw Failure{ std::string("ERROR: --realign-reads: ") + agpu_last_error(), status }; device_check(status); };
+	check(agpu_realign_begin(run.device, plan.in_assembly, contigs.names, contigs.name_offset, contigs.n_ref, paths[1] != nullptr, &info));
+	agpu_realign_stats stats;
+	struct Ender { Run& run; agpu_realign_stats& stats; bool done; ~Ender() { if (!done) agpu_realign_end(run.device, nullptr); } } ender = { run, stats, false };
+	FILE* file = nullptr;
+	try {
+		uint8_t* windows[2] = { run.stage<uint8_t>("realign.window0", info.window_bytes), run.stage<uint8_t>("realign.window1", info.window_bytes) };
+		for (int which = 0; which < 2; ++which) {
+			if (paths[which] == nullptr) continue;
+			const std::string temporary = std::string(paths[which]) + ".tmp";
+			file = fopen(temporary.c_str(), "wb");
+			if (file == nullptr) throw Failure{ "ERROR: failed to open '" + temporary + "' for writing" };
+			if (which == 1 && fwrite(plan.header, 1, plan.header_bytes, file) != plan.header_bytes) throw Failure{ "ERROR: failed to write '" + temporary + "'" };
+			for (unsigned int turn = 0; ; ++turn) {
+				uint64_t bytes = 0;
+				check(agpu_realign_next(run.device, which, windows[turn & 1], info.window_bytes, &bytes));
+				if (bytes == 0) break;
+				if (fwrite(windows[turn & 1], 1, bytes, file) != bytes) throw Failure{ "ERROR: failed to write '" + temporary + "'" };
+			}
+			const int closed = fclose(file); file = nullptr;
+			if (closed != 0) throw Failure{ "ERROR: failed to write '" + temporary + "'" };
+		}
+		for (int which = 0; which < 2; ++which) if (paths[which] != nullptr && rename((std::string(paths[which]) + ".tmp").c_str(), paths[which]) != 0) throw Failure{ std::string("ERROR: failed to write '") + paths[which] + "'" };
+	}
+	catch (...) { if (file) fclose(file); for (int which = 0; which < 2; ++which) if (paths[which] != nullptr) { remove((std::string(paths[which]) + ".tmp").c_str()); remove(paths[which]); } throw; }
+	ender.done = true;
+	check(agpu_realign_end(run.device, &stats));
+	run.say(realign_line(stats));
+	run.realign_seconds = now_seconds() - started;
+}
+
 // --supporting-alignments, phase 1: behind the ingest, while the stream is in HBM, the records of the read names of the batch go into a pool of this lane's context
 // (include/arriba_gpu.h: agpu_support_pool_build).  Phase 2 follows when the rows of fusions.tsv are fixed (write_supporting_alignments).
 void build_support_pool(Run& run) {
@@ -761,6 +835,8 @@ void finish_device_ingest(Run& run, double waited_since) {
 	if (run.options.splice_junctions_file != nullptr) write_splice_junctions(run); // (likewise)
 	run.allele_counts_seconds = 0;
 	if (run.options.allele_counts_file != nullptr) write_allele_counts(run); // (likewise)
+	run.realign_seconds = 0;
+	if (run.options.realign_reads_file != nullptr) write_realign(run); // (likewise)
 	run.supporting_seconds = 0; run.support_pool_built = false;
 	if (run.options.supporting_alignments_prefix != nullptr) build_support_pool(run); // (before after_ingest as well; the pool is this lane's own and outlives the hand-over of the stream)
 	run.sharded = false; run.first_rank = 0; run.exchanged_bytes = 0;
@@ -793,6 +869,7 @@ void note_device_ingest(Run& run, double waited_since) {
 	if (run.timing) run.timing->gene_counts = run.gene_counts_seconds;
 	if (run.timing) run.timing->splice_junctions = run.splice_junctions_seconds;
 	if (run.timing) run.timing->allele_counts = run.allele_counts_seconds;
+	if (run.timing) run.timing->realign = run.realign_seconds;
 	run.note("bam_records", run.ingest_records); // (for the report only: no line of the reference's log)
 	run.note("bam_stream_bytes", run.ingest_stream_bytes);
 }
@@ -1362,6 +1439,7 @@ void run_sample(Run& run, bool already_fed, double sample_started) {
 		if (run.ranks != nullptr) throw Failure{ "ERROR: one sample over several ranks needs read_chimeric_alignments on the device (host_ingest = 0): the parts of the batch are exchanged in device format" };
 		check_mark_duplicates(o);
 		if (check_allele_counts(run)) { ahost_allele_sites checked; host_check(ahost_allele_sites_load(o.allele_sites_file, nullptr, 0, &checked)); ahost_allele_sites_free(&checked); } // (refused before the input is read)
+		const bool realign = check_realign(run); // (refused before the input is read)
 		host_check(ahost_ingest_bam_file(run.host, o.chimeric_bam_file, o.device.external_duplicate_marking, o.device.max_itd_length));
 		if (o.sorted_bam_file != nullptr) { // (the host's stepping of the same code)
 			const double before = now_seconds();
@@ -1392,6 +1470,13 @@ void run_sample(Run& run, bool already_fed, double sample_started) {
 			host_check(ahost_allele_counts_file(run.host, o.chimeric_bam_file, o.allele_sites_file, o.allele_counts_file, o.allele_min_mapq, o.allele_min_baseq, &stats));
 			run.say(allele_counts_line(stats));
 			if (run.timing) run.timing->allele_counts = now_seconds() - before;
+		}
+		if (realign) { // (likewise)
+			const double before = now_seconds();
+			agpu_realign_stats stats;
+			host_check(ahost_realign_split_file(run.host, o.chimeric_bam_file, o.realign_reads_file, o.realign_kept_file, &stats));
+			run.say(realign_line(stats));
+			if (run.timing) run.timing->realign = now_seconds() - before;
 		}
 		device_check(agpu_upload_genome(run.device, ahost_genome_view(run.host)));
 		device_check(agpu_upload_batch(run.device, ahost_batch_view(run.host)));
@@ -1578,7 +1663,7 @@ int arriba_workflow_run(const arriba_workflow_options* options, arriba_workflow_
 struct arriba_workflow_session {
 	Run* lanes[2];
 	int processed_lane = 0; // of the sample arriba_workflow_sample worked on last
-	struct Submitted { std::string bam, sorted_bam, supporting, virus_expression, coverage, gene_counts, splice_junctions, allele_sites, allele_counts; uint32_t allele_min_mapq = 0, allele_min_baseq = 0; int sorted_bam_level = 0, mark_duplicates = 0; int lane = 0; std::thread feeder; bool fed = false, ingest_finished = false, started = false; std::string error; int error_code = 0; };
+	struct Submitted { std::string bam, sorted_bam, supporting, virus_expression, coverage, gene_counts, splice_junctions, allele_sites, allele_counts, realign_reads, realign_kept; uint32_t allele_min_mapq = 0, allele_min_baseq = 0; int sorted_bam_level = 0, mark_duplicates = 0; int lane = 0; std::thread feeder; bool fed = false, ingest_finished = false, started = false; std::string error; int error_code = 0; };
 	std::deque<std::unique_ptr<Submitted>> queue; // oldest first; at most two
 	std::mutex mutex; std::condition_variable changed;
 	bool ingest_busy = false; // a lane is between agpu_ingest_begin and agpu_ingest_finish
@@ -1589,6 +1674,7 @@ struct arriba_workflow_session {
 	std::string next_gene_counts; // arriba_workflow_gene_counts: likewise
 	std::string next_splice_junctions; // arriba_workflow_splice_junctions: likewise
 	std::string next_allele_sites, next_allele_counts; uint32_t next_allele_min_mapq = 0, next_allele_min_baseq = 13; // arriba_workflow_allele_counts: likewise
+	std::string next_realign_reads, next_realign_kept; // arriba_workflow_realign: likewise
 	int mark_duplicates = 0;  // arriba_workflow_sorted_bam_mark_duplicates: of the samples submitted from now on (at first: options.mark_duplicates of arriba_workflow_open)
 	int sorted_bam_level = 0; // arriba_workflow_sorted_bam_compression: of the samples submitted from now on (at first: options.sorted_bam_compression of arriba_workflow_open)
 	bool defer_output = false;
@@ -1664,10 +1750,12 @@ struct arriba_workflow_session {
 		run.allele_sites_path.swap(next_allele_sites); next_allele_sites.clear(); run.options.allele_sites_file = run.allele_sites_path.empty() ? nullptr : run.allele_sites_path.c_str();
 		run.allele_counts_path.swap(next_allele_counts); next_allele_counts.clear(); run.options.allele_counts_file = run.allele_counts_path.empty() ? nullptr : run.allele_counts_path.c_str();
 		run.options.allele_min_mapq = next_allele_min_mapq; run.options.allele_min_baseq = next_allele_min_baseq; next_allele_min_mapq = 0; next_allele_min_baseq = 13;
+		run.realign_reads_path.swap(next_realign_reads); next_realign_reads.clear(); run.options.realign_reads_file = run.realign_reads_path.empty() ? nullptr : run.realign_reads_path.c_str();
+		run.realign_kept_path.swap(next_realign_kept); next_realign_kept.clear(); run.options.realign_kept_file = run.realign_kept_path.empty() ? nullptr : run.realign_kept_path.c_str();
 		run.timing = nullptr; run.report = nullptr;
 		prepare_sample(run);
 		std::unique_ptr<Submitted> sample(new Submitted());
-		sample->bam = bam; sample->sorted_bam = run.sorted_bam_path; sample->supporting = run.supporting_prefix; sample->virus_expression = run.virus_expression_path; sample->coverage = run.coverage_path; sample->gene_counts = run.gene_counts_path; sample->splice_junctions = run.splice_junctions_path; sample->allele_sites = run.allele_sites_path; sample->allele_counts = run.allele_counts_path; sample->allele_min_mapq = run.options.allele_min_mapq; sample->allele_min_baseq = run.options.allele_min_baseq; sample->sorted_bam_level = sorted_bam_level; sample->mark_duplicates = mark_duplicates; sample->lane = lane;
+		sample->bam = bam; sample->sorted_bam = run.sorted_bam_path; sample->supporting = run.supporting_prefix; sample->virus_expression = run.virus_expression_path; sample->coverage = run.coverage_path; sample->gene_counts = run.gene_counts_path; sample->splice_junctions = run.splice_junctions_path; sample->allele_sites = run.allele_sites_path; sample->allele_counts = run.allele_counts_path; sample->allele_min_mapq = run.options.allele_min_mapq; sample->allele_min_baseq = run.options.allele_min_baseq; sample->realign_reads = run.realign_reads_path; sample->realign_kept = run.realign_kept_path; sample->sorted_bam_level = sorted_bam_level; sample->mark_duplicates = mark_duplicates; sample->lane = lane;
 		Submitted* mine = sample.get();
 		{ std::lock_guard<std::mutex> lock(mutex); queue.push_back(std::move(sample)); }
 		if (!run.device_ingest) { join_writer_of(lane); std::lock_guard<std::mutex> lock(mutex); mine->fed = true; return; } // (the host ingest reads the file inside arriba_workflow_sample)
@@ -1759,6 +1847,12 @@ int arriba_workflow_allele_counts(arriba_workflow_session* session, const char* 
 	return 0;
 }
 
+int arriba_workflow_realign(arriba_workflow_session* session, const char* reads_path, const char* kept_path) {
+	if (!session) { g_error = "ERROR: null argument"; return -1; }
+	session->next_realign_reads = reads_path ? reads_path : ""; session->next_realign_kept = kept_path ? kept_path : "";
+	return 0;
+}
+
 int arriba_workflow_submit(arriba_workflow_session* session, const char* chimeric_bam_file) {
 	if (!session || !chimeric_bam_file) { g_error = "ERROR: null argument"; return -1; }
 	try { session->submit(chimeric_bam_file); return 0; }
@@ -1807,7 +1901,7 @@ int arriba_workflow_sample(arriba_workflow_session* session, const char* chimeri
 	}
 	catch (const Failure& failure) { g_error = failure.text; g_error_code = failure.code; status = -1; }
 	catch (const std::exception& e) { g_error = std::string("ERROR: ") + e.what(); g_error_code = 0; status = -1; }
-	if (lane) { lane->after_ingest = nullptr; lane->before_host_writer = nullptr; lane->options.chimeric_bam_file = nullptr; lane->options.sorted_bam_file = nullptr; lane->options.supporting_alignments_prefix = nullptr; lane->options.virus_expression_file = nullptr; lane->options.coverage_file = nullptr; lane->options.gene_counts_file = nullptr; lane->options.splice_junctions_file = nullptr; lane->options.allele_sites_file = nullptr; lane->options.allele_counts_file = nullptr; lane->options.output_file = nullptr; lane->options.discarded_output_file = nullptr; lane->report = nullptr; lane->timing = nullptr; session->processed_lane = (int) (lane == session->lanes[1]); }
+	if (lane) { lane->after_ingest = nullptr; lane->before_host_writer = nullptr; lane->options.chimeric_bam_file = nullptr; lane->options.sorted_bam_file = nullptr; lane->options.supporting_alignments_prefix = nullptr; lane->options.virus_expression_file = nullptr; lane->options.coverage_file = nullptr; lane->options.gene_counts_file = nullptr; lane->options.splice_junctions_file = nullptr; lane->options.allele_sites_file = nullptr; lane->options.allele_counts_file = nullptr; lane->options.realign_reads_file = nullptr; lane->options.realign_kept_file = nullptr; lane->options.output_file = nullptr; lane->options.discarded_output_file = nullptr; lane->report = nullptr; lane->timing = nullptr; session->processed_lane = (int) (lane == session->lanes[1]); }
 	// The device ran out of memory while the session had two lanes (advisor, round 4): their contexts share one pool of scratch buffers, of which nothing is idle while one lane
 	// feeds and the other runs its stages, so the device library gives nothing back by itself (DeviceBuffer::release_idle_buffers).  The session does what INTEGRATION.md ("Memory")
 	// used to ask of the caller: what was fed ahead is thrown away, the second lane is closed -- the pool belongs to one context again, which gives back what it keeps for its next
@@ -1826,6 +1920,8 @@ int arriba_workflow_sample(arriba_workflow_session* session, const char* chimeri
 		const std::string behind_allele_sites = session->queue.empty() ? std::string() : session->queue.front()->allele_sites, again_allele_sites = lane->allele_sites_path;
 		const std::string behind_allele_counts = session->queue.empty() ? std::string() : session->queue.front()->allele_counts, again_allele_counts = lane->allele_counts_path;
 		const uint32_t behind_allele_mapq = session->queue.empty() ? 0 : session->queue.front()->allele_min_mapq, again_allele_mapq = lane->options.allele_min_mapq;
+		const std::string behind_realign_reads = session->queue.empty() ? std::string() : session->queue.front()->realign_reads, again_realign_reads = lane->realign_reads_path;
+		const std::string behind_realign_kept = session->queue.empty() ? std::string() : session->queue.front()->realign_kept, again_realign_kept = lane->realign_kept_path;
 		const uint32_t behind_allele_baseq = session->queue.empty() ? 13 : session->queue.front()->allele_min_baseq, again_allele_baseq = lane->options.allele_min_baseq;
 		session->drain();
 		session->join_writer_of(0); session->join_writer_of(1);
@@ -1835,11 +1931,11 @@ int arriba_workflow_sample(arriba_workflow_session* session, const char* chimeri
 		delete session->lanes[1]; session->lanes[1] = nullptr; session->processed_lane = 0;
 		fprintf(stderr, "arriba_workflow_sample: %s -- with two samples in flight; '%s' is run again with the device to itself\n", first_error.c_str(), chimeric_bam_file);
 		session->retrying = true;
-		session->next_sorted_bam = again_sorted_bam; session->next_supporting = again_supporting; session->next_virus_expression = again_virus; session->next_coverage = again_coverage; session->next_gene_counts = again_gene_counts; session->next_splice_junctions = again_splice_junctions; session->next_allele_sites = again_allele_sites; session->next_allele_counts = again_allele_counts; session->next_allele_min_mapq = again_allele_mapq; session->next_allele_min_baseq = again_allele_baseq; session->sorted_bam_level = again_level; session->mark_duplicates = again_marks;
+		session->next_sorted_bam = again_sorted_bam; session->next_supporting = again_supporting; session->next_virus_expression = again_virus; session->next_coverage = again_coverage; session->next_gene_counts = again_gene_counts; session->next_splice_junctions = again_splice_junctions; session->next_allele_sites = again_allele_sites; session->next_allele_counts = again_allele_counts; session->next_allele_min_mapq = again_allele_mapq; session->next_allele_min_baseq = again_allele_baseq; session->next_realign_reads = again_realign_reads; session->next_realign_kept = again_realign_kept; session->sorted_bam_level = again_level; session->mark_duplicates = again_marks;
 		status = arriba_workflow_sample(session, chimeric_bam_file, output_file, discarded_output_file, report, timing);
 		session->retrying = false;
 		if (status == 0 && !behind.empty()) { // (as its caller submitted it: a failure to feed it is reported by the call that asks for it)
-			try { session->next_sorted_bam = behind_sorted_bam; session->next_supporting = behind_supporting; session->next_virus_expression = behind_virus; session->next_coverage = behind_coverage; session->next_gene_counts = behind_gene_counts; session->next_splice_junctions = behind_splice_junctions; session->next_allele_sites = behind_allele_sites; session->next_allele_counts = behind_allele_counts; session->next_allele_min_mapq = behind_allele_mapq; session->next_allele_min_baseq = behind_allele_baseq; session->sorted_bam_level = behind_level; session->mark_duplicates = behind_marks; session->submit(behind.c_str()); }
+			try { session->next_sorted_bam = behind_sorted_bam; session->next_supporting = behind_supporting; session->next_virus_expression = behind_virus; session->next_coverage = behind_coverage; session->next_gene_counts = behind_gene_counts; session->next_splice_junctions = behind_splice_junctions; session->next_allele_sites = behind_allele_sites; session->next_allele_counts = behind_allele_counts; session->next_allele_min_mapq = behind_allele_mapq; session->next_allele_min_baseq = behind_allele_baseq; session->next_realign_reads = behind_realign_reads; session->next_realign_kept = behind_realign_kept; session->sorted_bam_level = behind_level; session->mark_duplicates = behind_marks; session->submit(behind.c_str()); }
 			catch (const Failure&) {} catch (const std::exception&) {}
 		}
 		session->sorted_bam_level = session_level; session->mark_duplicates = session_marks;

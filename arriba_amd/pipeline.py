@@ -70,6 +70,14 @@ def allele_stats_of(stats):
     return out
 
 
+def realign_stats_of(stats):
+    """agpu_realign_stats (the device's or the host's) as a dict"""
+    out = {name: int(getattr(stats, name)) for name in ("records", "templates", "realign_templates", "kept_templates", "dropped_secondary", "extra", "orphans", "placeholder_cigar", "realign_bytes", "kept_bytes", "peak_bytes")}
+    out["layout"] = "PE" if stats.layout else "SE"
+    out["seconds"] = dict(zip(("name", "verdict", "scan", "text"), stats.seconds))
+    return out
+
+
 class ArribaError(RuntimeError):
     pass
 
@@ -221,7 +229,7 @@ class WorkflowSession(object):
         if self._lib.arriba_workflow_sorted_bam_mark_duplicates(self._session, int(bool(on))) != 0:
             raise ArribaError(self._lib.arriba_workflow_last_error().decode())
 
-    def submit(self, bam, sorted_bam_file=None, supporting_alignments_prefix=None, sorted_bam_compression=None, virus_expression_file=None, coverage_file=None, mark_duplicates=None, gene_counts_file=None, splice_junctions_file=None, allele_sites_file=None, allele_counts_file=None, allele_min_mapq=0, allele_min_baseq=13):
+    def submit(self, bam, sorted_bam_file=None, supporting_alignments_prefix=None, sorted_bam_compression=None, virus_expression_file=None, coverage_file=None, mark_duplicates=None, gene_counts_file=None, splice_junctions_file=None, allele_sites_file=None, allele_counts_file=None, allele_min_mapq=0, allele_min_baseq=13, realign_reads_file=None, realign_kept_file=None):
         """the sample that comes after the one `sample` is called for next: its file is fed (PCIe, the front of read_chimeric_alignments) while the stages of that one run;
         sorted_bam_file: its records in coordinate order with their index (--sorted-bam), written when its ingest is finished; sorted_bam_compression: its level (None: as it is)"""
         if sorted_bam_compression is not None:
@@ -235,6 +243,7 @@ class WorkflowSession(object):
         self._lib.arriba_workflow_gene_counts(self._session, gene_counts_file.encode() if gene_counts_file else None)  # (--gene-counts: its reads per gene, likewise)
         self._lib.arriba_workflow_splice_junctions(self._session, splice_junctions_file.encode() if splice_junctions_file else None)  # (--splice-junctions: its junction table, likewise)
         self._lib.arriba_workflow_allele_counts(self._session, allele_sites_file.encode() if allele_sites_file else None, allele_counts_file.encode() if allele_counts_file else None, allele_min_mapq, allele_min_baseq)  # (--allele-counts: likewise)
+        self._lib.arriba_workflow_realign(self._session, realign_reads_file.encode() if realign_reads_file else None, realign_kept_file.encode() if realign_kept_file else None)  # (--realign-reads: likewise)
         if self._lib.arriba_workflow_submit(self._session, bam.encode()) != 0:
             raise ArribaError(self._lib.arriba_workflow_last_error().decode())
         if self._profiling_on:
@@ -329,7 +338,7 @@ class WorkflowSession(object):
     def _lane_contexts(self):
         return [ctx for ctx in (self._lib.arriba_workflow_lane_device(self._session, lane) for lane in (0, 1)) if ctx]
 
-    def sample(self, bam, output_file, discarded_output_file=None, sorted_bam_file=None, supporting_alignments_prefix=None, sorted_bam_compression=None, virus_expression_file=None, coverage_file=None, mark_duplicates=None, gene_counts_file=None, splice_junctions_file=None, allele_sites_file=None, allele_counts_file=None, allele_min_mapq=0, allele_min_baseq=13):
+    def sample(self, bam, output_file, discarded_output_file=None, sorted_bam_file=None, supporting_alignments_prefix=None, sorted_bam_compression=None, virus_expression_file=None, coverage_file=None, mark_duplicates=None, gene_counts_file=None, splice_junctions_file=None, allele_sites_file=None, allele_counts_file=None, allele_min_mapq=0, allele_min_baseq=13, realign_reads_file=None, realign_kept_file=None):
         """one sample, BAM file -> fusions.tsv (and discarded.tsv); returns the stages with their "(remaining=N)" counts.  sorted_bam_file (--sorted-bam): for a sample that was
         not submitted ahead; one that was says it to `submit`"""
         report, timing = _capi.WorkflowReport(), _capi.WorkflowTiming()
@@ -351,6 +360,8 @@ class WorkflowSession(object):
             self._lib.arriba_workflow_splice_junctions(self._session, splice_junctions_file.encode())
         if allele_sites_file or allele_counts_file:  # (likewise; one without the other is refused by the sample)
             self._lib.arriba_workflow_allele_counts(self._session, allele_sites_file.encode() if allele_sites_file else None, allele_counts_file.encode() if allele_counts_file else None, allele_min_mapq, allele_min_baseq)
+        if realign_reads_file or realign_kept_file:  # (likewise; the kept file without the other is refused by the sample)
+            self._lib.arriba_workflow_realign(self._session, realign_reads_file.encode() if realign_reads_file else None, realign_kept_file.encode() if realign_kept_file else None)
         if self._lib.arriba_workflow_sample(self._session, bam.encode(), output_file.encode(), discarded_output_file.encode() if discarded_output_file else None, byref(report), byref(timing)) != 0:
             raise ArribaError(self._lib.arriba_workflow_last_error().decode())
         self.ctx = self._lib.arriba_workflow_device(self._session)  # (the lane that worked on this sample)
@@ -825,6 +836,61 @@ class DevicePipeline(object):
         self._check(self.api.allele_counts_allocated_bytes(self.ctx, byref(count)))
         return int(count.value)
 
+    def realign_split(self, realign_path, kept_path=None):
+        """--realign-reads [--realign-kept]: the records of the last read_chimeric_alignments split into the templates that must be aligned again and the templates that are passed
+        on, as SAM text (fields 1-11; `kept_path` behind a header with the contigs of the assembly), decided and formatted on the device from the record stream that is still in
+        HBM (agpu_realign_*).  Valid after read_chimeric_alignments and before the next one.  Written through NAME.tmp; returns the statistics {"records",
+        "templates", "realign_templates", "kept_templates", "dropped_secondary", "extra", "orphans", "placeholder_cigar", "realign_bytes", "kept_bytes", "layout", "peak_bytes",
+        "seconds"}."""
+        import os
+        if not self.device_ingest or not hasattr(self.api, "realign_begin"):
+            raise ArribaError("ERROR: a split for realignment needs the record stream of an ingest on the device (DevicePipeline(bam=...))")
+        if kept_path is not None and os.path.abspath(kept_path) == os.path.abspath(realign_path):
+            raise ArribaError("ERROR: --realign-reads and --realign-kept name the same file")
+        lib, handle = self.session._lib, self.session._session
+        contigs, plan = _capi.DepthContigs(), _capi.RealignPlan()
+        if lib.ahost_depth_contigs_of_session(handle, byref(contigs)) != 0 or lib.ahost_realign_plan_of_session(handle, byref(plan)) != 0:
+            raise ArribaError("ERROR: " + lib.ahost_last_error().decode())
+        header = ctypes.string_at(plan.header, plan.header_bytes)
+        info, stats = _capi.RealignInfo(), _capi.RealignStats()
+        self._check(self.api.realign_begin(self.ctx, plan.in_assembly, contigs.names, contigs.name_offset, contigs.n_ref, int(kept_path is not None), byref(info)))  # (refused before anything is written)
+        paths = [path for path in (realign_path, kept_path) if path is not None]
+        try:
+            if getattr(self, "_depth_windows", None) is None or self._depth_windows[0] < info.window_bytes:  # the two pinned buffers of write_coverage: they stay with the pipeline
+                self._free_depth_windows()
+                buffers = [self.api.host_alloc(info.window_bytes) for _ in range(2)]
+                self._depth_windows = (info.window_bytes, buffers)
+                if not all(buffers):
+                    self._free_depth_windows()
+                    raise ArribaError("ERROR: " + self.api.last_error().decode())
+            capacity, buffers = self._depth_windows
+            for which, path in enumerate(paths):
+                with open(path + ".tmp", "wb") as out:
+                    if which == 1:
+                        out.write(header)
+                    got, turn = c_uint64(), 0
+                    while True:
+                        self._check(self.api.realign_next(self.ctx, which, buffers[turn & 1], capacity, byref(got)))
+                        if got.value == 0:
+                            break
+                        out.write((ctypes.c_char * got.value).from_address(buffers[turn & 1]))
+                        turn += 1
+            self._check(self.api.realign_end(self.ctx, byref(stats)))
+            for path in paths:
+                os.rename(path + ".tmp", path)
+        except BaseException:
+            self.api.realign_end(self.ctx, None)
+            for path in paths:
+                if os.path.exists(path + ".tmp"):
+                    os.remove(path + ".tmp")
+            raise
+        return realign_stats_of(stats)
+
+    def realign_allocated_bytes(self):
+        count = c_uint64()
+        self._check(self.api.realign_allocated_bytes(self.ctx, byref(count)))
+        return int(count.value)
+
     def _free_depth_windows(self):
         if getattr(self, "_depth_windows", None) is not None:
             for buffer in self._depth_windows[1]:
@@ -1101,7 +1167,7 @@ class DevicePipeline(object):
                      max_genomic_breakpoint_distance=100000, strandedness=None, evalue_cutoff=0.3,
                      min_itd_support=10, min_itd_allele_fraction=0.07, high_expression_quantile=0.998, min_spliced_events=4, min_anchor_length=23,
                      max_homolog_identity=0.3, max_itd_length=100, fill_sequence_gaps=False, top_viral_contigs=5, viral_contig_min_covered_fraction=0.05,
-                     print_extra_info_for_discarded_fusions=False, log=None, sorted_bam_file=None, supporting_alignments_prefix=None, supporting_alignments_window=1000000, virus_expression_file=None, coverage_file=None, mark_duplicates=False, gene_counts_file=None, splice_junctions_file=None, allele_sites_file=None, allele_counts_file=None, allele_min_mapq=0, allele_min_baseq=13):
+                     print_extra_info_for_discarded_fusions=False, log=None, sorted_bam_file=None, supporting_alignments_prefix=None, supporting_alignments_window=1000000, virus_expression_file=None, coverage_file=None, mark_duplicates=False, gene_counts_file=None, splice_junctions_file=None, allele_sites_file=None, allele_counts_file=None, allele_min_mapq=0, allele_min_baseq=13, realign_reads_file=None, realign_kept_file=None):
         """The reference's main() behind read_chimeric_alignments (source/arriba.cpp:119-610) with its default parameters: the read-level cascade, find_fusions,
         every candidate-level filter in the reference's order, assign_confidence, and the two output files.  `log` receives (stage, remaining) pairs --
         the numbers the reference prints as "(remaining=N)".  Filters switched off with -f are skipped by the stages themselves (agpu_params.filter_enabled)."""
@@ -1122,6 +1188,10 @@ class DevicePipeline(object):
             if not (allele_sites_file and allele_counts_file):
                 raise ArribaError("ERROR: --allele-sites and --allele-counts need each other")
             self.write_allele_counts(allele_sites_file, allele_counts_file, allele_min_mapq, allele_min_baseq)
+        if realign_reads_file or realign_kept_file:  # (--realign-reads: likewise)
+            if not realign_reads_file:
+                raise ArribaError("ERROR: --realign-kept needs --realign-reads")
+            self.realign_split(realign_reads_file, realign_kept_file)
         if supporting_alignments_prefix:  # (--supporting-alignments, phase 1: the records of the names of the batch leave the stream while it is there)
             self.build_support_pool()
         self.run_read_level(strandedness, top_viral_contigs, viral_contig_min_covered_fraction)

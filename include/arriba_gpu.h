@@ -544,6 +544,41 @@ typedef struct {
 int agpu_allele_counts(agpu_ctx* ctx, const agpu_allele_site* sites, uint64_t n_sites, const uint32_t* ref_length, uint32_t n_ref, uint32_t min_mapq, uint32_t min_baseq, const agpu_allele_row** rows,
                        agpu_allele_stats* stats /* may be NULL */);
 int agpu_allele_counts_allocated_bytes(agpu_ctx* ctx, uint64_t* bytes);
+/* --realign-reads: the records of the last ingest split into the templates that must be aligned again and the templates that are passed on, both as SAM text (fields 1-11, what
+ * `samtools view` prints), formatted on the device while the stream is in HBM (arriba_amd/csrc/device/agpu_realign.hip, realign_core.hpp).
+ *   agpu_realign_begin   behind agpu_ingest_finish, before the next agpu_ingest_begin on this context or its sibling (the refusals of agpu_depth_begin).  in_assembly: a byte per
+ *                        reference of the header of that ingest, 1 if it is a contig of the assembly (ahost_realign_plan); names, name_offset: their names, one behind the other
+ *                        (ahost_depth_contigs_of_session).  want_kept 0: only the file of the templates to realign is formatted.  It runs the name pass (paired-end only), the
+ *                        verdict pass and the scans: info and the statistics are complete when it returns.
+ *   agpu_realign_next    the next window of text of file `which` (0: realign, 1: kept -- without its header, which the host writes) into a pinned buffer of at least
+ *                        info.window_bytes; bytes 0: the file is complete.  The two files advance independently.
+ *   agpu_realign_end     frees the "realign.*" buffers (a failing _begin does so itself); stats may be NULL.  Without a _begin it does nothing.
+ *   agpu_realign_allocated_bytes   of those buffers: 0 outside begin .. end
+ * ARRIBA_REALIGN_TEXT_WINDOW (bytes of a window of text, default 16 MiB), ARRIBA_REALIGN_TEXT_FORM=lane (a knob for the measurement: one lane writes all bytes of its template
+ * instead of the wavefront sharing SEQ and QUAL), ARRIBA_REALIGN_LAUNCH_ITEMS (work-items of a launch), ARRIBA_REALIGN_HASH_BITS (bits of the name hash: the tests force collisions). */
+typedef struct {
+	uint64_t records;              /* of the stream */
+	uint64_t templates;            /* single-end: primary records; paired-end: names with a primary record.  = realign_templates + kept_templates + orphans */
+	uint64_t realign_templates, kept_templates;
+	uint64_t dropped_secondary;    /* records with 0x100 or 0x800: in neither file */
+	uint64_t extra;                /* further primary records of a claimed slot: in neither file */
+	uint64_t orphans;              /* paired-end templates that lack a slot: in neither file */
+	uint64_t placeholder_cigar;    /* written lines whose CIGAR is the placeholder of a CG field */
+	uint64_t realign_bytes, kept_bytes; /* the sums of the line lengths (kept_bytes: without the header; counted with want_kept 0 as well) */
+	uint32_t layout;               /* 0: single-end, 1: paired-end (bit 0x1 of the first record) */
+	uint32_t reserved;
+	uint64_t peak_bytes;           /* of the "realign.*" buffers (0 on the host) */
+	double seconds[4];             /* name pass, verdict pass, scans, text passes and their copies (device: from HIP events, 0 on the host) */
+} agpu_realign_stats;
+typedef struct {
+	uint64_t window_bytes;         /* the size of a window of text: the least capacity of the buffer of agpu_realign_next */
+	uint64_t realign_bytes, kept_bytes;
+	uint32_t layout, reserved;
+} agpu_realign_info;
+int agpu_realign_begin(agpu_ctx* ctx, const uint8_t* in_assembly /* [n_ref] */, const char* names, const uint32_t* name_offset /* [n_ref + 1] */, uint32_t n_ref, int want_kept, agpu_realign_info* info);
+int agpu_realign_next(agpu_ctx* ctx, int which, void* pinned, uint64_t capacity, uint64_t* bytes);
+int agpu_realign_end(agpu_ctx* ctx, agpu_realign_stats* stats /* may be NULL */);
+int agpu_realign_allocated_bytes(agpu_ctx* ctx, uint64_t* bytes);
 /* what the host's sequential stages and its output writer need from a batch that lives on the device:
  *   agpu_get_viral_read_counts   mapped_viral_reads_by_contig (source/read_chimeric_alignments.cpp:735-739)
  *   agpu_get_coverage            coverage_t as the reference holds it (16-bit saturating windows, start/end flags); sizes by coverage_window_offset

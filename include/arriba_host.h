@@ -234,6 +234,28 @@ int ahost_allele_counts_of(ahost_session* session, const void* input_header, siz
 int ahost_allele_counts_text(const ahost_allele_sites* sites, const agpu_allele_row* rows, uint64_t n_rows, const char** text, uint64_t* bytes);
 int ahost_allele_counts_write(const ahost_allele_sites* sites, const agpu_allele_row* rows, uint64_t n_rows, const char* path);
 int ahost_allele_counts_file(ahost_session* session, const char* input_path, const char* sites_path, const char* path, uint32_t min_mapq, uint32_t min_baseq, agpu_allele_stats* stats);
+/* ---- --realign-reads: the host side of agpu_realign_* (include/arriba_gpu.h) -- the records split into the templates to realign and the templates to keep, as SAM text (the
+ * rule: DESIGN.md 4.18) ----
+ *   ahost_realign_plan_of          what the split needs from the assembly of the session for the references of input_header (a BAM header, or the '@' lines of SAM text): a byte
+ *                                  per reference, 1 if it is a contig of the assembly -- the names compared as the loaders of the session compare them, a leading "chr" removed on
+ *                                  both sides --, and the header of the file of the kept templates: "@HD\tVN:1.4\tSO:unsorted\n", then "@SQ\tSN:...\tLN:...\n" per contig of the
+ *                                  assembly in the order of its file, spelled as the input spells it where the input has it.  Valid until the next call on the thread
+ *   ahost_realign_plan_of_session  the same for the file the last ahost_bam_open opened
+ *   ahost_realign_split_of         arriba_amd/csrc/device/realign_core.hpp stepped on the host over BAM records in host memory (the device's comparator; the CPU tier): the bytes
+ *                                  of the two files, the second with its header (want_kept 0: kept may be NULL).  Valid until the next call on the thread.
+ *                                  ARRIBA_REALIGN_HASH_BITS: bits of the name hash (the tests force collisions)
+ *   ahost_realign_split_file       all of it for a file (BAM in BGZF, gzip or raw; SAM text), written through NAME.tmp: what --host-ingest runs; kept_path and stats may be NULL */
+typedef struct {
+	uint32_t n_ref;
+	const uint8_t* in_assembly;     /* [n_ref] */
+	const char* header;             /* of the file of the kept templates */
+	uint64_t header_bytes;
+} ahost_realign_plan;
+int ahost_realign_plan_of(ahost_session* session, const void* input_header, size_t header_size, ahost_realign_plan* plan);
+int ahost_realign_plan_of_session(ahost_session* session, ahost_realign_plan* plan);
+int ahost_realign_split_of(ahost_session* session, const void* input_header, size_t header_size, const void* records, size_t size, int want_kept, const char** realign, uint64_t* realign_bytes, const char** kept, uint64_t* kept_bytes,
+                           agpu_realign_stats* stats /* may be NULL */);
+int ahost_realign_split_file(ahost_session* session, const char* input_path, const char* realign_path, const char* kept_path, agpu_realign_stats* stats);
 int ahost_adopt_device_ingest(ahost_session* session, const agpu_ingest_result* result, const uint64_t* viral_read_counts, const uint16_t* coverage, const uint8_t* fragment_starts, const uint8_t* fragment_ends);
 int ahost_set_batch_rows(ahost_session* session, const agpu_batch_rows* rows, const uint32_t* fragments /* [rows->n] ascending: the fragment every row holds; NULL: row k holds the fragment
                          of entry k of the read lists of the table the next ahost_write_fusions writes (the reads of a candidate next to each other; the table then carries read_filter_of_rows) */);

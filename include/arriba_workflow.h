@@ -88,6 +88,14 @@ typedef struct {
 	                                         several ranks. */
 	uint32_t allele_min_mapq;             /* --allele-min-mapq: records with a smaller MAPQ do not count; at most 255 */
 	uint32_t allele_min_baseq;            /* --allele-min-baseq: bases with a smaller quality go to LOWQ; at most 255; arriba_workflow_default_options sets 13 */
+	const char* realign_reads_file;       /* --realign-reads and --realign-kept; both NULL (and a zero-initialised struct) = none, realign_kept_file without realign_reads_file is refused. */
+	const char* realign_kept_file;        /* realign_reads_file: the templates of chimeric_bam_file that must be aligned again (unmapped, clipped at the 5' end, discordant, on a contig the
+	                                         assembly lacks) as headerless SAM lines, fields 1-11 -- what scripts/run_arriba_on_prealigned_bam.sh of the reference pipes to STAR.
+	                                         realign_kept_file: all other templates in the same form behind a header (@HD, then an @SQ line per contig of assembly_file).  Split and
+	                                         formatted behind read_chimeric_alignments from the record stream in HBM (include/arriba_gpu.h: agpu_realign_*; with host_ingest:
+	                                         the same code stepped on the host).  Paths that equal each other or another output, and directories that do not take the files, are refused
+	                                         before the feed starts.  Of arriba_workflow_run's sample; the samples of a session say theirs with arriba_workflow_realign.  Not for one sample
+	                                         over several ranks. */
 } arriba_workflow_options;
 
 /* what the reference prints as "(remaining=N)" / "(total=N)" / "(marked=N)", in the order of the stages; stage names as in the reference's source */
@@ -132,6 +140,7 @@ typedef struct { /* seconds of one sample, by part (wall clock of the calling th
 	double gene_counts;      /* --gene-counts: name ids and claims, rows and adds, the copy, the file (inside `ingest`; beside the sample in front when the ingest was finished ahead) */
 	double splice_junctions; /* --splice-junctions: counts, name ids, crossings, sorts, rows, classes, the copy, the file (inside `ingest`; beside the sample in front when the ingest was finished ahead) */
 	double allele_counts;    /* --allele-counts: the sites placed and sorted, the count, the rows, the copy, the file (inside `ingest`; beside the sample in front when the ingest was finished ahead) */
+	double realign;          /* --realign-reads: name ids and claims, verdicts, scans, the windows of text, the copies, the files (inside `ingest`; beside the sample in front when the ingest was finished ahead) */
 } arriba_workflow_timing;
 /* options->chimeric_bam_file, output_file and discarded_output_file are not used by open (they belong to a sample); NULL + arriba_workflow_last_error() on failure */
 arriba_workflow_session* arriba_workflow_open(const arriba_workflow_options* options);
@@ -167,6 +176,8 @@ int arriba_workflow_splice_junctions(arriba_workflow_session* session, const cha
 /* --allele-sites, --allele-counts, --allele-min-mapq and --allele-min-baseq of the sample that is submitted NEXT, in the same way; both paths NULL: none.  The sites file is read by
  * the call that submits the sample; the table is written by the thread that finishes its ingest. */
 int arriba_workflow_allele_counts(arriba_workflow_session* session, const char* sites_path, const char* output_path, uint32_t min_mapq, uint32_t min_baseq);
+/* --realign-reads and --realign-kept of the sample that is submitted NEXT, in the same way; both NULL: none.  The files are written by the thread that finishes its ingest. */
+int arriba_workflow_realign(arriba_workflow_session* session, const char* reads_path, const char* kept_path);
 /* (If the device runs out of memory while two samples are in flight, arriba_workflow_sample throws away what was fed ahead, closes the second lane, runs its sample again with the device
  * to itself and submits the other sample again behind it -- once; a sample that does not fit the device alone fails the call.  INTEGRATION.md, "Memory".) */
 /* on: arriba_workflow_sample returns when the last output file of the sample (-O if given, else -o) has everything it needs off the device; the file is formatted and written
