@@ -184,6 +184,25 @@ class RealignStats(ctypes.Structure):
         ("layout", c_uint32), ("reserved", c_uint32), ("peak_bytes", c_uint64), ("seconds", ctypes.c_double * 4)]
 
 
+class RegionTrack(ctypes.Structure):
+    """agpu_region_track: the annotation and the rRNA intervals as runs of bases, per contig (ahost_region_track)"""
+    _fields_ = [("id", c_uint64), ("n_contigs", c_uint32), ("contig_offset", c_void_p), ("n_runs", c_uint32), ("run_start", c_void_p), ("run_bits", c_void_p), ("run_gene", c_void_p), ("run_rank", c_void_p),
+                ("n_genes", c_uint32), ("gene_body", c_void_p)]
+
+
+class RegionTrackInfo(ctypes.Structure):
+    """ahost_region_track_info"""
+    _fields_ = [("n_contigs", c_uint32), ("runs", c_uint64), ("intervals", c_uint64), ("intervals_unknown_contig", c_uint64), ("bytes", c_uint64)]
+
+
+class RnaMetricsStats(ctypes.Structure):
+    """agpu_rna_metrics_stats: what agpu_rna_metrics / ahost_rna_metrics_of count"""
+    _fields_ = [(name, c_uint64) for name in ("records", "base_records", "blocks", "segments", "track_runs", "peak_bytes")] + [("seconds", ctypes.c_double * 1)]
+
+
+RNA_METRICS_SCALARS, RNA_METRICS_WORDS = 34, 1394  # AGPU_RNA_METRICS_SCALARS, AGPU_RNA_METRICS_WORDS
+
+
 class RealignInfo(ctypes.Structure):
     """agpu_realign_info: what agpu_realign_begin tells"""
     _fields_ = [("window_bytes", c_uint64), ("realign_bytes", c_uint64), ("kept_bytes", c_uint64), ("layout", c_uint32), ("reserved", c_uint32)]
@@ -369,6 +388,8 @@ def bind_device_api(lib, prefix="agpu_"):
         "realign_next": (c_int, [ctx, c_int, c_void_p, c_uint64, POINTER(c_uint64)]),
         "realign_end": (c_int, [ctx, POINTER(RealignStats)]),
         "realign_allocated_bytes": (c_int, [ctx, POINTER(c_uint64)]),
+        "rna_metrics": (c_int, [ctx, POINTER(RegionTrack), c_void_p, c_uint32, c_void_p, POINTER(RnaMetricsStats)]),
+        "rna_metrics_allocated_bytes": (c_int, [ctx, POINTER(c_uint64)]),
         "shard_export_size": (c_int, [ctx, POINTER(c_uint64)]),
         "shard_export": (c_int, [ctx, c_void_p, c_uint64]),
         "shard_merge": (c_int, [ctx, c_void_p, c_uint64, c_uint32, POINTER(IngestResult)]),
@@ -495,6 +516,12 @@ def bind_host_api(lib):
         "ahost_realign_plan_of_session": (c_int, [session, POINTER(RealignPlan)]),
         "ahost_realign_split_of": (c_int, [session, c_void_p, c_size_t, c_void_p, c_size_t, c_int, POINTER(c_void_p), POINTER(c_uint64), POINTER(c_void_p), POINTER(c_uint64), POINTER(RealignStats)]),
         "ahost_realign_split_file": (c_int, [session, c_char_p, c_char_p, c_char_p, POINTER(RealignStats)]),
+        "ahost_rrna_intervals_load": (c_int, [c_char_p, POINTER(c_uint64)]),
+        "ahost_region_track": (c_int, [session, c_char_p, POINTER(RegionTrack), POINTER(RegionTrackInfo)]),
+        "ahost_rna_metrics_of": (c_int, [session, c_char_p, c_void_p, c_size_t, c_void_p, c_size_t, c_void_p, c_uint64, POINTER(RnaMetricsStats)]),
+        "ahost_rna_metrics_text": (c_int, [c_void_p, c_uint64, POINTER(c_void_p), POINTER(c_uint64)]),
+        "ahost_rna_metrics_write": (c_int, [c_void_p, c_uint64, c_char_p]),
+        "ahost_rna_metrics_file": (c_int, [session, c_char_p, c_char_p, c_char_p, POINTER(RnaMetricsStats)]),
         "ahost_set_batch_rows": (c_int, [session, POINTER(BatchRows), c_void_p]),
         "ahost_fusion_table_reads": (c_int, [POINTER(FusionTable), c_int, c_void_p, c_uint64, POINTER(c_uint64)]),
         "ahost_read_length_sum_of": (c_float, [c_float, c_void_p, c_void_p, c_uint64]),
@@ -517,7 +544,7 @@ class WorkflowOptions(ctypes.Structure):
                                               "protein_domains_file", "genomic_breakpoints_file", "interesting_contigs", "viral_contigs", "gtf_features")] + [
         ("device", Params), ("min_itd_support", c_uint32), ("min_itd_allele_fraction", c_float), ("high_expression_quantile", c_float), ("min_spliced_events", c_uint32), ("min_anchor_length", c_uint32),
         ("max_homolog_identity", c_float), ("top_viral_contigs", c_uint32), ("viral_contig_min_covered_fraction", c_float), ("max_genomic_breakpoint_distance", c_int32),
-        ("print_extra_info_for_discarded_fusions", c_uint8), ("fill_sequence_gaps", c_uint8), ("device_index", c_int), ("log_to_stdout", c_uint8), ("host_ingest", c_uint8), ("sorted_bam_file", c_char_p), ("supporting_alignments_prefix", c_char_p), ("supporting_alignments_window", ctypes.c_int64), ("sorted_bam_compression", c_int), ("virus_expression_file", c_char_p), ("coverage_file", c_char_p), ("mark_duplicates", c_int), ("gene_counts_file", c_char_p), ("splice_junctions_file", c_char_p), ("allele_sites_file", c_char_p), ("allele_counts_file", c_char_p), ("allele_min_mapq", c_uint32), ("allele_min_baseq", c_uint32), ("realign_reads_file", c_char_p), ("realign_kept_file", c_char_p)]
+        ("print_extra_info_for_discarded_fusions", c_uint8), ("fill_sequence_gaps", c_uint8), ("device_index", c_int), ("log_to_stdout", c_uint8), ("host_ingest", c_uint8), ("sorted_bam_file", c_char_p), ("supporting_alignments_prefix", c_char_p), ("supporting_alignments_window", ctypes.c_int64), ("sorted_bam_compression", c_int), ("virus_expression_file", c_char_p), ("coverage_file", c_char_p), ("mark_duplicates", c_int), ("gene_counts_file", c_char_p), ("splice_junctions_file", c_char_p), ("allele_sites_file", c_char_p), ("allele_counts_file", c_char_p), ("allele_min_mapq", c_uint32), ("allele_min_baseq", c_uint32), ("realign_reads_file", c_char_p), ("realign_kept_file", c_char_p), ("rna_metrics_file", c_char_p), ("rrna_intervals_file", c_char_p)]
 
 
 class WorkflowStage(ctypes.Structure):
@@ -529,7 +556,7 @@ class WorkflowReport(ctypes.Structure):
 
 
 class WorkflowTiming(ctypes.Structure):
-    _fields_ = [(name, ctypes.c_double) for name in ("total", "feed", "ingest", "adopt", "stages", "filter_mismappers", "output", "output_results", "output_rows", "output_format", "feed_read", "feed_push", "feed_total", "exchange_parts", "exchange_verdicts", "exchange_rows", "shard_fragments", "exchanged_bytes", "sorted_bam", "supporting_alignments", "virus_expression", "coverage", "gene_counts", "splice_junctions", "allele_counts", "realign")]
+    _fields_ = [(name, ctypes.c_double) for name in ("total", "feed", "ingest", "adopt", "stages", "filter_mismappers", "output", "output_results", "output_rows", "output_format", "feed_read", "feed_push", "feed_total", "exchange_parts", "exchange_verdicts", "exchange_rows", "shard_fragments", "exchanged_bytes", "sorted_bam", "supporting_alignments", "virus_expression", "coverage", "gene_counts", "splice_junctions", "allele_counts", "realign", "rna_metrics")]
 
 
 WORKFLOW_MAX, WORKFLOW_MIN, WORKFLOW_SUM = 0, 1, 2
@@ -568,6 +595,7 @@ def workflow_library():
         lib.arriba_workflow_splice_junctions.argtypes = [c_void_p, c_char_p]; lib.arriba_workflow_splice_junctions.restype = c_int
         lib.arriba_workflow_allele_counts.argtypes = [c_void_p, c_char_p, c_char_p, c_uint32, c_uint32]; lib.arriba_workflow_allele_counts.restype = c_int
         lib.arriba_workflow_realign.argtypes = [c_void_p, c_char_p, c_char_p]; lib.arriba_workflow_realign.restype = c_int
+        lib.arriba_workflow_rna_metrics.argtypes = [c_void_p, c_char_p, c_char_p]; lib.arriba_workflow_rna_metrics.restype = c_int
         lib.arriba_workflow_sorted_bam_compression.argtypes = [c_void_p, c_int]; lib.arriba_workflow_sorted_bam_compression.restype = c_int
         lib.arriba_workflow_sorted_bam_mark_duplicates.argtypes = [c_void_p, c_int]; lib.arriba_workflow_sorted_bam_mark_duplicates.restype = c_int
         lib.arriba_workflow_cancel.argtypes = [c_void_p]; lib.arriba_workflow_cancel.restype = c_int

@@ -68,6 +68,7 @@ bool DeviceBuffer::release_idle_buffers() {
 		if (ctx->virus.active) continue; // (agpu_virus_expression reads the stream)
 		if (ctx->depth.active) continue; // (between agpu_depth_begin and _end: the mark kernel reads the stream)
 		if (ctx->genecount.active) continue; // (agpu_gene_counts reads the stream)
+		if (ctx->rnametrics.active) continue; // (agpu_rna_metrics reads the stream)
 		if (ctx->junction.active) continue; // (agpu_splice_junctions reads the stream)
 		if (ctx->allele.active) continue; // (agpu_allele_counts reads the stream)
 		if (ctx->realign.active) continue; // (between agpu_realign_begin and _end: the text kernels read the stream)

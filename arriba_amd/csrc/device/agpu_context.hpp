@@ -200,6 +200,18 @@ struct RealignState {
 	agpu_realign_stats stats = {};
 	hipEvent_t events[2] = { nullptr, nullptr };
 };
+// --rna-metrics (agpu_rnametrics.hip): the "rnametrics.*" buffers are the context's own.  The copy of the region track stays from the first agpu_rna_metrics that brings it until
+// another track comes or the context goes; the counter block and the lengths live inside one call
+struct RnametricsState {
+	std::map<std::string, DeviceBuffer> buffers;
+	DeviceBuffer& buffer(const char* name) { return buffers[name]; }
+	void release_all() { for (std::map<std::string, DeviceBuffer>::iterator b = buffers.begin(); b != buffers.end(); ++b) b->second.release(); }
+	uint64_t allocated() const { uint64_t sum = 0; for (std::map<std::string, DeviceBuffer>::const_iterator b = buffers.begin(); b != buffers.end(); ++b) sum += b->second.capacity; return sum; }
+	bool active = false;
+	uint64_t track_id = 0; // of the track on the device (0: none)
+	agpu_region_track track = {}; // ... with device pointers
+	agpu_rna_metrics_stats stats = {};
+};
 }
 struct agpu_ctx {
 	explicit agpu_ctx(std::shared_ptr<agpu::ScratchPool> shared = std::shared_ptr<agpu::ScratchPool>()) : pool(shared ? shared : std::make_shared<agpu::ScratchPool>()),
@@ -293,6 +305,7 @@ struct agpu_ctx {
 	agpu::GenecountState genecount; // --gene-counts (agpu_genecount.hip)
 	agpu::JunctionState junction;   // --splice-junctions (agpu_junctions.hip)
 	agpu::AlleleState allele;       // --allele-counts (agpu_alleles.hip)
+	agpu::RnametricsState rnametrics; // --rna-metrics (agpu_rnametrics.hip)
 	agpu::RealignState realign;     // --realign-reads (agpu_realign.hip)
 	// A pushed piece: copied on the context's stream (piece_copied: the caller's buffer is free), unwrapped and CRC-checked on a stream of its own (piece_stream; piece_ready: its
 	// bytes are in the stream, piece_done: the raw bytes are not needed any more), so that the copy of the next piece never waits for a kernel; AGPU_PIECE_SLOTS raw buffers in turn

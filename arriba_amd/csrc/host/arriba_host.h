@@ -322,6 +322,21 @@ std::string allele_counts_text(const AlleleSiteList& list, const agpu_allele_row
 struct RealignPlan { std::vector<uint8_t> in_assembly; std::string header; };
 void realign_plan_of(const Assembly& assembly, const uint8_t* header, size_t size, RealignPlan& plan);
 void realign_split_of(const uint8_t* in_assembly, const ahost_depth_contigs& contigs, const uint8_t* records, uint64_t size, bool want_kept, std::string& realign, std::string& kept, agpu_realign_stats& stats);
+// --rna-metrics on the host (region_track.cpp, rna_metrics.cpp): the lines of an rRNA interval file (BED); the region track of an annotation and those intervals -- runs of bases
+// with equal bits and body gene per contig (include/arriba_gpu.h: agpu_region_track) --; arriba_amd/csrc/device/rnametrics_core.hpp stepped over records in host memory against a
+// track -- the comparator of agpu_rnametrics.hip, and what --host-ingest and the CPU tier run; and the text of the file from a counter block, the host's or the device's
+struct RrnaInterval { std::string contig; int64_t start, end; }; // 0-based, half open, the contig as the file spells it
+void rrna_intervals_parse(const std::string& path, std::vector<RrnaInterval>& intervals); // refusals name the line
+struct RegionTrack {
+	uint64_t id = 0;
+	std::vector<uint32_t> contig_offset; std::vector<int32_t> run_start; std::vector<uint8_t> run_bits; std::vector<uint32_t> run_gene, run_rank, gene_body;
+	uint64_t intervals = 0, intervals_unknown_contig = 0;
+	agpu_region_track view() const;
+};
+void region_track_build(const Annotation& annotation, const Contigs& contigs, size_t n_contigs, const std::vector<RrnaInterval>& intervals, RegionTrack& track);
+void rna_metrics_of(const agpu_region_track& track, const std::vector<uint32_t>& tid_to_contig, const std::vector<uint32_t>& ref_length, const uint8_t* records, uint64_t size, std::vector<uint64_t>& counters,
+                    agpu_rna_metrics_stats& stats); // counters: [AGPU_RNA_METRICS_WORDS]
+std::string rna_metrics_text(const uint64_t* counters);
 const std::vector<uint8_t>& bam_feed_header_bytes(BamFeed* feed); // the head of the uncompressed input as the feed read it: the BAM header, or the '@' lines of SAM text
 
 // reference: source/read_chimeric_alignments.cpp:560-773 with separate_chimeric_bam_file=false, is_rna_bam_file=true

@@ -85,6 +85,8 @@ struct ahost_session {
 	~ahost_session() { if (feed) close_bam_feed(feed); }
 	std::map<std::pair<contig_t, contig_t>, bool> related_viruses;
 	std::string name_scratch;
+	size_t contigs_at_open = 0; // the contigs of the assembly and the annotation: ids below this were not learnt from the header of an input
+	std::map<std::string, std::unique_ptr<RegionTrack> > region_tracks; std::mutex region_track_mutex; // --rna-metrics: a track per interval file ("" = none), built when first asked for
 
 	void build_reference_views() {
 		size_t G = annotation.genes.size(), E = annotation.exons.size();
@@ -433,6 +435,7 @@ ahost_session* ahost_open(const char* fasta_path, const char* gtf_path, const ch
 		compute_exonic_length(session->annotation, session->exon_index);
 		session->build_reference_views();
 		session->build_genome_view();
+		session->contigs_at_open = session->contigs.size();
 		return session.release();
 	} catch (const std::exception& e) {
 		g_error = e.what();
@@ -1131,6 +1134,82 @@ int ahost_realign_split_file(ahost_session* session, const char* input_path, con
 		realign_split_of(plan.in_assembly.data(), contigs.view(), stream.data() + at, stream.size() - at, kept_path != nullptr, realign, kept, counted);
 		realign_write(realign, plan.header + kept, realign_path, kept_path);
 		if (stats) *stats = counted;
+		return 0;
+	} catch (const std::exception& e) { g_error = e.what(); return -1; }
+}
+
+// ---- --rna-metrics (include/arriba_host.h) ----
+namespace {
+thread_local std::string g_rna_metrics_text;
+// the track of the session for an interval file (NULL or "": no rRNA intervals), built and kept when it is asked for first
+const RegionTrack& region_track_of(ahost_session* session, const char* rrna_intervals_path) {
+	const std::string key = rrna_intervals_path ? rrna_intervals_path : "";
+	std::lock_guard<std::mutex> lock(session->region_track_mutex);
+	std::unique_ptr<RegionTrack>& slot = session->region_tracks[key];
+	if (!slot) {
+		try {
+			std::vector<RrnaInterval> intervals;
+			if (!key.empty()) rrna_intervals_parse(key, intervals);
+			std::unique_ptr<RegionTrack> built(new RegionTrack());
+			region_track_build(session->annotation, session->contigs, session->contigs_at_open, intervals, *built);
+			slot = std::move(built);
+		} catch (...) { session->region_tracks.erase(key); throw; }
+	}
+	return *slot;
+}
+void rna_metrics_checked(uint64_t n_counters) { if (n_counters != AGPU_RNA_METRICS_WORDS) throw std::runtime_error("rna metrics: a counter block has " + std::to_string((unsigned) AGPU_RNA_METRICS_WORDS) + " words"); }
+}
+int ahost_rrna_intervals_load(const char* path, uint64_t* n_intervals) {
+	if (!path) { g_error = "null argument"; return -1; }
+	try { std::vector<RrnaInterval> intervals; rrna_intervals_parse(path, intervals); if (n_intervals) *n_intervals = intervals.size(); return 0; }
+	catch (const std::exception& e) { g_error = e.what(); return -1; }
+}
+int ahost_region_track(ahost_session* session, const char* rrna_intervals_path, agpu_region_track* track, ahost_region_track_info* info) {
+	if (!session || !track) { g_error = "null argument"; return -1; }
+	try {
+		const RegionTrack& built = region_track_of(session, rrna_intervals_path);
+		*track = built.view();
+		if (info) {
+			info->n_contigs = track->n_contigs; info->runs = track->n_runs; info->intervals = built.intervals; info->intervals_unknown_contig = built.intervals_unknown_contig;
+			info->bytes = (uint64_t) (track->n_contigs + 1) * 4 + (uint64_t) track->n_runs * 13 + (uint64_t) track->n_genes * 4;
+		}
+		return 0;
+	} catch (const std::exception& e) { g_error = e.what(); return -1; }
+}
+int ahost_rna_metrics_of(ahost_session* session, const char* rrna_intervals_path, const void* input_header, size_t header_size, const void* records, size_t size, uint64_t* counters, uint64_t n_counters, agpu_rna_metrics_stats* stats) {
+	if (!session || (!input_header && header_size > 0) || (!records && size > 0) || !counters) { g_error = "null argument"; return -1; }
+	try {
+		rna_metrics_checked(n_counters);
+		const RegionTrack& track = region_track_of(session, rrna_intervals_path);
+		std::vector<uint32_t> tid_to_contig, ref_length; std::vector<uint64_t> counted; agpu_rna_metrics_stats counted_stats;
+		if (header_size > 0) gene_count_references(session, (const uint8_t*) input_header, header_size, tid_to_contig, ref_length);
+		rna_metrics_of(track.view(), tid_to_contig, ref_length, (const uint8_t*) records, size, counted, counted_stats);
+		memcpy(counters, counted.data(), counted.size() * 8);
+		if (stats) *stats = counted_stats;
+		return 0;
+	} catch (const std::exception& e) { g_error = e.what(); return -1; }
+}
+int ahost_rna_metrics_text(const uint64_t* counters, uint64_t n_counters, const char** text, uint64_t* bytes) {
+	if (!counters || !text || !bytes) { g_error = "null argument"; return -1; }
+	try { rna_metrics_checked(n_counters); g_rna_metrics_text = rna_metrics_text(counters); *text = g_rna_metrics_text.data(); *bytes = g_rna_metrics_text.size(); return 0; }
+	catch (const std::exception& e) { g_error = e.what(); return -1; }
+}
+int ahost_rna_metrics_write(const uint64_t* counters, uint64_t n_counters, const char* path) {
+	if (!counters || !path) { g_error = "null argument"; return -1; }
+	try { rna_metrics_checked(n_counters); virus_expression_write(rna_metrics_text(counters), path); return 0; } // (the writer of a text through path.tmp)
+	catch (const std::exception& e) { g_error = e.what(); return -1; }
+}
+int ahost_rna_metrics_file(ahost_session* session, const char* input_path, const char* rrna_intervals_path, const char* path, agpu_rna_metrics_stats* stats) {
+	if (!session || !input_path || !path) { g_error = "null argument"; return -1; }
+	try {
+		const RegionTrack& track = region_track_of(session, rrna_intervals_path); // (an interval file that does not parse is refused before the input is read)
+		std::vector<uint8_t> stream;
+		const uint64_t at = read_whole_bam(input_path, stream); // (SAM text comes out as the BAM stream of its alignments, behind a BAM header)
+		std::vector<uint32_t> tid_to_contig, ref_length; std::vector<uint64_t> counted; agpu_rna_metrics_stats counted_stats;
+		gene_count_references(session, stream.data(), at, tid_to_contig, ref_length);
+		rna_metrics_of(track.view(), tid_to_contig, ref_length, stream.data() + at, stream.size() - at, counted, counted_stats);
+		virus_expression_write(rna_metrics_text(counted.data()), path);
+		if (stats) *stats = counted_stats;
 		return 0;
 	} catch (const std::exception& e) { g_error = e.what(); return -1; }
 }

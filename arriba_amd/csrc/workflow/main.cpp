@@ -82,7 +82,10 @@ void usage() {
 	             " --allele-min-mapq N  records with a smaller MAPQ do not count (default 0)    --allele-min-baseq N  bases with a smaller quality go to LOWQ (default 13)\n"
 	             " --realign-reads FILE [--realign-kept FILE]  the templates of -x that must be aligned again -- unmapped, clipped by 10 or more bases at the 5' end, discordant, or on a\n"
 	             "                    contig that -a lacks -- as headerless SAM lines (fields 1-11) for STAR --readFilesType SAM; --realign-kept gets all other templates behind a header\n"
-	             "                    with the contigs of -a: what scripts/run_arriba_on_prealigned_bam.sh of arriba feeds to STAR and passes on\n";
+	             "                    with the contigs of -a: what scripts/run_arriba_on_prealigned_bam.sh of arriba feeds to STAR and passes on\n"
+	             " --rna-metrics FILE [--rrna-intervals FILE.bed]  the alignment QC table of -x: records by flag, MAPQ histogram, aligned bases by class (ribosomal -- the intervals of the BED\n"
+	             "                    file --, coding, UTR, intronic, intergenic), sense and antisense records, insert sizes with their median, and the coverage of gene bodies from 5' to\n"
+	             "                    3' in 100 bins: what Picard CollectRnaSeqMetrics / CollectInsertSizeMetrics, samtools flagstat and RSeQC are run for\n";
 }
 
 }
@@ -121,6 +124,8 @@ int main(int argc, char** argv) {
 		else if (strcmp(argv[a], "--allele-counts") == 0 && a + 1 < argc) { options.allele_counts_file = argv[++a]; parent_exists(options.allele_counts_file); }
 		else if (strcmp(argv[a], "--realign-reads") == 0 && a + 1 < argc) { options.realign_reads_file = argv[++a]; parent_exists(options.realign_reads_file); }
 		else if (strcmp(argv[a], "--realign-kept") == 0 && a + 1 < argc) { options.realign_kept_file = argv[++a]; parent_exists(options.realign_kept_file); }
+		else if (strcmp(argv[a], "--rna-metrics") == 0 && a + 1 < argc) { options.rna_metrics_file = argv[++a]; parent_exists(options.rna_metrics_file); }
+		else if (strcmp(argv[a], "--rrna-intervals") == 0 && a + 1 < argc) { options.rrna_intervals_file = argv[++a]; readable(options.rrna_intervals_file); }
 		else if (strcmp(argv[a], "--allele-min-mapq") == 0 && a + 1 < argc) { long value; require(parse_int(argv[++a], value) && value >= 0 && value <= 0xFFFFFFFFl, "invalid argument to --allele-min-mapq"); options.allele_min_mapq = (uint32_t) value; }
 		else if (strcmp(argv[a], "--allele-min-baseq") == 0 && a + 1 < argc) { long value; require(parse_int(argv[++a], value) && value >= 0 && value <= 0xFFFFFFFFl, "invalid argument to --allele-min-baseq"); options.allele_min_baseq = (uint32_t) value; }
 		else if (strcmp(argv[a], "--supporting-window") == 0 && a + 1 < argc) { long window; require(parse_int(argv[++a], window) && window > 0 && window <= 0x7FFFFFFFl, "invalid argument to --supporting-window"); options.supporting_alignments_window = window; }
@@ -129,6 +134,7 @@ int main(int argc, char** argv) {
 	}
 	require(!compression_given || options.sorted_bam_file != nullptr, "--sorted-bam-compression needs --sorted-bam");
 	require(!options.mark_duplicates || options.sorted_bam_file != nullptr, "--mark-duplicates needs --sorted-bam");
+	require(options.rrna_intervals_file == nullptr || options.rna_metrics_file != nullptr, "--rrna-intervals needs --rna-metrics");
 	std::string interesting_contigs, viral_contigs;
 	bool seen[256]; memset(seen, 0, sizeof(seen));
 	bool blacklist_enabled = true;

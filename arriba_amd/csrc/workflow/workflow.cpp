@@ -61,6 +61,8 @@ extern "C" int agpu_allele_counts(agpu_ctx* ctx, const agpu_allele_site* sites, 
 extern "C" int agpu_realign_begin(agpu_ctx* ctx, const uint8_t* in_assembly, const char* names, const uint32_t* name_offset, uint32_t n_ref, int want_kept, agpu_realign_info* info) __attribute__((weak));
 extern "C" int agpu_realign_next(agpu_ctx* ctx, int which, void* pinned, uint64_t capacity, uint64_t* bytes) __attribute__((weak));
 extern "C" int agpu_realign_end(agpu_ctx* ctx, agpu_realign_stats* stats) __attribute__((weak));
+// ... and the one of --rna-metrics
+extern "C" int agpu_rna_metrics(agpu_ctx* ctx, const agpu_region_track* track, const uint32_t* ref_length, uint32_t n_ref, uint64_t* counters, agpu_rna_metrics_stats* stats) __attribute__((weak));
 
 namespace {
 
@@ -111,7 +113,7 @@ struct Run {
 	// read_chimeric_alignments in two halves (feed_file: the bytes of the file into HBM, on a thread of its own when the sample was submitted ahead; finish_device_ingest: what is
 	// left behind the last piece): what the first half leaves for the second
 	bool bam_open = false; uint64_t coverage_windows = 0; uint32_t bam_contigs = 0; double feed_started = 0, feed_finished = 0, feed_reading = 0, feed_pushing = 0;
-	std::string bam_path, output_path, discarded_path, sorted_bam_path, supporting_prefix, virus_expression_path, coverage_path, gene_counts_path, splice_junctions_path, allele_sites_path, allele_counts_path, realign_reads_path, realign_kept_path; // of the sample this lane works on (options.* point at them)
+	std::string bam_path, output_path, discarded_path, sorted_bam_path, supporting_prefix, virus_expression_path, coverage_path, gene_counts_path, splice_junctions_path, allele_sites_path, allele_counts_path, realign_reads_path, realign_kept_path, rna_metrics_path, rrna_intervals_path; // of the sample this lane works on (options.* point at them)
 	double sorted_bam_seconds = 0; // --sorted-bam of the sample at work
 	double virus_expression_seconds = 0; // --virus-expression of the sample at work
 	double coverage_seconds = 0; // --coverage of the sample at work
@@ -119,6 +121,7 @@ struct Run {
 	double splice_junctions_seconds = 0; // --splice-junctions of the sample at work
 	double allele_counts_seconds = 0; // --allele-counts of the sample at work
 	double realign_seconds = 0; // --realign-reads of the sample at work
+	double rna_metrics_seconds = 0; // --rna-metrics of the sample at work
 	ahost_allele_sites allele_sites = {}; // --allele-sites of the sample at work: read (and refused) before the feed, placed on the references of the header behind it
 	double supporting_seconds = 0; bool support_pool_built = false; // --supporting-alignments of the sample at work: the pool behind the ingest and the files behind fusions.tsv
 	std::function<void()> after_ingest; // a session with two lanes: the stream and the tables of the ingest are free for the feed of the next sample
@@ -157,7 +160,7 @@ struct Run {
 	Run(const arriba_workflow_options& o): options(o), report(nullptr), timing(nullptr), host(nullptr), device(nullptr), dummy_genes(0), n_candidates(0), n_fragments(0), mapped_reads(0), device_ingest(false) {
 		for (int k = 0; k < FEED_BUFFERS; ++k) { pieces[k] = nullptr; tables[k] = nullptr; }
 		const char** texts[] = { &options.assembly_file, &options.gene_annotation_file, &options.chimeric_bam_file, &options.output_file, &options.discarded_output_file, &options.blacklist_file, &options.known_fusions_file,
-		                         &options.tags_file, &options.protein_domains_file, &options.genomic_breakpoints_file, &options.interesting_contigs, &options.viral_contigs, &options.gtf_features, &options.sorted_bam_file, &options.supporting_alignments_prefix, &options.virus_expression_file, &options.coverage_file, &options.gene_counts_file, &options.splice_junctions_file, &options.allele_sites_file, &options.allele_counts_file, &options.realign_reads_file, &options.realign_kept_file };
+		                         &options.tags_file, &options.protein_domains_file, &options.genomic_breakpoints_file, &options.interesting_contigs, &options.viral_contigs, &options.gtf_features, &options.sorted_bam_file, &options.supporting_alignments_prefix, &options.virus_expression_file, &options.coverage_file, &options.gene_counts_file, &options.splice_junctions_file, &options.allele_sites_file, &options.allele_counts_file, &options.realign_reads_file, &options.realign_kept_file, &options.rna_metrics_file, &options.rrna_intervals_file };
 		strings.reserve(sizeof(texts) / sizeof(texts[0]));
 		for (size_t k = 0; k < sizeof(texts) / sizeof(texts[0]); ++k) if (*texts[k] != nullptr) { strings.push_back(*texts[k]); *texts[k] = strings.back().c_str(); }
 	}
@@ -296,6 +299,20 @@ bool check_realign(const Run& run) {
 	return true;
 }
 
+std::string rna_metrics_line(const agpu_rna_metrics_stats& c) {
+	std::ostringstream text;
+	text << "Collecting RNA-seq metrics (records=" << c.records << ", base_records=" << c.base_records << ", blocks=" << c.blocks << ", segments=" << c.segments << ", track_runs=" << c.track_runs << ")";
+	return text.str();
+}
+// --rna-metrics / --rrna-intervals: what can be refused without the input; true if the option is on
+bool check_rna_metrics(const Run& run) {
+	const arriba_workflow_options& o = run.options;
+	if (o.rna_metrics_file == nullptr && o.rrna_intervals_file == nullptr) return false;
+	if (o.rna_metrics_file == nullptr) throw Failure{ "ERROR: --rrna-intervals needs --rna-metrics: the file the table goes to" };
+	if (run.ranks != nullptr) throw Failure{ "ERROR: rna metrics of one sample over several GPUs are not supported" };
+	return true;
+}
+
 void feed_file(Run& run) {
 	const arriba_workflow_options& o = run.options;
 	const double started = now_seconds();
@@ -317,6 +334,11 @@ void feed_file(Run& run) {
 	if (check_allele_counts(run)) {
 		if (!agpu_allele_counts) throw Failure{ "ERROR: --allele-counts needs the device library (agpu_allele_counts), which this build is not linked with" }; // (likewise)
 		host_check(ahost_allele_sites_load(o.allele_sites_file, nullptr, 0, &run.allele_sites)); // (a sites file that does not parse is refused here; its lines are placed when the header is known)
+	}
+	if (check_rna_metrics(run)) {
+		if (!agpu_rna_metrics) throw Failure{ "ERROR: --rna-metrics needs the device library (agpu_rna_metrics), which this build is not linked with" }; // (likewise)
+		agpu_region_track track;
+		host_check(ahost_region_track(run.host, o.rrna_intervals_file, &track, nullptr)); // (an interval file that does not parse is refused here; the track of the session is built once and kept)
 	}
 	agpu_ingest_config config;
 	if (run.ranks != nullptr) host_check(ahost_bam_open_part(run.host, o.chimeric_bam_file, o.device.external_duplicate_marking, o.device.max_itd_length, run.ranks->rank, run.ranks->size, &config)); // this rank's part of the records
@@ -749,6 +771,26 @@ void write_realign(Run& run) {
 	run.realign_seconds = now_seconds() - started;
 }
 
+// --rna-metrics: behind the ingest, while the stream is in HBM, the QC table of its records (include/arriba_gpu.h: agpu_rna_metrics).  The host builds the region
+// track of the session (once per interval file); the device sums; the host turns the counter block into text and writes it through FILE.tmp.  On a failure nothing is left and the
+// sample fails with the message.
+void write_rna_metrics(Run& run) {
+	if (!agpu_rna_metrics) throw Failure{ "ERROR: --rna-metrics needs the device library (agpu_rna_metrics), which this build is not linked with" };
+	const double started = now_seconds();
+	agpu_region_track track;
+	host_check(ahost_region_track(run.host, run.options.rrna_intervals_file, &track, nullptr));
+	ahost_depth_contigs contigs;
+	host_check(ahost_depth_contigs_of_session(run.host, &contigs)); // (LN of the references of the header)
+	std::vector<uint64_t> counters(AGPU_RNA_METRICS_WORDS, 0);
+	agpu_rna_metrics_stats stats;
+	const int status = agpu_rna_metrics(run.device, &track, contigs.length, contigs.n_ref, counters.data(), &stats);
+	if (status == AGPU_ERR_NO_MEMORY) throw Failure{ std::string("ERROR: --rna-metrics: ") + agpu_last_error(), status };
+	device_check(status);
+	host_check(ahost_rna_metrics_write(counters.data(), counters.size(), run.options.rna_metrics_file));
+	run.say(rna_metrics_line(stats));
+	run.rna_metrics_seconds = now_seconds() - started;
+}
+
 // --supporting-alignments, phase 1: behind the ingest, while the stream is in HBM, the records of the read names of the batch go into a pool of this lane's context
 // (include/arriba_gpu.h: agpu_support_pool_build).  Phase 2 follows when the rows of fusions.tsv are fixed (write_supporting_alignments).
 void build_support_pool(Run& run) {
@@ -837,6 +879,8 @@ void finish_device_ingest(Run& run, double waited_since) {
 	if (run.options.allele_counts_file != nullptr) write_allele_counts(run); // (likewise)
 	run.realign_seconds = 0;
 	if (run.options.realign_reads_file != nullptr) write_realign(run); // (likewise)
+	run.rna_metrics_seconds = 0;
+	if (run.options.rna_metrics_file != nullptr) write_rna_metrics(run); // (likewise)
 	run.supporting_seconds = 0; run.support_pool_built = false;
 	if (run.options.supporting_alignments_prefix != nullptr) build_support_pool(run); // (before after_ingest as well; the pool is this lane's own and outlives the hand-over of the stream)
 	run.sharded = false; run.first_rank = 0; run.exchanged_bytes = 0;
@@ -870,6 +914,7 @@ void note_device_ingest(Run& run, double waited_since) {
 	if (run.timing) run.timing->splice_junctions = run.splice_junctions_seconds;
 	if (run.timing) run.timing->allele_counts = run.allele_counts_seconds;
 	if (run.timing) run.timing->realign = run.realign_seconds;
+	if (run.timing) run.timing->rna_metrics = run.rna_metrics_seconds;
 	run.note("bam_records", run.ingest_records); // (for the report only: no line of the reference's log)
 	run.note("bam_stream_bytes", run.ingest_stream_bytes);
 }
@@ -1440,6 +1485,7 @@ void run_sample(Run& run, bool already_fed, double sample_started) {
 		check_mark_duplicates(o);
 		if (check_allele_counts(run)) { ahost_allele_sites checked; host_check(ahost_allele_sites_load(o.allele_sites_file, nullptr, 0, &checked)); ahost_allele_sites_free(&checked); } // (refused before the input is read)
 		const bool realign = check_realign(run); // (refused before the input is read)
+		if (check_rna_metrics(run)) { agpu_region_track track; host_check(ahost_region_track(run.host, o.rrna_intervals_file, &track, nullptr)); } // (likewise)
 		host_check(ahost_ingest_bam_file(run.host, o.chimeric_bam_file, o.device.external_duplicate_marking, o.device.max_itd_length));
 		if (o.sorted_bam_file != nullptr) { // (the host's stepping of the same code)
 			const double before = now_seconds();
@@ -1477,6 +1523,13 @@ void run_sample(Run& run, bool already_fed, double sample_started) {
 			host_check(ahost_realign_split_file(run.host, o.chimeric_bam_file, o.realign_reads_file, o.realign_kept_file, &stats));
 			run.say(realign_line(stats));
 			if (run.timing) run.timing->realign = now_seconds() - before;
+		}
+		if (o.rna_metrics_file != nullptr) { // (likewise)
+			const double before = now_seconds();
+			agpu_rna_metrics_stats stats;
+			host_check(ahost_rna_metrics_file(run.host, o.chimeric_bam_file, o.rrna_intervals_file, o.rna_metrics_file, &stats));
+			run.say(rna_metrics_line(stats));
+			if (run.timing) run.timing->rna_metrics = now_seconds() - before;
 		}
 		device_check(agpu_upload_genome(run.device, ahost_genome_view(run.host)));
 		device_check(agpu_upload_batch(run.device, ahost_batch_view(run.host)));
@@ -1663,7 +1716,7 @@ int arriba_workflow_run(const arriba_workflow_options* options, arriba_workflow_
 struct arriba_workflow_session {
 	Run* lanes[2];
 	int processed_lane = 0; // of the sample arriba_workflow_sample worked on last
-	struct Submitted { std::string bam, sorted_bam, supporting, virus_expression, coverage, gene_counts, splice_junctions, allele_sites, allele_counts, realign_reads, realign_kept; uint32_t allele_min_mapq = 0, allele_min_baseq = 0; int sorted_bam_level = 0, mark_duplicates = 0; int lane = 0; std::thread feeder; bool fed = false, ingest_finished = false, started = false; std::string error; int error_code = 0; };
+	struct Submitted { std::string bam, sorted_bam, supporting, virus_expression, coverage, gene_counts, splice_junctions, allele_sites, allele_counts, realign_reads, realign_kept, rna_metrics, rrna_intervals; uint32_t allele_min_mapq = 0, allele_min_baseq = 0; int sorted_bam_level = 0, mark_duplicates = 0; int lane = 0; std::thread feeder; bool fed = false, ingest_finished = false, started = false; std::string error; int error_code = 0; };
 	std::deque<std::unique_ptr<Submitted>> queue; // oldest first; at most two
 	std::mutex mutex; std::condition_variable changed;
 	bool ingest_busy = false; // a lane is between agpu_ingest_begin and agpu_ingest_finish
@@ -1675,6 +1728,7 @@ struct arriba_workflow_session {
 	std::string next_splice_junctions; // arriba_workflow_splice_junctions: likewise
 	std::string next_allele_sites, next_allele_counts; uint32_t next_allele_min_mapq = 0, next_allele_min_baseq = 13; // arriba_workflow_allele_counts: likewise
 	std::string next_realign_reads, next_realign_kept; // arriba_workflow_realign: likewise
+	std::string next_rna_metrics, next_rrna_intervals; // arriba_workflow_rna_metrics: likewise
 	int mark_duplicates = 0;  // arriba_workflow_sorted_bam_mark_duplicates: of the samples submitted from now on (at first: options.mark_duplicates of arriba_workflow_open)
 	int sorted_bam_level = 0; // arriba_workflow_sorted_bam_compression: of the samples submitted from now on (at first: options.sorted_bam_compression of arriba_workflow_open)
 	bool defer_output = false;
@@ -1752,10 +1806,12 @@ struct arriba_workflow_session {
 		run.options.allele_min_mapq = next_allele_min_mapq; run.options.allele_min_baseq = next_allele_min_baseq; next_allele_min_mapq = 0; next_allele_min_baseq = 13;
 		run.realign_reads_path.swap(next_realign_reads); next_realign_reads.clear(); run.options.realign_reads_file = run.realign_reads_path.empty() ? nullptr : run.realign_reads_path.c_str();
 		run.realign_kept_path.swap(next_realign_kept); next_realign_kept.clear(); run.options.realign_kept_file = run.realign_kept_path.empty() ? nullptr : run.realign_kept_path.c_str();
+		run.rna_metrics_path.swap(next_rna_metrics); next_rna_metrics.clear(); run.options.rna_metrics_file = run.rna_metrics_path.empty() ? nullptr : run.rna_metrics_path.c_str();
+		run.rrna_intervals_path.swap(next_rrna_intervals); next_rrna_intervals.clear(); run.options.rrna_intervals_file = run.rrna_intervals_path.empty() ? nullptr : run.rrna_intervals_path.c_str();
 		run.timing = nullptr; run.report = nullptr;
 		prepare_sample(run);
 		std::unique_ptr<Submitted> sample(new Submitted());
-		sample->bam = bam; sample->sorted_bam = run.sorted_bam_path; sample->supporting = run.supporting_prefix; sample->virus_expression = run.virus_expression_path; sample->coverage = run.coverage_path; sample->gene_counts = run.gene_counts_path; sample->splice_junctions = run.splice_junctions_path; sample->allele_sites = run.allele_sites_path; sample->allele_counts = run.allele_counts_path; sample->allele_min_mapq = run.options.allele_min_mapq; sample->allele_min_baseq = run.options.allele_min_baseq; sample->realign_reads = run.realign_reads_path; sample->realign_kept = run.realign_kept_path; sample->sorted_bam_level = sorted_bam_level; sample->mark_duplicates = mark_duplicates; sample->lane = lane;
+		sample->bam = bam; sample->sorted_bam = run.sorted_bam_path; sample->supporting = run.supporting_prefix; sample->virus_expression = run.virus_expression_path; sample->coverage = run.coverage_path; sample->gene_counts = run.gene_counts_path; sample->splice_junctions = run.splice_junctions_path; sample->allele_sites = run.allele_sites_path; sample->allele_counts = run.allele_counts_path; sample->allele_min_mapq = run.options.allele_min_mapq; sample->allele_min_baseq = run.options.allele_min_baseq; sample->realign_reads = run.realign_reads_path; sample->realign_kept = run.realign_kept_path; sample->rna_metrics = run.rna_metrics_path; sample->rrna_intervals = run.rrna_intervals_path; sample->sorted_bam_level = sorted_bam_level; sample->mark_duplicates = mark_duplicates; sample->lane = lane;
 		Submitted* mine = sample.get();
 		{ std::lock_guard<std::mutex> lock(mutex); queue.push_back(std::move(sample)); }
 		if (!run.device_ingest) { join_writer_of(lane); std::lock_guard<std::mutex> lock(mutex); mine->fed = true; return; } // (the host ingest reads the file inside arriba_workflow_sample)
@@ -1847,6 +1903,12 @@ int arriba_workflow_allele_counts(arriba_workflow_session* session, const char* 
 	return 0;
 }
 
+int arriba_workflow_rna_metrics(arriba_workflow_session* session, const char* path, const char* rrna_intervals_path) {
+	if (!session) { g_error = "ERROR: null argument"; return -1; }
+	session->next_rna_metrics = path ? path : ""; session->next_rrna_intervals = rrna_intervals_path ? rrna_intervals_path : "";
+	return 0;
+}
+
 int arriba_workflow_realign(arriba_workflow_session* session, const char* reads_path, const char* kept_path) {
 	if (!session) { g_error = "ERROR: null argument"; return -1; }
 	session->next_realign_reads = reads_path ? reads_path : ""; session->next_realign_kept = kept_path ? kept_path : "";
@@ -1901,7 +1963,7 @@ int arriba_workflow_sample(arriba_workflow_session* session, const char* chimeri
 	}
 	catch (const Failure& failure) { g_error = failure.text; g_error_code = failure.code; status = -1; }
 	catch (const std::exception& e) { g_error = std::string("ERROR: ") + e.what(); g_error_code = 0; status = -1; }
-	if (lane) { lane->after_ingest = nullptr; lane->before_host_writer = nullptr; lane->options.chimeric_bam_file = nullptr; lane->options.sorted_bam_file = nullptr; lane->options.supporting_alignments_prefix = nullptr; lane->options.virus_expression_file = nullptr; lane->options.coverage_file = nullptr; lane->options.gene_counts_file = nullptr; lane->options.splice_junctions_file = nullptr; lane->options.allele_sites_file = nullptr; lane->options.allele_counts_file = nullptr; lane->options.realign_reads_file = nullptr; lane->options.realign_kept_file = nullptr; lane->options.output_file = nullptr; lane->options.discarded_output_file = nullptr; lane->report = nullptr; lane->timing = nullptr; session->processed_lane = (int) (lane == session->lanes[1]); }
+	if (lane) { lane->after_ingest = nullptr; lane->before_host_writer = nullptr; lane->options.chimeric_bam_file = nullptr; lane->options.sorted_bam_file = nullptr; lane->options.supporting_alignments_prefix = nullptr; lane->options.virus_expression_file = nullptr; lane->options.coverage_file = nullptr; lane->options.gene_counts_file = nullptr; lane->options.splice_junctions_file = nullptr; lane->options.allele_sites_file = nullptr; lane->options.allele_counts_file = nullptr; lane->options.realign_reads_file = nullptr; lane->options.realign_kept_file = nullptr; lane->options.rna_metrics_file = nullptr; lane->options.rrna_intervals_file = nullptr; lane->options.output_file = nullptr; lane->options.discarded_output_file = nullptr; lane->report = nullptr; lane->timing = nullptr; session->processed_lane = (int) (lane == session->lanes[1]); }
 	// The device ran out of memory while the session had two lanes (advisor, round 4): their contexts share one pool of scratch buffers, of which nothing is idle while one lane
 	// feeds and the other runs its stages, so the device library gives nothing back by itself (DeviceBuffer::release_idle_buffers).  The session does what INTEGRATION.md ("Memory")
 	// used to ask of the caller: what was fed ahead is thrown away, the second lane is closed -- the pool belongs to one context again, which gives back what it keeps for its next
@@ -1922,6 +1984,8 @@ int arriba_workflow_sample(arriba_workflow_session* session, const char* chimeri
 		const uint32_t behind_allele_mapq = session->queue.empty() ? 0 : session->queue.front()->allele_min_mapq, again_allele_mapq = lane->options.allele_min_mapq;
 		const std::string behind_realign_reads = session->queue.empty() ? std::string() : session->queue.front()->realign_reads, again_realign_reads = lane->realign_reads_path;
 		const std::string behind_realign_kept = session->queue.empty() ? std::string() : session->queue.front()->realign_kept, again_realign_kept = lane->realign_kept_path;
+		const std::string behind_rna_metrics = session->queue.empty() ? std::string() : session->queue.front()->rna_metrics, again_rna_metrics = lane->rna_metrics_path;
+		const std::string behind_rrna_intervals = session->queue.empty() ? std::string() : session->queue.front()->rrna_intervals, again_rrna_intervals = lane->rrna_intervals_path;
 		const uint32_t behind_allele_baseq = session->queue.empty() ? 13 : session->queue.front()->allele_min_baseq, again_allele_baseq = lane->options.allele_min_baseq;
 		session->drain();
 		session->join_writer_of(0); session->join_writer_of(1);
@@ -1931,11 +1995,11 @@ int arriba_workflow_sample(arriba_workflow_session* session, const char* chimeri
 		delete session->lanes[1]; session->lanes[1] = nullptr; session->processed_lane = 0;
 		fprintf(stderr, "arriba_workflow_sample: %s -- with two samples in flight; '%s' is run again with the device to itself\n", first_error.c_str(), chimeric_bam_file);
 		session->retrying = true;
-		session->next_sorted_bam = again_sorted_bam; session->next_supporting = again_supporting; session->next_virus_expression = again_virus; session->next_coverage = again_coverage; session->next_gene_counts = again_gene_counts; session->next_splice_junctions = again_splice_junctions; session->next_allele_sites = again_allele_sites; session->next_allele_counts = again_allele_counts; session->next_allele_min_mapq = again_allele_mapq; session->next_allele_min_baseq = again_allele_baseq; session->next_realign_reads = again_realign_reads; session->next_realign_kept = again_realign_kept; session->sorted_bam_level = again_level; session->mark_duplicates = again_marks;
+		session->next_sorted_bam = again_sorted_bam; session->next_supporting = again_supporting; session->next_virus_expression = again_virus; session->next_coverage = again_coverage; session->next_gene_counts = again_gene_counts; session->next_splice_junctions = again_splice_junctions; session->next_allele_sites = again_allele_sites; session->next_allele_counts = again_allele_counts; session->next_allele_min_mapq = again_allele_mapq; session->next_allele_min_baseq = again_allele_baseq; session->next_realign_reads = again_realign_reads; session->next_realign_kept = again_realign_kept; session->next_rna_metrics = again_rna_metrics; session->next_rrna_intervals = again_rrna_intervals; session->sorted_bam_level = again_level; session->mark_duplicates = again_marks;
 		status = arriba_workflow_sample(session, chimeric_bam_file, output_file, discarded_output_file, report, timing);
 		session->retrying = false;
 		if (status == 0 && !behind.empty()) { // (as its caller submitted it: a failure to feed it is reported by the call that asks for it)
-			try { session->next_sorted_bam = behind_sorted_bam; session->next_supporting = behind_supporting; session->next_virus_expression = behind_virus; session->next_coverage = behind_coverage; session->next_gene_counts = behind_gene_counts; session->next_splice_junctions = behind_splice_junctions; session->next_allele_sites = behind_allele_sites; session->next_allele_counts = behind_allele_counts; session->next_allele_min_mapq = behind_allele_mapq; session->next_allele_min_baseq = behind_allele_baseq; session->next_realign_reads = behind_realign_reads; session->next_realign_kept = behind_realign_kept; session->sorted_bam_level = behind_level; session->mark_duplicates = behind_marks; session->submit(behind.c_str()); }
+			try { session->next_sorted_bam = behind_sorted_bam; session->next_supporting = behind_supporting; session->next_virus_expression = behind_virus; session->next_coverage = behind_coverage; session->next_gene_counts = behind_gene_counts; session->next_splice_junctions = behind_splice_junctions; session->next_allele_sites = behind_allele_sites; session->next_allele_counts = behind_allele_counts; session->next_allele_min_mapq = behind_allele_mapq; session->next_allele_min_baseq = behind_allele_baseq; session->next_realign_reads = behind_realign_reads; session->next_realign_kept = behind_realign_kept; session->next_rna_metrics = behind_rna_metrics; session->next_rrna_intervals = behind_rrna_intervals; session->sorted_bam_level = behind_level; session->mark_duplicates = behind_marks; session->submit(behind.c_str()); }
 			catch (const Failure&) {} catch (const std::exception&) {}
 		}
 		session->sorted_bam_level = session_level; session->mark_duplicates = session_marks;

@@ -70,6 +70,13 @@ def allele_stats_of(stats):
     return out
 
 
+def rna_metrics_stats_of(stats):
+    """agpu_rna_metrics_stats (the device's or the host's) as a dict"""
+    out = {name: int(getattr(stats, name)) for name in ("records", "base_records", "blocks", "segments", "track_runs", "peak_bytes")}
+    out["seconds"] = {"kernel": stats.seconds[0]}
+    return out
+
+
 def realign_stats_of(stats):
     """agpu_realign_stats (the device's or the host's) as a dict"""
     out = {name: int(getattr(stats, name)) for name in ("records", "templates", "realign_templates", "kept_templates", "dropped_secondary", "extra", "orphans", "placeholder_cigar", "realign_bytes", "kept_bytes", "peak_bytes")}
@@ -229,7 +236,7 @@ class WorkflowSession(object):
         if self._lib.arriba_workflow_sorted_bam_mark_duplicates(self._session, int(bool(on))) != 0:
             raise ArribaError(self._lib.arriba_workflow_last_error().decode())
 
-    def submit(self, bam, sorted_bam_file=None, supporting_alignments_prefix=None, sorted_bam_compression=None, virus_expression_file=None, coverage_file=None, mark_duplicates=None, gene_counts_file=None, splice_junctions_file=None, allele_sites_file=None, allele_counts_file=None, allele_min_mapq=0, allele_min_baseq=13, realign_reads_file=None, realign_kept_file=None):
+    def submit(self, bam, sorted_bam_file=None, supporting_alignments_prefix=None, sorted_bam_compression=None, virus_expression_file=None, coverage_file=None, mark_duplicates=None, gene_counts_file=None, splice_junctions_file=None, allele_sites_file=None, allele_counts_file=None, allele_min_mapq=0, allele_min_baseq=13, realign_reads_file=None, realign_kept_file=None, rna_metrics_file=None, rrna_intervals_file=None):
         """the sample that comes after the one `sample` is called for next: its file is fed (PCIe, the front of read_chimeric_alignments) while the stages of that one run;
         sorted_bam_file: its records in coordinate order with their index (--sorted-bam), written when its ingest is finished; sorted_bam_compression: its level (None: as it is)"""
         if sorted_bam_compression is not None:
@@ -244,6 +251,7 @@ class WorkflowSession(object):
         self._lib.arriba_workflow_splice_junctions(self._session, splice_junctions_file.encode() if splice_junctions_file else None)  # (--splice-junctions: its junction table, likewise)
         self._lib.arriba_workflow_allele_counts(self._session, allele_sites_file.encode() if allele_sites_file else None, allele_counts_file.encode() if allele_counts_file else None, allele_min_mapq, allele_min_baseq)  # (--allele-counts: likewise)
         self._lib.arriba_workflow_realign(self._session, realign_reads_file.encode() if realign_reads_file else None, realign_kept_file.encode() if realign_kept_file else None)  # (--realign-reads: likewise)
+        self._lib.arriba_workflow_rna_metrics(self._session, rna_metrics_file.encode() if rna_metrics_file else None, rrna_intervals_file.encode() if rrna_intervals_file else None)  # (--rna-metrics: its QC table, likewise)
         if self._lib.arriba_workflow_submit(self._session, bam.encode()) != 0:
             raise ArribaError(self._lib.arriba_workflow_last_error().decode())
         if self._profiling_on:
@@ -338,7 +346,7 @@ class WorkflowSession(object):
     def _lane_contexts(self):
         return [ctx for ctx in (self._lib.arriba_workflow_lane_device(self._session, lane) for lane in (0, 1)) if ctx]
 
-    def sample(self, bam, output_file, discarded_output_file=None, sorted_bam_file=None, supporting_alignments_prefix=None, sorted_bam_compression=None, virus_expression_file=None, coverage_file=None, mark_duplicates=None, gene_counts_file=None, splice_junctions_file=None, allele_sites_file=None, allele_counts_file=None, allele_min_mapq=0, allele_min_baseq=13, realign_reads_file=None, realign_kept_file=None):
+    def sample(self, bam, output_file, discarded_output_file=None, sorted_bam_file=None, supporting_alignments_prefix=None, sorted_bam_compression=None, virus_expression_file=None, coverage_file=None, mark_duplicates=None, gene_counts_file=None, splice_junctions_file=None, allele_sites_file=None, allele_counts_file=None, allele_min_mapq=0, allele_min_baseq=13, realign_reads_file=None, realign_kept_file=None, rna_metrics_file=None, rrna_intervals_file=None):
         """one sample, BAM file -> fusions.tsv (and discarded.tsv); returns the stages with their "(remaining=N)" counts.  sorted_bam_file (--sorted-bam): for a sample that was
         not submitted ahead; one that was says it to `submit`"""
         report, timing = _capi.WorkflowReport(), _capi.WorkflowTiming()
@@ -362,6 +370,8 @@ class WorkflowSession(object):
             self._lib.arriba_workflow_allele_counts(self._session, allele_sites_file.encode() if allele_sites_file else None, allele_counts_file.encode() if allele_counts_file else None, allele_min_mapq, allele_min_baseq)
         if realign_reads_file or realign_kept_file:  # (likewise; the kept file without the other is refused by the sample)
             self._lib.arriba_workflow_realign(self._session, realign_reads_file.encode() if realign_reads_file else None, realign_kept_file.encode() if realign_kept_file else None)
+        if rna_metrics_file or rrna_intervals_file:  # (likewise; the intervals without the table are refused by the sample)
+            self._lib.arriba_workflow_rna_metrics(self._session, rna_metrics_file.encode() if rna_metrics_file else None, rrna_intervals_file.encode() if rrna_intervals_file else None)
         if self._lib.arriba_workflow_sample(self._session, bam.encode(), output_file.encode(), discarded_output_file.encode() if discarded_output_file else None, byref(report), byref(timing)) != 0:
             raise ArribaError(self._lib.arriba_workflow_last_error().decode())
         self.ctx = self._lib.arriba_workflow_device(self._session)  # (the lane that worked on this sample)
@@ -886,6 +896,34 @@ class DevicePipeline(object):
             raise
         return realign_stats_of(stats)
 
+    def rna_metrics(self, rrna_intervals_file=None):
+        """--rna-metrics: the alignment QC counters of the records of the last read_chimeric_alignments, summed on the device from the record stream that is still in HBM
+        (agpu_rna_metrics) against the region track of the session for `rrna_intervals_file` (BED; None: no rRNA intervals), which is built when first asked for.
+        Valid after read_chimeric_alignments and before the next one.  Returns (counters, stats): a uint64 array of _capi.RNA_METRICS_WORDS words -- the scalars of "## METRICS" in
+        file order, two statistics, the MAPQ, insert-size and gene-body bins -- and {"records", "base_records", "blocks", "segments", "track_runs", "peak_bytes", "seconds"}."""
+        if not self.device_ingest or not hasattr(self.api, "rna_metrics"):
+            raise ArribaError("ERROR: rna metrics need the record stream of an ingest on the device (DevicePipeline(bam=...))")
+        lib, handle = self.session._lib, self.session._session
+        contigs, track = _capi.DepthContigs(), _capi.RegionTrack()
+        if lib.ahost_region_track(handle, rrna_intervals_file.encode() if rrna_intervals_file else None, byref(track), None) != 0 or lib.ahost_depth_contigs_of_session(handle, byref(contigs)) != 0:
+            raise ArribaError("ERROR: " + lib.ahost_last_error().decode())
+        counters, stats = np.zeros(_capi.RNA_METRICS_WORDS, dtype=np.uint64), _capi.RnaMetricsStats()
+        self._check(self.api.rna_metrics(self.ctx, byref(track), contigs.length, contigs.n_ref, counters.ctypes.data, byref(stats)))
+        return counters, rna_metrics_stats_of(stats)
+
+    def write_rna_metrics(self, path, rrna_intervals_file=None):
+        """--rna-metrics: the counters of `rna_metrics` as the text of the table, written through `path`.tmp; returns the statistics"""
+        lib = self.session._lib
+        counters, stats = self.rna_metrics(rrna_intervals_file)  # (refused before anything is written)
+        if lib.ahost_rna_metrics_write(counters.ctypes.data, counters.size, path.encode()) != 0:
+            raise ArribaError("ERROR: " + lib.ahost_last_error().decode())
+        return stats
+
+    def rna_metrics_allocated_bytes(self):
+        count = c_uint64()
+        self._check(self.api.rna_metrics_allocated_bytes(self.ctx, byref(count)))
+        return int(count.value)
+
     def realign_allocated_bytes(self):
         count = c_uint64()
         self._check(self.api.realign_allocated_bytes(self.ctx, byref(count)))
@@ -1167,7 +1205,7 @@ class DevicePipeline(object):
                      max_genomic_breakpoint_distance=100000, strandedness=None, evalue_cutoff=0.3,
                      min_itd_support=10, min_itd_allele_fraction=0.07, high_expression_quantile=0.998, min_spliced_events=4, min_anchor_length=23,
                      max_homolog_identity=0.3, max_itd_length=100, fill_sequence_gaps=False, top_viral_contigs=5, viral_contig_min_covered_fraction=0.05,
-                     print_extra_info_for_discarded_fusions=False, log=None, sorted_bam_file=None, supporting_alignments_prefix=None, supporting_alignments_window=1000000, virus_expression_file=None, coverage_file=None, mark_duplicates=False, gene_counts_file=None, splice_junctions_file=None, allele_sites_file=None, allele_counts_file=None, allele_min_mapq=0, allele_min_baseq=13, realign_reads_file=None, realign_kept_file=None):
+                     print_extra_info_for_discarded_fusions=False, log=None, sorted_bam_file=None, supporting_alignments_prefix=None, supporting_alignments_window=1000000, virus_expression_file=None, coverage_file=None, mark_duplicates=False, gene_counts_file=None, splice_junctions_file=None, allele_sites_file=None, allele_counts_file=None, allele_min_mapq=0, allele_min_baseq=13, realign_reads_file=None, realign_kept_file=None, rna_metrics_file=None, rrna_intervals_file=None):
         """The reference's main() behind read_chimeric_alignments (source/arriba.cpp:119-610) with its default parameters: the read-level cascade, find_fusions,
         every candidate-level filter in the reference's order, assign_confidence, and the two output files.  `log` receives (stage, remaining) pairs --
         the numbers the reference prints as "(remaining=N)".  Filters switched off with -f are skipped by the stages themselves (agpu_params.filter_enabled)."""
@@ -1192,6 +1230,10 @@ class DevicePipeline(object):
             if not realign_reads_file:
                 raise ArribaError("ERROR: --realign-kept needs --realign-reads")
             self.realign_split(realign_reads_file, realign_kept_file)
+        if rna_metrics_file or rrna_intervals_file:  # (--rna-metrics: likewise)
+            if not rna_metrics_file:
+                raise ArribaError("ERROR: --rrna-intervals needs --rna-metrics")
+            self.write_rna_metrics(rna_metrics_file, rrna_intervals_file)
         if supporting_alignments_prefix:  # (--supporting-alignments, phase 1: the records of the names of the batch leave the stream while it is there)
             self.build_support_pool()
         self.run_read_level(strandedness, top_viral_contigs, viral_contig_min_covered_fraction)

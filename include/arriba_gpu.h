@@ -579,6 +579,40 @@ int agpu_realign_begin(agpu_ctx* ctx, const uint8_t* in_assembly /* [n_ref] */, 
 int agpu_realign_next(agpu_ctx* ctx, int which, void* pinned, uint64_t capacity, uint64_t* bytes);
 int agpu_realign_end(agpu_ctx* ctx, agpu_realign_stats* stats /* may be NULL */);
 int agpu_realign_allocated_bytes(agpu_ctx* ctx, uint64_t* bytes);
+/* --rna-metrics: the alignment QC table of the records of the last ingest -- flag and MAPQ counts, aligned bases per class of the annotation (ribosomal, coding, UTR, intronic,
+ * intergenic), strandedness, insert sizes and the 5'->3' coverage of gene bodies --, summed on the device while the stream is in HBM (DESIGN.md 4.19;
+ * arriba_amd/csrc/device/agpu_rnametrics.hip, rnametrics_core.hpp).  Every number is a sum over single records: one kernel over the stream, no name table.
+ *   agpu_region_track  the annotation and the rRNA intervals as runs of bases with equal bits and body gene, per contig of the session, built on the host (ahost_region_track;
+ *                      arriba_amd/csrc/host/region_track.cpp).  Runs [contig_offset[c], contig_offset[c + 1]) are those of contig c; run_start ascends from 0 and a run ends where the
+ *                      next begins (the last: never).  run_gene: the body gene of the run or 0xFFFFFFFF; run_rank: the ascending exonic rank of its first base in that gene;
+ *                      gene_body[g]: L of gene g, bit 31 set for a forward gene.  id: not 0, and different for every track a process builds
+ *   agpu_rna_metrics   behind agpu_ingest_finish, before the next agpu_ingest_begin on this context or its sibling (the refusals of agpu_depth_begin).  ref_length: LN of every
+ *                      reference of the header of that ingest (n_ref of them: ahost_depth_contigs_of_session), to which blocks are clipped.  counters: AGPU_RNA_METRICS_WORDS words --
+ *                      the AGPU_RNA_METRICS_SCALARS counters of "## METRICS" in the order of the file, two statistics, then the MAPQ (256), insert-size (1002) and gene-body (100) bins.
+ *                      The track is copied to the device when the context sees its id for the first time and kept until another one comes or the context goes; the counter block and
+ *                      the lengths are freed before the call returns.
+ *   agpu_rna_metrics_allocated_bytes   of the "rnametrics.*" buffers (track, lengths, counter block): 0 until the first call
+ * ARRIBA_RNAMETRICS_PLAIN_ATOMICS=1 (a knob for the measurement): every lane adds to global memory instead of the workgroup summing in LDS first. */
+#define AGPU_RNA_METRICS_SCALARS 34
+#define AGPU_RNA_METRICS_WORDS 1394
+enum { AGPU_TRACK_RRNA = 1, AGPU_TRACK_CODING = 2, AGPU_TRACK_EXON = 4, AGPU_TRACK_GENE_FORWARD = 8, AGPU_TRACK_GENE_REVERSE = 16 };
+typedef struct {
+	uint64_t id;
+	uint32_t n_contigs; const uint32_t* contig_offset; /* [n_contigs + 1] */
+	uint32_t n_runs; const int32_t* run_start; const uint8_t* run_bits; const uint32_t* run_gene; const uint32_t* run_rank; /* [n_runs] each */
+	uint32_t n_genes; const uint32_t* gene_body;       /* [n_genes] */
+} agpu_region_track;
+typedef struct {
+	uint64_t records;              /* of the stream */
+	uint64_t base_records;         /* mapped primary records without 0x200 on a reference of the header: the ones whose bases are classified */
+	uint64_t blocks;               /* their blocks */
+	uint64_t segments;             /* the pieces of runs those blocks were cut into (blocks on a contig the track lacks have none) */
+	uint64_t track_runs;           /* of the track used */
+	uint64_t peak_bytes;           /* of the "rnametrics.*" buffers (0 on the host) */
+	double seconds[1];             /* the kernel (device: from HIP events, 0 on the host) */
+} agpu_rna_metrics_stats;
+int agpu_rna_metrics(agpu_ctx* ctx, const agpu_region_track* track, const uint32_t* ref_length, uint32_t n_ref, uint64_t* counters /* [AGPU_RNA_METRICS_WORDS] */, agpu_rna_metrics_stats* stats /* may be NULL */);
+int agpu_rna_metrics_allocated_bytes(agpu_ctx* ctx, uint64_t* bytes);
 /* what the host's sequential stages and its output writer need from a batch that lives on the device:
  *   agpu_get_viral_read_counts   mapped_viral_reads_by_contig (source/read_chimeric_alignments.cpp:735-739)
  *   agpu_get_coverage            coverage_t as the reference holds it (16-bit saturating windows, start/end flags); sizes by coverage_window_offset

@@ -256,6 +256,34 @@ int ahost_realign_plan_of_session(ahost_session* session, ahost_realign_plan* pl
 int ahost_realign_split_of(ahost_session* session, const void* input_header, size_t header_size, const void* records, size_t size, int want_kept, const char** realign, uint64_t* realign_bytes, const char** kept, uint64_t* kept_bytes,
                            agpu_realign_stats* stats /* may be NULL */);
 int ahost_realign_split_file(ahost_session* session, const char* input_path, const char* realign_path, const char* kept_path, agpu_realign_stats* stats);
+/* ---- --rna-metrics: the host side of agpu_rna_metrics (include/arriba_gpu.h) -- the alignment QC table of an input (the rule: DESIGN.md 4.19).  A counter block is
+ * AGPU_RNA_METRICS_WORDS words as agpu_rna_metrics fills them; n_counters is checked ----
+ *   ahost_rrna_intervals_load  reads an rRNA interval file (--rrna-intervals; BED: contig, start, end separated by tabs, 0-based and half open; further fields are ignored; lines that
+ *                              start with '#', "track" or "browser" and empty lines are skipped).  A line that does not parse or whose start lies behind its end is refused with
+ *                              its number.  n_intervals may be NULL
+ *   ahost_region_track         the region track of the session for an interval file (NULL: no rRNA intervals): built when it is asked for first and kept until ahost_close; the
+ *                              pointers of `track` stay valid as long.  Contig names are looked up without a leading "chr" among the contigs of the assembly and the annotation; a
+ *                              line on another contig is counted in info->intervals_unknown_contig and ignored.  info may be NULL
+ *   ahost_rna_metrics_of       arriba_amd/csrc/device/rnametrics_core.hpp stepped on the host over BAM records in host memory (the device's comparator; the CPU tier).  input_header:
+ *                              the head of the input the records come from (a BAM header, or the '@' lines of SAM text): its references are looked up among the contigs of the
+ *                              session by name, their LN clips the blocks
+ *   ahost_rna_metrics_text     a counter block -> the text of the file; valid until the next call on the thread
+ *   ahost_rna_metrics_write    that text into `path`, through path.tmp; on a failure nothing is left behind
+ *   ahost_rna_metrics_file     all of it for a file (BAM in BGZF, gzip or raw; SAM text): what --host-ingest runs; rrna_intervals_path and stats may be NULL */
+typedef struct {
+	uint32_t n_contigs;                 /* of the track: the contigs the session knew when it was opened */
+	uint64_t runs;
+	uint64_t intervals;                 /* lines of the interval file */
+	uint64_t intervals_unknown_contig;  /* ... on a contig the session lacks: ignored */
+	uint64_t bytes;                     /* of the arrays of the track */
+} ahost_region_track_info;
+int ahost_rrna_intervals_load(const char* path, uint64_t* n_intervals);
+int ahost_region_track(ahost_session* session, const char* rrna_intervals_path, agpu_region_track* track, ahost_region_track_info* info);
+int ahost_rna_metrics_of(ahost_session* session, const char* rrna_intervals_path, const void* input_header, size_t header_size, const void* records, size_t size, uint64_t* counters, uint64_t n_counters,
+                         agpu_rna_metrics_stats* stats /* may be NULL */);
+int ahost_rna_metrics_text(const uint64_t* counters, uint64_t n_counters, const char** text, uint64_t* bytes);
+int ahost_rna_metrics_write(const uint64_t* counters, uint64_t n_counters, const char* path);
+int ahost_rna_metrics_file(ahost_session* session, const char* input_path, const char* rrna_intervals_path, const char* path, agpu_rna_metrics_stats* stats);
 int ahost_adopt_device_ingest(ahost_session* session, const agpu_ingest_result* result, const uint64_t* viral_read_counts, const uint16_t* coverage, const uint8_t* fragment_starts, const uint8_t* fragment_ends);
 int ahost_set_batch_rows(ahost_session* session, const agpu_batch_rows* rows, const uint32_t* fragments /* [rows->n] ascending: the fragment every row holds; NULL: row k holds the fragment
                          of entry k of the read lists of the table the next ahost_write_fusions writes (the reads of a candidate next to each other; the table then carries read_filter_of_rows) */);

@@ -96,6 +96,12 @@ typedef struct {
 	                                         the same code stepped on the host).  Paths that equal each other or another output, and directories that do not take the files, are refused
 	                                         before the feed starts.  Of arriba_workflow_run's sample; the samples of a session say theirs with arriba_workflow_realign.  Not for one sample
 	                                         over several ranks. */
+	const char* rna_metrics_file;         /* --rna-metrics and --rrna-intervals; both NULL (and a zero-initialised struct) = none, rrna_intervals_file without rna_metrics_file is refused. */
+	const char* rrna_intervals_file;      /* rna_metrics_file: the alignment QC table of the records of chimeric_bam_file -- records by flag, MAPQ histogram, aligned bases per class
+	                                         (ribosomal, coding, UTR, intronic, intergenic), strandedness, insert sizes, coverage of gene bodies -- summed behind read_chimeric_alignments
+	                                         from the record stream in HBM (include/arriba_gpu.h: agpu_rna_metrics; with host_ingest: the same code stepped on the host).
+	                                         rrna_intervals_file: BED intervals whose bases are ribosomal; a file that does not parse is refused before the feed starts.  Of
+	                                         arriba_workflow_run's sample; the samples of a session say theirs with arriba_workflow_rna_metrics.  Not for one sample over several ranks. */
 } arriba_workflow_options;
 
 /* what the reference prints as "(remaining=N)" / "(total=N)" / "(marked=N)", in the order of the stages; stage names as in the reference's source */
@@ -141,6 +147,7 @@ typedef struct { /* seconds of one sample, by part (wall clock of the calling th
 	double splice_junctions; /* --splice-junctions: counts, name ids, crossings, sorts, rows, classes, the copy, the file (inside `ingest`; beside the sample in front when the ingest was finished ahead) */
 	double allele_counts;    /* --allele-counts: the sites placed and sorted, the count, the rows, the copy, the file (inside `ingest`; beside the sample in front when the ingest was finished ahead) */
 	double realign;          /* --realign-reads: name ids and claims, verdicts, scans, the windows of text, the copies, the files (inside `ingest`; beside the sample in front when the ingest was finished ahead) */
+	double rna_metrics;      /* --rna-metrics: the region track when it is built, the kernel, the copy, the file (inside `ingest`; beside the sample in front when the ingest was finished ahead) */
 } arriba_workflow_timing;
 /* options->chimeric_bam_file, output_file and discarded_output_file are not used by open (they belong to a sample); NULL + arriba_workflow_last_error() on failure */
 arriba_workflow_session* arriba_workflow_open(const arriba_workflow_options* options);
@@ -178,6 +185,8 @@ int arriba_workflow_splice_junctions(arriba_workflow_session* session, const cha
 int arriba_workflow_allele_counts(arriba_workflow_session* session, const char* sites_path, const char* output_path, uint32_t min_mapq, uint32_t min_baseq);
 /* --realign-reads and --realign-kept of the sample that is submitted NEXT, in the same way; both NULL: none.  The files are written by the thread that finishes its ingest. */
 int arriba_workflow_realign(arriba_workflow_session* session, const char* reads_path, const char* kept_path);
+/* --rna-metrics and --rrna-intervals of the sample that is submitted NEXT, in the same way; path NULL: none.  The table is written by the thread that finishes its ingest. */
+int arriba_workflow_rna_metrics(arriba_workflow_session* session, const char* path, const char* rrna_intervals_path);
 /* (If the device runs out of memory while two samples are in flight, arriba_workflow_sample throws away what was fed ahead, closes the second lane, runs its sample again with the device
  * to itself and submits the other sample again behind it -- once; a sample that does not fit the device alone fails the call.  INTEGRATION.md, "Memory".) */
 /* on: arriba_workflow_sample returns when the last output file of the sample (-O if given, else -o) has everything it needs off the device; the file is formatted and written
