@@ -74,7 +74,10 @@ class BatchView(ctypes.Structure):
 
 class IngestConfig(ctypes.Structure):
     _fields_ = [("n_targets", c_uint32), ("tid_to_contig", POINTER(c_uint32)), ("first_record_offset", c_uint64), ("stream_size_hint", c_uint64), ("n_contigs", c_uint32),
-                ("coverage_window_offset", POINTER(c_uint64)), ("external_duplicate_marking", c_uint8), ("max_itd_length", c_uint32), ("part_of_sample", c_uint8), ("host_buffers", c_uint8)]
+                ("coverage_window_offset", POINTER(c_uint64)), ("external_duplicate_marking", c_uint8), ("max_itd_length", c_uint32), ("part_of_sample", c_uint8), ("host_buffers", c_uint8), ("role", c_uint8)]
+
+
+ROLE_WHOLE, ROLE_SEPARATE_CHIMERIC, ROLE_SEPARATE_RNA = 0, 1, 2  # agpu_ingest_config.role (include/arriba_gpu.h: AGPU_ROLE_*)
 
 
 class BgzfBlock(ctypes.Structure):
@@ -354,6 +357,8 @@ def bind_device_api(lib, prefix="agpu_"):
         "sam_transcode": (c_int, [ctx, c_void_p, c_size_t, c_void_p, c_void_p, c_uint32, c_void_p, c_size_t, POINTER(c_uint64), POINTER(c_uint64), POINTER(c_uint64)]),
         "bgzf_unpack": (c_int, [ctx, c_void_p, c_size_t, POINTER(BgzfBlock), c_uint32, c_int, c_void_p, c_size_t, c_void_p, POINTER(c_uint32), POINTER(c_uint32)]),
         "ingest_finish": (c_int, [ctx, POINTER(IngestResult)]),
+        "separate_adopt": (c_int, [ctx]),
+        "separate_merge": (c_int, [ctx, POINTER(IngestResult)]),
         "sorted_bam_begin": (c_int, [ctx, POINTER(SortedBamInfo)]),
         "sorted_bam_next": (c_int, [ctx, c_void_p, c_uint64, POINTER(c_uint64)]),
         "sorted_bam_index": (c_int, [ctx, c_uint64, c_void_p, c_uint32, POINTER(SortedBamIndex)]),
@@ -429,6 +434,8 @@ def bind_host_api(lib):
         "ahost_close": (None, [session]),
         "ahost_ingest_bam_file": (c_int, [session, c_char_p, c_int, ctypes.c_uint]),
         "ahost_ingest_bam_memory": (c_int, [session, c_void_p, c_size_t, c_int, ctypes.c_uint]),
+        "ahost_ingest_separate": (c_int, [session, c_char_p, c_char_p, c_int, ctypes.c_uint, POINTER(c_uint64), POINTER(c_uint64)]),
+        "ahost_bam_open_role": (c_int, [session, c_char_p, c_int, ctypes.c_uint, c_int, POINTER(IngestConfig)]),
         "ahost_save_ingest": (c_int, [session, c_char_p]),
         "ahost_load_ingest": (c_int, [session, c_char_p]),
         "ahost_annotation_view": (POINTER(AnnotationView), [session]),
@@ -436,6 +443,7 @@ def bind_host_api(lib):
         "ahost_batch_view": (POINTER(BatchView), [session]),
         "ahost_fragment_count": (c_uint64, [session]),
         "ahost_mapped_reads": (c_uint64, [session]),
+        "ahost_viral_read_total": (c_uint64, [session]),
         "ahost_coverage_checksum": (c_uint64, [session]),
         "ahost_coverage_view": (POINTER(CoverageView), [session]),
         "ahost_write_fusions": (c_int, [session, POINTER(FusionTable), c_char_p, c_int, c_int, c_uint32, c_int, c_int]),
@@ -544,7 +552,7 @@ class WorkflowOptions(ctypes.Structure):
                                               "protein_domains_file", "genomic_breakpoints_file", "interesting_contigs", "viral_contigs", "gtf_features")] + [
         ("device", Params), ("min_itd_support", c_uint32), ("min_itd_allele_fraction", c_float), ("high_expression_quantile", c_float), ("min_spliced_events", c_uint32), ("min_anchor_length", c_uint32),
         ("max_homolog_identity", c_float), ("top_viral_contigs", c_uint32), ("viral_contig_min_covered_fraction", c_float), ("max_genomic_breakpoint_distance", c_int32),
-        ("print_extra_info_for_discarded_fusions", c_uint8), ("fill_sequence_gaps", c_uint8), ("device_index", c_int), ("log_to_stdout", c_uint8), ("host_ingest", c_uint8), ("sorted_bam_file", c_char_p), ("supporting_alignments_prefix", c_char_p), ("supporting_alignments_window", ctypes.c_int64), ("sorted_bam_compression", c_int), ("virus_expression_file", c_char_p), ("coverage_file", c_char_p), ("mark_duplicates", c_int), ("gene_counts_file", c_char_p), ("splice_junctions_file", c_char_p), ("allele_sites_file", c_char_p), ("allele_counts_file", c_char_p), ("allele_min_mapq", c_uint32), ("allele_min_baseq", c_uint32), ("realign_reads_file", c_char_p), ("realign_kept_file", c_char_p), ("rna_metrics_file", c_char_p), ("rrna_intervals_file", c_char_p)]
+        ("print_extra_info_for_discarded_fusions", c_uint8), ("fill_sequence_gaps", c_uint8), ("device_index", c_int), ("log_to_stdout", c_uint8), ("host_ingest", c_uint8), ("sorted_bam_file", c_char_p), ("supporting_alignments_prefix", c_char_p), ("supporting_alignments_window", ctypes.c_int64), ("sorted_bam_compression", c_int), ("virus_expression_file", c_char_p), ("coverage_file", c_char_p), ("mark_duplicates", c_int), ("gene_counts_file", c_char_p), ("splice_junctions_file", c_char_p), ("allele_sites_file", c_char_p), ("allele_counts_file", c_char_p), ("allele_min_mapq", c_uint32), ("allele_min_baseq", c_uint32), ("realign_reads_file", c_char_p), ("realign_kept_file", c_char_p), ("rna_metrics_file", c_char_p), ("rrna_intervals_file", c_char_p), ("separate_chimeric_file", c_char_p)]
 
 
 class WorkflowStage(ctypes.Structure):
@@ -586,6 +594,7 @@ def workflow_library():
         lib.arriba_workflow_run.argtypes = [POINTER(WorkflowOptions), POINTER(WorkflowReport)]; lib.arriba_workflow_run.restype = c_int
         lib.arriba_workflow_open.argtypes = [POINTER(WorkflowOptions)]; lib.arriba_workflow_open.restype = c_void_p
         lib.arriba_workflow_sample.argtypes = [c_void_p, c_char_p, c_char_p, c_char_p, POINTER(WorkflowReport), POINTER(WorkflowTiming)]; lib.arriba_workflow_sample.restype = c_int
+        lib.arriba_workflow_sample_separate.argtypes = [c_void_p, c_char_p, c_char_p, c_char_p, c_char_p, POINTER(WorkflowReport), POINTER(WorkflowTiming)]; lib.arriba_workflow_sample_separate.restype = c_int
         lib.arriba_workflow_submit.argtypes = [c_void_p, c_char_p]; lib.arriba_workflow_submit.restype = c_int
         lib.arriba_workflow_sorted_bam.argtypes = [c_void_p, c_char_p]; lib.arriba_workflow_sorted_bam.restype = c_int
         lib.arriba_workflow_supporting_alignments.argtypes = [c_void_p, c_char_p]; lib.arriba_workflow_supporting_alignments.restype = c_int

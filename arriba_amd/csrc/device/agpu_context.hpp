@@ -288,6 +288,11 @@ struct agpu_ctx {
 	bool ingest_active = false, ingest_finishing = false /* inside agpu_ingest_finish: its tables are in use although the feed is over */, batch_from_ingest = false, ingest_part_of_sample = false, ingest_verify_crc = false, ingest_deflated_pieces = false /* a piece of this ingest went through bgzf_inflate_kernel */;
 	bool ingest_sam = false; uint32_t sam_n_targets = 0, sam_table_mask = 0; // the pieces of this ingest are SAM text (agpu_sam.hip: agpu_ingest_sam_targets uploaded the @SQ names to "sam.names" / "sam.name_offset" / "sam.table")
 	agpu::DeviceBuffer ingest_qname_keys; uint64_t ingest_qname_runs = 0; // a part of a sample: 128-bit keys of the runs of read names in its stream
+	// -c (agpu_separate_adopt / agpu_separate_merge): the role of the ingest under way; the batch of pass C as the block agpu_shard_export makes of it, the name keys of its fragments
+	// (ascending) and the fragment of every key; what pass C reported
+	uint8_t ingest_role = 0; bool separate_adopted = false;
+	agpu::DeviceBuffer separate_block, separate_keys, separate_rows; uint64_t separate_block_bytes = 0, separate_n = 0, separate_names_at = 0, separate_name_offset_at = 0;
+	agpu_ingest_result separate_result;
 	agpu_ingest_result ingest_result; uint64_t ingest_pool_sizes[2] = { 0, 0 }; // what the last ingest (or merge of parts) reported; CIGAR words and sequence bytes of its pools
 	agpu::IngestProgress ingest_progress;
 	// --sorted-bam (agpu_sorted_bam.hip): the stream of the last ingest as agpu_ingest_finish left it (it zeroes ingest_stream_size) -- valid until the next agpu_ingest_begin on this

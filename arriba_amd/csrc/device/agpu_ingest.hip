@@ -161,8 +161,10 @@ __global__ void segment_emit_kernel(const uint8_t* bytes, uint64_t size, uint64_
 // its bytes, in a dozen loads whose lines the 10^4 wavefronts in flight push out of the L2 between one load and the next: the counters saw the stream fetched 5.4 times over
 // (profiles/r05t_pmc100m_pmc_summary.txt).  So the wavefront copies its piece of the stream into LDS first, 16 bytes per lane and turn, every line once, and the lanes parse there.
 // A piece that does not fit (reads of some kilobases) is parsed from the stream as before.
+// ROLE (-c, ingest_core.hpp): both passes ignore HI -- every name is "QNAME,1", a secondary record without the tag is kept -- and pass C skips no unmapped record; a record of
+// pass C without a reference (the reference indexes tid_to_contig[-1] there) is counted for the refusal (IC_BROKEN).
 const uint32_t PARSE_WINDOW = 16384;
-__global__ void __launch_bounds__(BLOCK) record_parse_kernel(IngestStream in, GenomeView genome, uint64_t seed, uint64_t record_begin, uint64_t* keys, uint8_t* bits, int32_t* hit_index, uint32_t* counters) {
+template <int ROLE> __global__ void __launch_bounds__(BLOCK) record_parse_kernel(IngestStream in, GenomeView genome, uint64_t seed, uint64_t record_begin, uint64_t* keys, uint8_t* bits, int32_t* hit_index, uint32_t* counters) {
 	__shared__ uint32_t sums[4];
 	__shared__ __attribute__((aligned(16))) uint8_t staged[BLOCK / 64][PARSE_WINDOW + 64];
 	const uint32_t wave = threadIdx.x / 64, lane = threadIdx.x % 64;
@@ -187,16 +189,16 @@ __global__ void __launch_bounds__(BLOCK) record_parse_kernel(IngestStream in, Ge
 			if (!record_sizes_ok(p + 4, block_size)) { status = RECORD_BROKEN; ++broken; }
 			else {
 				const Rec record = load_record_at(in, p);
-				if (!((record.flag & BAMF_UNMAP) || ((record.flag & BAMF_PAIRED) && (record.flag & BAMF_MUNMAP)))) {
+				if (ROLE == ROLE_SEPARATE_CHIMERIC || !((record.flag & BAMF_UNMAP) || ((record.flag & BAMF_PAIRED) && (record.flag & BAMF_MUNMAP)))) {
 					const AuxTags tags = scan_aux(record.aux, record.end);
-					if (!tags.has_hi && (record.flag & BAMF_SECONDARY)) { status = RECORD_MISSING_HI; ++missing; }
+					if (ROLE == ROLE_WHOLE && !tags.has_hi && (record.flag & BAMF_SECONDARY)) { status = RECORD_MISSING_HI; ++missing; }
 					else if (record.contig < 0) { status = RECORD_BROKEN; ++broken; } // reference id outside the header
 					else {
 						status = RECORD_ACTIVE | (tags.has_sa ? RECORD_HAS_SA : 0);
-						key = name_key(record, tags.has_hi ? tags.hi : 1, seed);
-						hit = hit_index_to_keep(tags);
+						key = name_key(record, ROLE == ROLE_WHOLE ? (tags.has_hi ? tags.hi : 1) : 1, seed);
+						hit = ROLE == ROLE_WHOLE ? hit_index_to_keep(tags) : 1;
 						++active;
-						if (!(record.flag & BAMF_SUPPLEMENTARY) && (genome.contig_bits[record.contig] & CBIT_INTERESTING)) ++mapped;
+						if (ROLE != ROLE_SEPARATE_CHIMERIC && !(record.flag & BAMF_SUPPLEMENTARY) && (genome.contig_bits[record.contig] & CBIT_INTERESTING)) ++mapped;
 					}
 				}
 			}
@@ -320,8 +322,9 @@ struct ViralCounter {
 #else
 #define AGPU_PACK_OCCUPANCY
 #endif
-template <bool RUNS> __global__ void __launch_bounds__(BLOCK) AGPU_REPLAY_OCCUPANCY group_replay_kernel(IngestContext ctx, const uint32_t* sorted_records, const uint32_t* group_begin, const uint32_t* group_count, uint32_t first_group, uint32_t n_groups,
-                                                             FragmentPlan* plain, TandemPlan* itd, uint8_t* valid, FragmentSizes* sizes, unsigned long long* viral_counts, uint32_t* qname_differs, uint32_t* counters) {
+// ROLE (-c, ingest_core.hpp): pass R asks `taken` whether the name of the group is a fragment of pass C; the whole file and pass C never read it.
+template <bool RUNS, int ROLE = ROLE_WHOLE> __global__ void __launch_bounds__(BLOCK) AGPU_REPLAY_OCCUPANCY group_replay_kernel(IngestContext ctx, const uint32_t* sorted_records, const uint32_t* group_begin, const uint32_t* group_count, uint32_t first_group, uint32_t n_groups,
+                                                             FragmentPlan* plain, TandemPlan* itd, uint8_t* valid, FragmentSizes* sizes, unsigned long long* viral_counts, uint32_t* qname_differs, uint32_t* counters, TakenNames taken) {
 	__shared__ uint32_t sums[2];
 	GroupTally tally; tally.malformed = 0; tally.chimeric = 0; tally.collision = 0;
 	const uint32_t g = first_group + blockIdx.x * BLOCK + threadIdx.x; // (groups numbered in the order of their first records)
@@ -347,7 +350,7 @@ template <bool RUNS> __global__ void __launch_bounds__(BLOCK) AGPU_REPLAY_OCCUPA
 		}
 		FragmentPlan plain_plan; TandemPlan itd_plan;
 		ViralCounter viral = { viral_counts };
-		replay_group(ctx, sorted_records + begin, n_records, plain_plan, itd_plan, tally, viral, RUNS ? &representative : nullptr, length, hit);
+		replay_group_as<ROLE>(ctx, sorted_records + begin, n_records, plain_plan, itd_plan, tally, viral, RUNS ? &representative : nullptr, length, hit, taken);
 		if (tally.collision) atomicOr(&counters[IC_COLLISION], 1u);
 		Fragment3 fragment;
 		AGPU_NOUNROLL for (uint32_t entry = 0; entry < 2; ++entry) { // the fragment of the name, then its "ITD" entry (one copy of the sanity check in the code: the kernel is 140 KB of instructions as it is)
@@ -567,6 +570,24 @@ __global__ void qname_equal_kernel(const uint64_t* low_sorted, const uint32_t* i
 	const uint64_t k = blockIdx.x * (uint64_t) BLOCK + threadIdx.x;
 	if (k > 0 && k < n && low_sorted[k] == low_sorted[k - 1] && keys[2 * (uint64_t) index_sorted[k] + 1] == keys[2 * (uint64_t) index_sorted[k - 1] + 1]) atomicAdd(equal, 1u);
 }
+// -c: name_key (hit index 1, seed 0) of the QNAME of fragment i of the batch of pass C -- its name is "QNAME,1": the two last bytes are not part of it
+__global__ void separate_name_key_kernel(const char* names, const uint64_t* name_offset, uint64_t n, uint64_t* keys) {
+	const uint64_t i = blockIdx.x * (uint64_t) BLOCK + threadIdx.x;
+	if (i >= n) return;
+	const uint64_t begin = name_offset[i], size = name_offset[i + 1] - begin;
+	keys[i] = qname_bytes_key((const uint8_t*) names + begin, size >= 2 ? (uint32_t) (size - 2) : 0u);
+}
+// -c: row order[i] of the merged batch stays unless it is a single-end fragment of pass C (the rows [0, first_part) in front of the sort)
+// *inconsistent counts the paired split reads of pass C whose SPLIT_READ and SUPPLEMENTARY disagree on first-in-pair behind the first sanity check: both mates carry the same
+// flag there, the second run of the reference would swap them once more and cut the supplementary alignment against the other mate -- not replayed, refused
+__global__ void separate_keep_kernel(const uint32_t* order, uint64_t n, const uint8_t* fbits, const uint8_t* n_aln, const uint8_t* abits_split_read, const uint8_t* abits_supplementary, uint32_t first_part, uint8_t* keep, uint32_t* inconsistent) {
+	const uint64_t i = blockIdx.x * (uint64_t) BLOCK + threadIdx.x;
+	if (i >= n) return;
+	const uint32_t row = order[i];
+	const bool of_pass_c = row < first_part, single_end = fbits[row] & FBIT_SINGLE_END;
+	keep[i] = !(of_pass_c && single_end);
+	if (of_pass_c && !single_end && n_aln[row] == 3 && ((abits_split_read[row] ^ abits_supplementary[row]) & ABIT_FIRST_IN_PAIR)) atomicAdd(inconsistent, 1u);
+}
 __global__ void iota_kernel(uint32_t* out, uint64_t n) { const uint64_t i = blockIdx.x * (uint64_t) BLOCK + threadIdx.x; if (i < n) out[i] = (uint32_t) i; }
 
 // the windows of coverage_t from the prefix sums over the difference array of the replay (ingest_core.hpp: CoverageRange): window i of contig c is slot i + c; the counts in
@@ -661,6 +682,15 @@ int select_flagged(agpu_ctx* ctx, DeviceBuffer& scratch, const uint8_t* flags, u
 	HIP_CHECK(rocprim::select(nullptr, bytes, rocprim::counting_iterator<uint32_t>(0), flags, out, device_count, n, ctx->stream));
 	if (bytes > scratch.capacity) ALLOC(scratch, bytes);
 	HIP_CHECK(rocprim::select(scratch.ptr, bytes, rocprim::counting_iterator<uint32_t>(0), flags, out, device_count, n, ctx->stream));
+	return AGPU_OK;
+}
+
+// the values whose flag is set, in order; *count on the device
+int select_by_flag(agpu_ctx* ctx, DeviceBuffer& scratch, const uint32_t* values, const uint8_t* flags, uint32_t* out, uint32_t* device_count, uint64_t n) {
+	size_t bytes = 0;
+	HIP_CHECK(rocprim::select(nullptr, bytes, values, flags, out, device_count, n, ctx->stream));
+	if (bytes > scratch.capacity) ALLOC(scratch, bytes);
+	HIP_CHECK(rocprim::select(scratch.ptr, bytes, values, flags, out, device_count, n, ctx->stream));
 	return AGPU_OK;
 }
 
@@ -768,7 +798,7 @@ int window_step(agpu_ctx* ctx, IngestWindow& w) {
 		  segment_emit_kernel<<<grid_for(n), BLOCK, 0, s>>>(bytes, w.avail, base, w.segment_begin, w.segment_end, ctx->scratch("ingest.segment_first").as<uint64_t>(), ctx->scratch("ingest.segment_base").as<uint32_t>(), record_offset.as<uint64_t>()); }
 		const IngestStream in = window_stream(ctx, w.avail, w.record_end);
 		{ KernelTimer timer(ctx, "record_parse_kernel", records * (8 + 64 + 9), s);
-		  record_parse_kernel<<<tally_grid(records, BLOCK) * 8, BLOCK, 0, s>>>(in, ctx->genome, 0, w.record_begin, keys.as<uint64_t>(), record_bits.as<uint8_t>(), ctx->scratch("ingest.hit_index").as<int32_t>(), device_counters); }
+		  record_parse_kernel<ROLE_WHOLE><<<tally_grid(records, BLOCK) * 8, BLOCK, 0, s>>>(in, ctx->genome, 0, w.record_begin, keys.as<uint64_t>(), record_bits.as<uint8_t>(), ctx->scratch("ingest.hit_index").as<int32_t>(), device_counters); }
 		auto flags = rocprim::make_transform_iterator(record_bits.as<uint8_t>() + w.record_begin, RecordIsActive());
 		HIP_CHECK(rocprim::select(nullptr, temporary, rocprim::counting_iterator<uint32_t>((uint32_t) w.record_begin), flags, active_records.as<uint32_t>() + w.active_begin, words + 2, records, s));
 		if (temporary > rocprim_scratch.capacity) ALLOC(rocprim_scratch, temporary);
@@ -803,7 +833,7 @@ int window_step(agpu_ctx* ctx, IngestWindow& w) {
 		TRY(grow_keeping(ctx, qname_differs, n_groups * 4, first_group * 4, estimated_groups * 4));
 		{ KernelTimer timer(ctx, "group_replay_kernel", n * SEGMENT_BYTES, s);
 		  group_replay_kernel<true><<<grid_for(groups), BLOCK, 0, s>>>(replay_context(ctx, in), active_records, run_begin, group_count.as<uint32_t>(), (uint32_t) first_group, (uint32_t) n_groups, plain.as<FragmentPlan>(), itd.as<TandemPlan>(), valid.as<uint8_t>(),
-		                                                              sizes.as<FragmentSizes>(), ctx->ingest_viral_counts.as<unsigned long long>(), qname_differs.as<uint32_t>(), device_counters); }
+		                                                              sizes.as<FragmentSizes>(), ctx->ingest_viral_counts.as<unsigned long long>(), qname_differs.as<uint32_t>(), device_counters, TakenNames()); }
 		{ KernelTimer timer(ctx, "run_itd_order_kernel", groups * 2, s);
 		  run_itd_order_kernel<<<grid_for(groups), BLOCK, 0, s>>>(in, group_first.as<uint32_t>(), valid.as<uint8_t>(), (uint32_t) first_group, (uint32_t) n_groups, device_counters); }
 		p.groups_done = n_groups; p.touched = true;
@@ -1012,6 +1042,8 @@ int agpu_ingest_begin(agpu_ctx* ctx, const agpu_ingest_config* config) {
 		for (int k = 0; k < AGPU_PIECE_SLOTS; ++k) { HIP_CHECK(hipEventCreateWithFlags(&ctx->piece_copied[k], hipEventDisableTiming | hipEventBlockingSync)); /* (the thread that waits for a copy leaves its core to the readers of the file) */ HIP_CHECK(hipEventCreateWithFlags(&ctx->piece_ready[k], hipEventDisableTiming)); HIP_CHECK(hipEventCreateWithFlags(&ctx->piece_done[k], hipEventDisableTiming)); }
 	}
 	if (config->host_buffers > AGPU_PIECE_SLOTS) { set_last_error("agpu_ingest_config.host_buffers: at most 4"); return AGPU_ERR_INVALID; }
+	if (config->role > AGPU_ROLE_SEPARATE_RNA || (config->role != AGPU_ROLE_WHOLE && config->part_of_sample)) { set_last_error("agpu_ingest_config.role: AGPU_ROLE_WHOLE, AGPU_ROLE_SEPARATE_CHIMERIC or AGPU_ROLE_SEPARATE_RNA, the latter two not as a part of a sample"); return AGPU_ERR_INVALID; }
+	if (config->role == AGPU_ROLE_SEPARATE_RNA && !ctx->separate_adopted) { set_last_error("the main alignments of -c (AGPU_ROLE_SEPARATE_RNA) come behind agpu_separate_adopt of the separate chimeric file"); return AGPU_ERR_INVALID; }
 	ctx->ingest_host_buffers = config->host_buffers < 2 ? 2 : config->host_buffers;
 	ctx->last_ingest_kept = false; if (ctx->sibling) ctx->sibling->last_ingest_kept = false; // (the stream is written again from here on: no agpu_sorted_bam_begin of the sample before)
 	ctx->ingest_n_targets = config->n_targets; ctx->ingest_first_record = config->first_record_offset; ctx->ingest_stream_size = 0; ctx->ingest_pushes = 0; ctx->ingest_deflated_pieces = false; ctx->ingest_sam = false;
@@ -1019,7 +1051,10 @@ int agpu_ingest_begin(agpu_ctx* ctx, const agpu_ingest_config* config) {
 	ALLOC(ctx->scratch("ingest.crc_mismatches"), 8); // [0] blocks whose payload does not give the CRC-32 of their trailer, [1] deflated blocks that did not decode (read whatever ARRIBA_VERIFY_CRC says)
 	if (ctx->ingest_verify_crc) TRY(upload_crc_tables(ctx));
 	HIP_CHECK(hipMemsetAsync(ctx->scratch("ingest.crc_mismatches").ptr, 0, 8, s));
-	ctx->ingest_external_duplicate_marking = config->external_duplicate_marking; ctx->ingest_max_itd_length = config->max_itd_length; ctx->ingest_part_of_sample = config->part_of_sample != 0;
+	ctx->ingest_external_duplicate_marking = config->external_duplicate_marking; ctx->ingest_max_itd_length = config->max_itd_length;
+	// -c: both passes are done behind the last piece and hand their batch on as a part of a sample does (agpu_separate_adopt, agpu_separate_merge)
+	ctx->ingest_role = config->role; ctx->ingest_part_of_sample = config->part_of_sample != 0 || config->role != AGPU_ROLE_WHOLE;
+	if (config->role != AGPU_ROLE_SEPARATE_RNA) { ctx->separate_adopted = false; ctx->separate_block.release(); ctx->separate_keys.release(); ctx->separate_rows.release(); ctx->separate_n = 0; }
 	ALLOC(ctx->ingest_tid_to_contig, std::max<size_t>(config->n_targets, 1) * 4);
 	if (config->n_targets) HIP_CHECK(hipMemcpyAsync(ctx->ingest_tid_to_contig.ptr, config->tid_to_contig, (size_t) config->n_targets * 4, hipMemcpyHostToDevice, s));
 	ctx->host_coverage_window_offset.assign(config->coverage_window_offset, config->coverage_window_offset + config->n_contigs + 1);
@@ -1307,7 +1342,7 @@ int agpu_ingest_finish(agpu_ctx* ctx, agpu_ingest_result* result) {
 	in.hit_index = nullptr; // (set where the records have been parsed: below)
 
 	ctx->ingest_qname_runs = 0;
-	if (ctx->ingest_part_of_sample && n_records > 0) { // the read names of this part, for the check that no name has records in another part (agpu_shard_merge)
+	if (ctx->ingest_part_of_sample && ctx->ingest_role == AGPU_ROLE_WHOLE && n_records > 0) { // (the two passes of -c may share read names) the read names of this part, for the check that no name has records in another part (agpu_shard_merge)
 		DeviceBuffer& run_flags = ctx->scratch("ingest.run_flags"); DeviceBuffer& run_starts = ctx->scratch("ingest.run_starts");
 		ALLOC(run_flags, n_records); ALLOC(run_starts, n_records * 4);
 		HIP_CHECK(hipMemsetAsync(device_counters, 0, IC_COUNT * 4, s));
@@ -1341,11 +1376,14 @@ int agpu_ingest_finish(agpu_ctx* ctx, agpu_ingest_result* result) {
 		HIP_CHECK(hipMemsetAsync(device_counters, 0, IC_COUNT * 4, s));
 		if (n_records > 0) {
 			{ KernelTimer timer(ctx, "record_parse_kernel", n_records * (8 + 64 + 9));
-			  record_parse_kernel<<<tally_grid(n_records, BLOCK) * 8, BLOCK, 0, s>>>(in, ctx->genome, seed, 0, keys.as<uint64_t>(), record_bits.as<uint8_t>(), ctx->scratch("ingest.hit_index").as<int32_t>(), device_counters); }
+			  const unsigned int parse_grid = tally_grid(n_records, BLOCK) * 8;
+			  if (ctx->ingest_role == AGPU_ROLE_SEPARATE_CHIMERIC) record_parse_kernel<ROLE_SEPARATE_CHIMERIC><<<parse_grid, BLOCK, 0, s>>>(in, ctx->genome, seed, 0, keys.as<uint64_t>(), record_bits.as<uint8_t>(), ctx->scratch("ingest.hit_index").as<int32_t>(), device_counters);
+			  else if (ctx->ingest_role == AGPU_ROLE_SEPARATE_RNA) record_parse_kernel<ROLE_SEPARATE_RNA><<<parse_grid, BLOCK, 0, s>>>(in, ctx->genome, seed, 0, keys.as<uint64_t>(), record_bits.as<uint8_t>(), ctx->scratch("ingest.hit_index").as<int32_t>(), device_counters);
+			  else record_parse_kernel<ROLE_WHOLE><<<parse_grid, BLOCK, 0, s>>>(in, ctx->genome, seed, 0, keys.as<uint64_t>(), record_bits.as<uint8_t>(), ctx->scratch("ingest.hit_index").as<int32_t>(), device_counters); }
 			TRY(sort_pairs<uint64_t>(ctx, rocprim_scratch, keys.as<uint64_t>(), keys_sorted.as<uint64_t>(), nullptr, sorted_records.as<uint32_t>(), n_records, 64, "rocprim::radix_sort_pairs(record keys)", true));
 		}
 		TRY(read_counters());
-		if (host_counters[IC_BROKEN] > 0) { set_last_error("failed to load alignments"); return AGPU_ERR_INVALID; }
+		if (host_counters[IC_BROKEN] > 0) { set_last_error(ctx->ingest_role == AGPU_ROLE_SEPARATE_CHIMERIC ? "failed to load alignments: a record of the separate chimeric file (-c) is damaged or has no reference sequence" : "failed to load alignments"); return AGPU_ERR_INVALID; }
 		n_active = host_counters[IC_ACTIVE];
 		n_groups = 0;
 		if (n_active > 0) {
@@ -1384,9 +1422,18 @@ int agpu_ingest_finish(agpu_ctx* ctx, agpu_ingest_result* result) {
 	ALLOC(refs, 2 * groups1 * 4);
 	uint64_t n_fragments = 0;
 	if (n_groups > 0) {
-		if (!streamed) { KernelTimer timer(ctx, "group_replay_kernel", size - base);
+		if (!streamed && ctx->ingest_role == AGPU_ROLE_SEPARATE_CHIMERIC) { KernelTimer timer(ctx, "group_replay_kernel(separate chimeric)", size - base);
+		  group_replay_kernel<false, ROLE_SEPARATE_CHIMERIC><<<grid_for(n_groups), BLOCK, 0, s>>>(replay_context(ctx, in), sorted_records.as<uint32_t>(), group_begin.as<uint32_t>(), group_count.as<uint32_t>(), 0, n_groups, plain.as<FragmentPlan>(), itd.as<TandemPlan>(), valid.as<uint8_t>(),
+		                                                            sizes.as<FragmentSizes>(), ctx->ingest_viral_counts.as<unsigned long long>(), nullptr, device_counters, TakenNames()); }
+		else if (!streamed && ctx->ingest_role == AGPU_ROLE_SEPARATE_RNA) { KernelTimer timer(ctx, "group_replay_kernel(separate rna)", size - base);
+		  TakenNames taken; // the fragments of pass C (agpu_separate_adopt)
+		  taken.keys = ctx->separate_keys.as<uint64_t>(); taken.rows = ctx->separate_rows.as<uint32_t>(); taken.n = ctx->separate_n;
+		  taken.names = ctx->separate_block.as<char>() + ctx->separate_names_at; taken.name_offset = (const uint64_t*) (ctx->separate_block.as<uint8_t>() + ctx->separate_name_offset_at);
+		  group_replay_kernel<false, ROLE_SEPARATE_RNA><<<grid_for(n_groups), BLOCK, 0, s>>>(replay_context(ctx, in), sorted_records.as<uint32_t>(), group_begin.as<uint32_t>(), group_count.as<uint32_t>(), 0, n_groups, plain.as<FragmentPlan>(), itd.as<TandemPlan>(), valid.as<uint8_t>(),
+		                                                            sizes.as<FragmentSizes>(), ctx->ingest_viral_counts.as<unsigned long long>(), nullptr, device_counters, taken); }
+		else if (!streamed) { KernelTimer timer(ctx, "group_replay_kernel", size - base);
 		  group_replay_kernel<false><<<grid_for(n_groups), BLOCK, 0, s>>>(replay_context(ctx, in), sorted_records.as<uint32_t>(), group_begin.as<uint32_t>(), group_count.as<uint32_t>(), 0, n_groups, plain.as<FragmentPlan>(), itd.as<TandemPlan>(), valid.as<uint8_t>(),
-		                                                            sizes.as<FragmentSizes>(), ctx->ingest_viral_counts.as<unsigned long long>(), nullptr, device_counters); }
+		                                                            sizes.as<FragmentSizes>(), ctx->ingest_viral_counts.as<unsigned long long>(), nullptr, device_counters, TakenNames()); }
 		TRY(select_flagged(ctx, rocprim_scratch, valid.as<uint8_t>(), refs.as<uint32_t>(), device_counters + IC_MAX_NAME, 2 * (uint64_t) n_groups));
 		TRY(read_counters());
 		n_fragments = host_counters[IC_MAX_NAME];
@@ -1568,7 +1615,10 @@ int agpu_shard_export(agpu_ctx* ctx, void* block, uint64_t capacity) {
 	return AGPU_OK;
 }
 
-int agpu_shard_merge(agpu_ctx* ctx, const void* blocks, uint64_t stride, uint32_t n_parts, agpu_ingest_result* result) {
+// separate (-c, agpu_separate_merge): the parts are the batches of pass C and pass R.  They may share QNAMEs, so the merged rows are always put in name order and their read-name
+// groups numbered again; the single-end fragments of part 0 are left out and counted (*separate_dropped): what the second run of remove_malformed_alignments does to them.
+static const char* const SEPARATE_SAME_MATE_FLAGS = "a paired split read of the separate chimeric file (-c) has two mates with the same first-in-pair flag: not supported";
+static int shard_merge_parts(agpu_ctx* ctx, const void* blocks, uint64_t stride, uint32_t n_parts, agpu_ingest_result* result, bool separate, uint64_t* separate_dropped) {
 	if (!ctx || !blocks || n_parts == 0 || (stride & 15) != 0) { set_last_error("agpu_shard_merge takes the blocks of all parts at a stride that is a multiple of 16 bytes"); return AGPU_ERR_INVALID; }
 	if (!ctx->have_annotation || !ctx->have_genome || ctx->host_coverage_window_offset.empty()) { set_last_error("the context must have ingested its own part before the parts are merged"); return AGPU_ERR_INVALID; }
 	HIP_CHECK(hipSetDevice(ctx->device));
@@ -1691,7 +1741,7 @@ int agpu_shard_merge(agpu_ctx* ctx, const void* blocks, uint64_t stride, uint32_
 	TRY(agpu::finish_batch_setup(ctx));
 	ctx->batch_from_ingest = true; ctx->ingest_part_of_sample = false;
 	ctx->coverage_windows32.release(); ctx->scratch("shard.blocks").release();
-	if (!parts_in_name_order && n > 1) {
+	if (separate ? n > 0 : (!parts_in_name_order && n > 1)) {
 		// The fragments of the whole sample in name order: least-significant-chunk-first radix sort over the 8-byte chunks of the packed names (as the ingest does
 		// it for the records of one part), the rows moved by the kernels of agpu_gather_rows_*, the read-name groups numbered again.
 		DeviceBuffer& order = ctx->scratch("shard.order"); DeviceBuffer& order_out = ctx->scratch("shard.order_out"); DeviceBuffer& keys = ctx->scratch("shard.keys"); DeviceBuffer& keys_out = ctx->scratch("shard.keys_out");
@@ -1708,21 +1758,43 @@ int agpu_shard_merge(agpu_ctx* ctx, const void* blocks, uint64_t stride, uint32_
 			TRY(sort_pairs<uint64_t>(ctx, rocprim_scratch, keys.as<uint64_t>(), keys_out.as<uint64_t>(), order.as<uint32_t>(), order_out.as<uint32_t>(), n, 64, "rocprim::radix_sort_pairs(name chunk of the merged batch)", false));
 			order.swap(order_out);
 		}
-		packed_name_neighbours_kernel<<<grid_for(n), BLOCK, 0, s>>>(ctx->names.as<char>(), ctx->name_offset.as<uint64_t>(), order.as<uint32_t>(), n, new_group.as<uint32_t>(), small.as<uint32_t>() + 1);
+		uint64_t kept = n;
+		if (separate) { // the rows that survive the second sanity check, still in name order
+			DeviceBuffer& keep = ctx->scratch("shard.keep");
+			ALLOC(keep, n);
+			HIP_CHECK(hipMemsetAsync(small.as<uint32_t>(), 0, 8, s));
+			separate_keep_kernel<<<grid_for(n), BLOCK, 0, s>>>(order.as<uint32_t>(), n, ctx->fbits.as<uint8_t>(), ctx->n_aln.as<uint8_t>(), ctx->abits[SPLIT_READ].as<uint8_t>(), ctx->abits[SUPPLEMENTARY].as<uint8_t>(), (uint32_t) parts[0].n, keep.as<uint8_t>(), small.as<uint32_t>() + 1);
+			uint32_t inconsistent = 0;
+			HIP_CHECK(hipMemcpyAsync(&inconsistent, small.as<uint32_t>() + 1, 4, hipMemcpyDeviceToHost, s));
+			HIP_CHECK(hipStreamSynchronize(s));
+			if (inconsistent > 0) { ctx->have_batch = false; set_last_error(SEPARATE_SAME_MATE_FLAGS); return AGPU_ERR_INVALID; }
+			HIP_CHECK(hipMemsetAsync(small.as<uint32_t>(), 0, 8, s));
+			HIP_CHECK(hipMemcpyAsync(keys.ptr, order.ptr, n * 4, hipMemcpyDeviceToDevice, s)); // (the keys of the sort are done with)
+			TRY(select_by_flag(ctx, rocprim_scratch, keys.as<uint32_t>(), keep.as<uint8_t>(), order.as<uint32_t>(), small.as<uint32_t>(), n));
+			uint32_t count = 0;
+			HIP_CHECK(hipMemcpyAsync(&count, small.ptr, 4, hipMemcpyDeviceToHost, s));
+			HIP_CHECK(hipStreamSynchronize(s));
+			kept = count; keep.release();
+			if (separate_dropped) *separate_dropped = n - kept;
+		}
+		if (kept > 0) packed_name_neighbours_kernel<<<grid_for(kept), BLOCK, 0, s>>>(ctx->names.as<char>(), ctx->name_offset.as<uint64_t>(), order.as<uint32_t>(), kept, new_group.as<uint32_t>(), small.as<uint32_t>() + 1);
 		uint32_t equal_names = 0;
 		HIP_CHECK(hipMemcpyAsync(&equal_names, small.as<uint32_t>() + 1, 4, hipMemcpyDeviceToHost, s));
 		HIP_CHECK(hipStreamSynchronize(s));
-		if (equal_names > 0) { ctx->have_batch = false; set_last_error("a read name occurs in more than one part of the sample: the alignments of a read must follow each other in the file (STAR's output order; samtools collate otherwise)"); return AGPU_ERR_INVALID; }
+		if (equal_names > 0) { ctx->have_batch = false; set_last_error(separate ? "a fragment name occurs in both passes of -c" : "a read name occurs in more than one part of the sample: the alignments of a read must follow each other in the file (STAR's output order; samtools collate otherwise)"); return AGPU_ERR_INVALID; }
 		uint64_t pool_sizes[3];
-		TRY(gather_rows_prepare(ctx, order.as<uint32_t>(), n, pool_sizes));
+		TRY(gather_rows_prepare(ctx, order.as<uint32_t>(), kept, pool_sizes));
 		agpu_batch_rows nowhere; memset(&nowhere, 0, sizeof(nowhere)); // (the rows stay on the device: in the scratch buffers "gather.*")
 		TRY(agpu_gather_rows_copy(ctx, &nowhere));
 		{ // the gathered columns become the batch
 			size_t bytes = 0;
-			HIP_CHECK(rocprim::inclusive_scan(nullptr, bytes, new_group.as<uint32_t>(), ctx->scratch("gather.group").as<uint32_t>(), n, rocprim::plus<uint32_t>(), s));
-			if (bytes > rocprim_scratch.capacity) ALLOC(rocprim_scratch, bytes);
-			HIP_CHECK(rocprim::inclusive_scan(rocprim_scratch.ptr, bytes, new_group.as<uint32_t>(), ctx->scratch("gather.group").as<uint32_t>(), n, rocprim::plus<uint32_t>(), s));
+			if (kept > 0) {
+				HIP_CHECK(rocprim::inclusive_scan(nullptr, bytes, new_group.as<uint32_t>(), ctx->scratch("gather.group").as<uint32_t>(), kept, rocprim::plus<uint32_t>(), s));
+				if (bytes > rocprim_scratch.capacity) ALLOC(rocprim_scratch, bytes);
+				HIP_CHECK(rocprim::inclusive_scan(rocprim_scratch.ptr, bytes, new_group.as<uint32_t>(), ctx->scratch("gather.group").as<uint32_t>(), kept, rocprim::plus<uint32_t>(), s));
+			}
 			HIP_CHECK(hipStreamSynchronize(s));
+			if (kept != n) { ctx->n = kept; ctx->names_size = pool_sizes[2]; ctx->ingest_pool_sizes[0] = pool_sizes[0]; ctx->ingest_pool_sizes[1] = pool_sizes[1]; }
 			ctx->n_aln.swap(ctx->scratch("gather.n_aln")); ctx->fbits.swap(ctx->scratch("gather.fbits")); ctx->group.swap(ctx->scratch("gather.group"));
 			static const char* const slot_names[3][6] = { { "gather.contig0", "gather.start0", "gather.end0", "gather.abits0", "gather.cigar_offset0", "gather.cigar_count0" }, { "gather.contig1", "gather.start1", "gather.end1", "gather.abits1", "gather.cigar_offset1", "gather.cigar_count1" },
 			                                              { "gather.contig2", "gather.start2", "gather.end2", "gather.abits2", "gather.cigar_offset2", "gather.cigar_count2" } };
@@ -1743,8 +1815,65 @@ int agpu_shard_merge(agpu_ctx* ctx, const void* blocks, uint64_t stride, uint32_
 	}
 	agpu_ingest_result& whole = ctx->ingest_result;
 	memset(&whole, 0, sizeof(whole));
-	whole.records = total.records; whole.fragments = n; whole.mapped_reads = total.mapped_reads; whole.malformed_count = total.malformed_count; whole.missing_hi_tag = total.missing_hi_tag;
+	whole.records = total.records; whole.fragments = ctx->n; whole.mapped_reads = total.mapped_reads; whole.malformed_count = total.malformed_count; whole.missing_hi_tag = total.missing_hi_tag;
 	whole.no_chimeric_reads = (uint8_t) total.no_chimeric_reads; whole.names_were_sorted = (uint8_t) total.names_were_sorted; whole.stream_bytes = total.stream_bytes;
+	if (result) *result = whole;
+	return AGPU_OK;
+}
+
+int agpu_shard_merge(agpu_ctx* ctx, const void* blocks, uint64_t stride, uint32_t n_parts, agpu_ingest_result* result) { return shard_merge_parts(ctx, blocks, stride, n_parts, result, false, nullptr); }
+
+// ---- -c: the batch of pass C set aside, looked up by pass R, and both as one (include/arriba_gpu.h) --------------------------------------------
+
+int agpu_separate_adopt(agpu_ctx* ctx) {
+	if (!ctx || !ctx->batch_from_ingest || ctx->ingest_active || ctx->ingest_role != AGPU_ROLE_SEPARATE_CHIMERIC || !ctx->ingest_part_of_sample || ctx->annotated) { set_last_error("agpu_separate_adopt comes behind agpu_ingest_finish of an ingest with role AGPU_ROLE_SEPARATE_CHIMERIC"); return AGPU_ERR_INVALID; }
+	HIP_CHECK(hipSetDevice(ctx->device));
+	hipStream_t s = ctx->stream;
+	ShardHeader h;
+	TRY(shard_header_of(ctx, h));
+	const ShardLayout layout = shard_layout(h);
+	ALLOC(ctx->separate_block, std::max<uint64_t>(h.total_bytes, 16));
+	TRY(agpu_shard_export(ctx, ctx->separate_block.ptr, h.total_bytes));
+	ctx->separate_block_bytes = h.total_bytes; ctx->separate_n = h.n; ctx->separate_names_at = layout.offset[SHARD_NAMES]; ctx->separate_name_offset_at = layout.offset[SHARD_NAME_OFFSET];
+	ctx->separate_result = ctx->ingest_result;
+	const uint64_t n = h.n, n1 = std::max<uint64_t>(n, 1);
+	ALLOC(ctx->separate_keys, n1 * 8); ALLOC(ctx->separate_rows, n1 * 4);
+	if (n > 0) { // the key of every QNAME, ascending, with the fragment it belongs to
+		DeviceBuffer& unsorted = ctx->scratch("separate.keys_unsorted"); DeviceBuffer& rocprim_scratch = ctx->scratch("shard.rocprim");
+		ALLOC(unsorted, n * 8);
+		{ KernelTimer timer(ctx, "separate_name_key_kernel", n * 8 + h.names_bytes);
+		  separate_name_key_kernel<<<grid_for(n), BLOCK, 0, s>>>(ctx->names.as<char>(), ctx->name_offset.as<uint64_t>(), n, unsorted.as<uint64_t>()); }
+		TRY(sort_pairs<uint64_t>(ctx, rocprim_scratch, unsorted.as<uint64_t>(), ctx->separate_keys.as<uint64_t>(), nullptr, ctx->separate_rows.as<uint32_t>(), n, 64, "rocprim::radix_sort_pairs(names of the separate chimeric file)", true));
+		HIP_CHECK(hipStreamSynchronize(s));
+		unsorted.release();
+	}
+	// the stream of pass C is not needed any more: pass R grows its own into the same buffer
+	ctx->have_batch = false; ctx->batch_from_ingest = false; ctx->last_ingest_kept = false;
+	ctx->separate_adopted = true;
+	return AGPU_OK;
+}
+
+int agpu_separate_merge(agpu_ctx* ctx, agpu_ingest_result* result) {
+	if (!ctx || !ctx->separate_adopted || !ctx->batch_from_ingest || ctx->ingest_active || ctx->ingest_role != AGPU_ROLE_SEPARATE_RNA || !ctx->ingest_part_of_sample || ctx->annotated) { set_last_error("agpu_separate_merge comes behind agpu_separate_adopt and agpu_ingest_finish of an ingest with role AGPU_ROLE_SEPARATE_RNA"); return AGPU_ERR_INVALID; }
+	HIP_CHECK(hipSetDevice(ctx->device));
+	const agpu_ingest_result rna = ctx->ingest_result;
+	ShardHeader h;
+	TRY(shard_header_of(ctx, h));
+	const uint64_t stride = (std::max<uint64_t>(h.total_bytes, ctx->separate_block_bytes) + 15) & ~(uint64_t) 15;
+	DeviceBuffer& both = ctx->scratch("separate.blocks");
+	ALLOC(both, 2 * stride);
+	HIP_CHECK(hipMemcpy(both.ptr, ctx->separate_block.ptr, ctx->separate_block_bytes, hipMemcpyDeviceToDevice));
+	TRY(agpu_shard_export(ctx, both.as<uint8_t>() + stride, stride));
+	ctx->separate_adopted = false; ctx->separate_block.release(); ctx->separate_keys.release(); ctx->separate_rows.release(); ctx->separate_n = 0;
+	uint64_t dropped = 0;
+	const int status = shard_merge_parts(ctx, both.ptr, stride, 2, nullptr, true, &dropped);
+	both.release();
+	ctx->ingest_role = AGPU_ROLE_WHOLE;
+	if (status != AGPU_OK) return status;
+	agpu_ingest_result& whole = ctx->ingest_result; // what the reference's second call of read_chimeric_alignments reports (the first call made its own report: agpu_ingest_finish of pass C)
+	whole.records = rna.records + ctx->separate_result.records; whole.mapped_reads = rna.mapped_reads; whole.malformed_count = rna.malformed_count + dropped; whole.missing_hi_tag = rna.missing_hi_tag;
+	whole.no_chimeric_reads = 0; whole.stream_bytes = rna.stream_bytes + ctx->separate_result.stream_bytes;
+	ctx->last_ingest_part_of_sample = true; // (the resident stream is that of pass R alone: nothing that reads "the records of -x" may take it for the sample)
 	if (result) *result = whole;
 	return AGPU_OK;
 }

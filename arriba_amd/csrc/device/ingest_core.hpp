@@ -248,6 +248,11 @@ AGPU_HD int64_t hit_index_of(const IngestStream& in, uint32_t record, const Rec&
 	return tags.has_hi ? tags.hi : 1;
 }
 
+// What a stream is to the loop (the two booleans of read_chimeric_alignments, source/read_chimeric_alignments.cpp:560): the one file of STAR --chimOutType WithinBAM, or -- with
+// -c -- Chimeric.out.sam (pass C: separate_chimeric_bam_file, !is_rna_bam_file) and then the main alignments (pass R: both true).  A template parameter wherever the loop is
+// restated: ROLE_WHOLE is the code that was there before the roles.
+enum : int { ROLE_WHOLE = 0, ROLE_SEPARATE_CHIMERIC = 1, ROLE_SEPARATE_RNA = 2 };
+
 // per-record verdict of the first lines of the loop body (source/read_chimeric_alignments.cpp:611-631)
 enum : uint8_t { RECORD_SKIPPED = 0, RECORD_ACTIVE = 1, RECORD_MISSING_HI = 2, RECORD_BROKEN = 3, RECORD_STATUS_MASK = 3, RECORD_HAS_SA = 4 };
 
@@ -286,6 +291,32 @@ AGPU_HD bool same_name(const Rec& a, uint32_t length_a /* qname_length(a) */, in
 	return first_difference(a.name, b.name, length_a) == length_a;
 }
 AGPU_HD bool same_name(const Rec& a, int64_t hi_a, const Rec& b, int64_t hi_b) { return same_name(a, qname_length(a), hi_a, b, hi_b); }
+
+// -c: the fragments pass C left behind its sanity check, as pass R asks for them -- "is QNAME,1 a fragment already?" (the failed insert of extract_read_through_alignment).
+// keys: name_key (hit index 1, seed 0) of the QNAME of every fragment, ascending; rows: the fragment each key belongs to; names / name_offset: the packed names of that batch
+// ("QNAME,1" all of them: pass C ignores HI and makes no "ITD" entries).  A key found is confirmed on the bytes: two names with one key do not block each other.
+struct TakenNames { const uint64_t* keys; const uint32_t* rows; uint64_t n; const char* names; const uint64_t* name_offset; };
+AGPU_HD uint64_t qname_bytes_key(const uint8_t* qname, uint32_t length) { // == name_key(record, 1, 0) of a record with that QNAME
+	uint64_t h = 1469598103934665603ull;
+	for (uint32_t i = 0; i < length; ++i) h = (h ^ qname[i]) * 1099511628211ull;
+	h ^= 0x9E3779B97F4A7C15ull;
+	h ^= h >> 33; h *= 0xFF51AFD7ED558CCDull; h ^= h >> 33; h *= 0xC4CEB9FE1A85EC53ull; h ^= h >> 33;
+	return h == ~0ull ? ~0ull - 1 : h;
+}
+AGPU_HD bool name_is_taken(const TakenNames& taken, const uint8_t* qname, uint32_t length) {
+	if (taken.n == 0) return false;
+	const uint64_t key = qname_bytes_key(qname, length);
+	uint64_t lo = 0, hi = taken.n;
+	while (lo < hi) { const uint64_t mid = lo + (hi - lo) / 2; if (taken.keys[mid] < key) lo = mid + 1; else hi = mid; }
+	for (; lo < taken.n && taken.keys[lo] == key; ++lo) {
+		const uint64_t begin = taken.name_offset[taken.rows[lo]], size = taken.name_offset[taken.rows[lo] + 1] - begin;
+		if (size != (uint64_t) length + 2) continue;
+		uint32_t i = 0;
+		while (i < length && (uint8_t) taken.names[begin + i] == qname[i]) ++i;
+		if (i == length) return true;
+	}
+	return false;
+}
 
 // ---- plans: a fragment as references into the stream ----------------------------------------------------------------------------------------------
 
@@ -596,7 +627,8 @@ AGPU_HD void boundaries_of_biggest_gene(const AnnotationView& ann, ListRef genes
 }
 
 // reference: source/read_chimeric_alignments.cpp:93-193.  `record` is never null; `previous` may be.
-AGPU_HD bool extract_read_through_alignment(FragmentPlan& plan, uint32_t record_index, const Rec& record, uint32_t previous_index, const Rec* previous, const AnnotationView& ann) {
+// name_taken (pass R of -c): the name is a fragment of pass C already -- the insert fails as it does on a name of this pass
+AGPU_HD bool extract_read_through_alignment(FragmentPlan& plan, uint32_t record_index, const Rec& record, uint32_t previous_index, const Rec* previous, const AnnotationView& ann, bool name_taken = false) {
 	const Rec* forward_mate = &record; const Rec* reverse_mate = previous;
 	uint32_t forward_index = record_index, reverse_index = previous_index;
 	if (!forward_mate->forward()) { const Rec* t = forward_mate; forward_mate = reverse_mate; reverse_mate = t; const uint32_t ti = forward_index; forward_index = reverse_index; reverse_index = ti; }
@@ -618,7 +650,7 @@ AGPU_HD bool extract_read_through_alignment(FragmentPlan& plan, uint32_t record_
 	int32_t forward_read_pos = 0, reverse_read_pos = 0;
 	const bool forward_has_intron = (forward_mate == nullptr) ? false : find_spanning_intron(*forward_mate, forward_gene_end, reverse_gene_start, forward_cigar_op, forward_read_pos);
 	const bool reverse_has_intron = (reverse_mate == nullptr) ? false : find_spanning_intron(*reverse_mate, forward_gene_end, reverse_gene_start, reverse_cigar_op, reverse_read_pos);
-	const bool is_new = plan.count == 0; // fragments.insert(...).second
+	const bool is_new = plan.count == 0 && !name_taken; // fragments.insert(...).second
 	if (forward_has_intron && (!reverse_has_intron || forward_read_pos < reverse_mate->l_seq - reverse_read_pos)) {
 		if (is_new) {
 			plan_push(plan, forward_index, *forward_mate, false, forward_cigar_op + 1, CLIP_START);
@@ -764,8 +796,11 @@ struct GroupTally { uint32_t malformed; uint32_t chimeric; uint32_t collision; }
 // `records` = the indices of the active records of one "QNAME,HI" in stream order.  plain = fragments[read_name], itd = fragments[read_name + "ITD"].
 // viral_reads[contig] += pristine reads (64-bit counters).
 // names_of != nullptr: the records were put together by their keys and nobody has compared their names yet -- every record against *names_of, the first one, while it is at hand
-template <class ViralCounter> AGPU_HD void replay_group(const IngestContext& ctx, const uint32_t* records, uint32_t n_records, FragmentPlan& plain, TandemPlan& itd, GroupTally& tally, ViralCounter& count_viral_read,
-                                                        const Rec* names_of = nullptr, uint32_t length_of_names = 0 /* qname_length(*names_of) */, int64_t hit_index_of_names = 0) {
+// ROLE (-c): pass C adds every record -- a secondary one as the supplementary alignment at once, a paired one with its parked mate, a third paired record parks again and is never
+// added (:634-638, :692-698) -- and touches neither coverage nor counters; pass R is the loop of the whole file that adds nothing but "ITD" entries and read-throughs, the latter
+// only where the name is not a fragment of pass C (name_is_taken, asked in front of that insert alone), and drops supplementary records unseen (:641-650, :657-668, :723-733).
+template <int ROLE, class ViralCounter> AGPU_HD void replay_group_as(const IngestContext& ctx, const uint32_t* records, uint32_t n_records, FragmentPlan& plain, TandemPlan& itd, GroupTally& tally, ViralCounter& count_viral_read,
+                                                                     const Rec* names_of, uint32_t length_of_names /* qname_length(*names_of) */, int64_t hit_index_of_names, const TakenNames& taken) {
 	plan_clear(plain); plan_clear(itd.plan);
 	itd.tandem.start = 0; itd.tandem.end = 0; itd.tandem.cigar[0] = itd.tandem.cigar[1] = itd.tandem.cigar[2] = 0; itd.tandem.record = NO_RECORD;
 	itd.tandem.n_cigar = 0; itd.tandem.strand = 0; itd.tandem.first_in_pair = 0; itd.tandem.supplementary = 0;
@@ -774,7 +809,20 @@ template <class ViralCounter> AGPU_HD void replay_group(const IngestContext& ctx
 		const uint32_t index = records[k];
 		const Rec record = load_record(ctx.stream, index);
 		if (names_of != nullptr && k > 0 && !same_name(*names_of, length_of_names, hit_index_of_names, record, hit_index_of(ctx.stream, index, record))) tally.collision = 1;
+		if (ROLE == ROLE_SEPARATE_CHIMERIC) {
+			if (record.flag & BAMF_SECONDARY) { plan_push(plain, index, record, true, 0, CLIP_NONE); tally.chimeric = 1; continue; }
+			uint32_t mate = NO_RECORD;
+			if (record.flag & BAMF_PAIRED) {
+				if (parked == NO_RECORD) { parked = index; continue; }
+				mate = parked; parked = NO_RECORD;
+			}
+			plan_push(plain, index, record, false, 0, CLIP_NONE);
+			if (mate != NO_RECORD) plan_push(plain, mate, load_record(ctx.stream, mate), false, 0, CLIP_NONE);
+			tally.chimeric = 1;
+			continue;
+		}
 		if (record.flag & BAMF_SUPPLEMENTARY) {
+			if (ROLE == ROLE_SEPARATE_RNA) continue; // (don't load alignments twice)
 			if (is_clipped_at_correct_end(record)) plan_push(plain, index, record, true, 0, CLIP_NONE);
 			else tally.malformed++;
 			tally.chimeric = 1;
@@ -788,8 +836,10 @@ template <class ViralCounter> AGPU_HD void replay_group(const IngestContext& ctx
 		uint16_t coverage_flag = record.flag;
 		const bool discordant_mate = (record.flag & BAMF_PAIRED) && !(record.flag & BAMF_PROPER_PAIR);
 		if (discordant_mate) {
-			plan_push(plain, index, record, false, 0, CLIP_NONE);
-			tally.chimeric = 1;
+			if (ROLE != ROLE_SEPARATE_RNA) {
+				plan_push(plain, index, record, false, 0, CLIP_NONE);
+				tally.chimeric = 1;
+			}
 			coverage_flag = 0; is_read_through = true; // (the reference zeroes the flag word and passes is_chimeric = true)
 		} else {
 			if (record.flag & BAMF_PAIRED) {
@@ -813,11 +863,14 @@ template <class ViralCounter> AGPU_HD void replay_group(const IngestContext& ctx
 			}
 			const bool record_has_sa = ctx.record_bits[index] & RECORD_HAS_SA, previous_has_sa = previous != nullptr && (ctx.record_bits[previous_index] & RECORD_HAS_SA);
 			if ((record_has_sa && is_clipped_at_correct_end(record)) || (previous_has_sa && is_clipped_at_correct_end(*previous))) {
-				plan_push(plain, index, record, false, 0, CLIP_NONE);
-				if (previous != nullptr) plan_push(plain, previous_index, *previous, false, 0, CLIP_NONE);
-				tally.chimeric = 1;
+				if (ROLE != ROLE_SEPARATE_RNA) {
+					plan_push(plain, index, record, false, 0, CLIP_NONE);
+					if (previous != nullptr) plan_push(plain, previous_index, *previous, false, 0, CLIP_NONE);
+					tally.chimeric = 1;
+				}
 			} else if (!is_tandem_alignment) {
-				is_read_through = extract_read_through_alignment(plain, index, record, previous_index, previous, ctx.annotation);
+				is_read_through = extract_read_through_alignment(plain, index, record, previous_index, previous, ctx.annotation,
+				                                                 ROLE == ROLE_SEPARATE_RNA && name_is_taken(taken, record.name, qname_length(record))); // (asked only here, where an insert may follow: few pairs come this far)
 				if (record.contig >= 0 && (ctx.genome.contig_bits[record.contig] & CBIT_VIRAL)) {
 					AGPU_NOUNROLL for (uint32_t mate = 0; mate < 2; ++mate) { const Rec* read = mate ? previous : &record; if (read != nullptr && is_pristine_alignment(*read)) count_viral_read((uint32_t) read->contig); }
 				}
@@ -825,6 +878,12 @@ template <class ViralCounter> AGPU_HD void replay_group(const IngestContext& ctx
 		}
 		if (!ctx.external_duplicate_marking || !(record.flag & BAMF_DUP)) add_fragment_to_coverage(ctx.coverage, record, coverage_flag, previous, is_read_through);
 	}
+}
+
+// the one file of --chimOutType WithinBAM
+template <class ViralCounter> AGPU_HD void replay_group(const IngestContext& ctx, const uint32_t* records, uint32_t n_records, FragmentPlan& plain, TandemPlan& itd, GroupTally& tally, ViralCounter& count_viral_read,
+                                                        const Rec* names_of = nullptr, uint32_t length_of_names = 0 /* qname_length(*names_of) */, int64_t hit_index_of_names = 0) {
+	replay_group_as<ROLE_WHOLE>(ctx, records, n_records, plain, itd, tally, count_viral_read, names_of, length_of_names, hit_index_of_names, TakenNames());
 }
 
 // ---- sanity check and slot order (reference: remove_malformed_alignments, source/read_chimeric_alignments.cpp:377-506) -----------------------------

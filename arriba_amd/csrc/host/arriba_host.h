@@ -203,7 +203,9 @@ struct IngestResult {
 	std::vector<uint64_t> mapped_viral_reads_by_contig;
 	unsigned int malformed_count = 0, missing_hi_tag = 0;
 	uint64_t records = 0;
+	uint64_t separate_fragments = 0; unsigned int separate_malformed_count = 0; // -c: what pass C (the separate chimeric file) reported: its "(total=N)" and its WARNING
 };
+enum { INGEST_ROLE_WHOLE = 0, INGEST_ROLE_SEPARATE_CHIMERIC = 1, INGEST_ROLE_SEPARATE_RNA = 2 }; // what a file is to the loop of read_chimeric_alignments (its two booleans)
 
 // Streaming source of uncompressed BAM bytes; returns the number of bytes delivered (0 = end of data).
 struct ByteSource { virtual size_t read(uint8_t* buffer, size_t capacity) = 0; virtual ~ByteSource() {} };
@@ -342,6 +344,8 @@ const std::vector<uint8_t>& bam_feed_header_bytes(BamFeed* feed); // the head of
 // reference: source/read_chimeric_alignments.cpp:560-773 with separate_chimeric_bam_file=false, is_rna_bam_file=true
 // gene_index must be the index over the GTF genes (before dummy genes are added).
 void read_chimeric_alignments(ByteSource& source, const Assembly& assembly, Contigs& contigs, const Annotation& annotation, const FlatIndex& gene_index, const IngestOptions& options, IngestResult& result);
+// -c: the same with separate_chimeric_bam_file=true, twice over one table of fragments (source/arriba.cpp:123-130): is_rna_bam_file=false over `chimeric_source`, true over `rna_source`
+void read_chimeric_alignments_separate(ByteSource& chimeric_source, ByteSource& rna_source, const Assembly& assembly, Contigs& contigs, const Annotation& annotation, const FlatIndex& gene_index, const IngestOptions& options, IngestResult& result);
 
 }
 

@@ -70,6 +70,8 @@ struct ahost_session {
 	// device ingest: the open file and what agpu_ingest_begin needs from its header
 	BamFeed* feed = nullptr;
 	bool device_batch = false;           // the fragments live on the device (ahost_adopt_device_ingest)
+	std::vector<std::string> last_target_names; // the reference names of the header of the last ahost_bam_open
+	std::vector<std::string> separate_target_names; // -c: the reference names of the separate chimeric file, which those of the main alignments must equal (ahost_bam_open_role)
 	Batch spare_rows;                    // the vectors of the last sample's rows (ahost_set_batch_rows), kept over ahost_bam_open for the next sample's
 	// ahost_detach_sample: a writer thread holds what a sample left behind while the session reads the next one.  It shares the reference data of the session that no sample changes
 	// (annotation, assembly, tags, protein domains) and takes a copy of `contigs` -- ahost_bam_open stores the names of the next header there
@@ -453,6 +455,23 @@ int ahost_ingest_bam_file(ahost_session* session, const char* bam_path, int exte
 	try { return ingest(session, open_bam_file(bam_path), external_duplicate_marking, max_itd_length); }
 	catch (const std::exception& e) { g_error = e.what(); return -1; }
 }
+int ahost_ingest_separate(ahost_session* session, const char* chimeric_path, const char* rna_path, int external_duplicate_marking, unsigned int max_itd_length, uint64_t* chimeric_fragments, uint64_t* chimeric_malformed) {
+	if (!session || !chimeric_path || !rna_path) { g_error = "null argument"; return -1; }
+	try {
+		std::unique_ptr<ByteSource> chimeric(open_bam_file(chimeric_path)), rna(open_bam_file(rna_path));
+		session->options.external_duplicate_marking = external_duplicate_marking != 0;
+		session->options.max_itd_length = max_itd_length;
+		session->ingest = IngestResult(); session->sample_was_detached = false;
+		session->row_fragments.clear(); session->device_batch = false; session->rows_in_list_order = false;
+		read_chimeric_alignments_separate(*chimeric, *rna, session->assembly, session->contigs, session->annotation, session->gene_index, session->options, session->ingest);
+		if (chimeric_fragments) *chimeric_fragments = session->ingest.separate_fragments;
+		if (chimeric_malformed) *chimeric_malformed = session->ingest.separate_malformed_count;
+		session->build_genome_view();
+		session->build_batch_view();
+		session->have_batch = true;
+		return 0;
+	} catch (const std::exception& e) { g_error = e.what(); return -1; }
+}
 int ahost_save_ingest(ahost_session* session, const char* path) {
 	if (!session || !session->have_batch) { g_error = "no BAM ingested yet"; return -1; }
 	FILE* file = fopen(path, "wb");
@@ -526,6 +545,7 @@ int ahost_bam_open(ahost_session* session, const char* bam_path, int external_du
 		std::vector<std::string> target_names;
 		const uint64_t header_size = bam_feed_header(session->feed, target_names);
 		session->input_header = bam_feed_header_bytes(session->feed);
+		session->last_target_names = target_names;
 		// reference: source/read_chimeric_alignments.cpp:566-582 (contigs of the header join contigs_t; interesting contigs need a sequence)
 		session->tid_to_contig.resize(target_names.size());
 		for (size_t target = 0; target < target_names.size(); ++target) session->tid_to_contig[target] = session->contigs.add(target_names[target]);
@@ -543,6 +563,21 @@ int ahost_bam_open(ahost_session* session, const char* bam_path, int external_du
 		config->first_record_offset = header_size; config->stream_size_hint = bam_feed_size_hint(session->feed);
 		config->n_contigs = (uint32_t) session->contigs.size(); config->coverage_window_offset = session->window_offset.data();
 		config->external_duplicate_marking = external_duplicate_marking != 0; config->max_itd_length = max_itd_length;
+		return 0;
+	} catch (const std::exception& e) { g_error = e.what(); return -1; }
+}
+
+int ahost_bam_open_role(ahost_session* session, const char* bam_path, int external_duplicate_marking, unsigned int max_itd_length, int role, agpu_ingest_config* config) {
+	if (role < AGPU_ROLE_WHOLE || role > AGPU_ROLE_SEPARATE_RNA) { g_error = "ahost_bam_open_role: role must be AGPU_ROLE_WHOLE, AGPU_ROLE_SEPARATE_CHIMERIC or AGPU_ROLE_SEPARATE_RNA"; return -1; }
+	if (ahost_bam_open(session, bam_path, external_duplicate_marking, max_itd_length, config) != 0) return -1;
+	try {
+		const std::vector<std::string>& target_names = session->last_target_names;
+		if (role == AGPU_ROLE_SEPARATE_RNA && target_names != session->separate_target_names) {
+			close_bam_feed(session->feed); session->feed = nullptr;
+			throw std::runtime_error("the headers of the separate chimeric file (-c) and of the main alignments (-x) do not list the same reference sequences in the same order");
+		}
+		if (role == AGPU_ROLE_SEPARATE_CHIMERIC) session->separate_target_names = target_names; else session->separate_target_names.clear();
+		config->role = (uint8_t) role;
 		return 0;
 	} catch (const std::exception& e) { g_error = e.what(); return -1; }
 }
@@ -1331,6 +1366,7 @@ const agpu_batch_view* ahost_batch_slice_view(ahost_session* session, uint64_t f
 }
 uint64_t ahost_fragment_count(ahost_session* session) { return session->ingest.batch.n; }
 uint64_t ahost_mapped_reads(ahost_session* session) { return session->ingest.mapped_reads; }
+uint64_t ahost_viral_read_total(ahost_session* session) { uint64_t total = 0; for (size_t c = 0; c < session->ingest.mapped_viral_reads_by_contig.size(); ++c) total += session->ingest.mapped_viral_reads_by_contig[c]; return total; }
 uint64_t ahost_coverage_checksum(ahost_session* session) {
 	uint64_t hash = 1469598103934665603ull;
 	auto mix = [&hash](const uint8_t* bytes, size_t n) { for (size_t i = 0; i < n; ++i) hash = (hash ^ bytes[i]) * 1099511628211ull; };

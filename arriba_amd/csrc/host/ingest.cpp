@@ -20,6 +20,7 @@
 #include <stdexcept>
 #include <sched.h>
 #include <thread>
+#include <unordered_set>
 #include <zlib.h>
 #include <errno.h>
 #include <fcntl.h>
@@ -350,7 +351,9 @@ void get_boundaries_of_biggest_gene(const std::vector<uint32_t>& genes, const An
 }
 
 // reference: source/read_chimeric_alignments.cpp:93-193
-bool extract_read_through_alignment(fragment_table_t& fragments, const std::string& read_name, const Record* forward_mate, const Record* reverse_mate, const Annotation& annotation, const FlatIndex& gene_index) {
+// taken (pass R of -c): the names of the fragments of pass C -- chimeric_alignments holds them in the reference, and the insert of a name among them fails like any other
+bool extract_read_through_alignment(fragment_table_t& fragments, const std::string& read_name, const Record* forward_mate, const Record* reverse_mate, const Annotation& annotation, const FlatIndex& gene_index, const std::unordered_set<std::string>* taken = NULL) {
+	const bool name_taken = taken != NULL && taken->count(read_name) != 0;
 	if (!forward_mate->forward_strand())
 		std::swap(forward_mate, reverse_mate);
 	std::vector<uint32_t> forward_genes, reverse_genes, common_genes;
@@ -373,7 +376,7 @@ bool extract_read_through_alignment(fragment_table_t& fragments, const std::stri
 	bool forward_has_intron = (forward_mate == NULL) ? false : find_spanning_intron(*forward_mate, forward_gene_end, reverse_gene_start, forward_cigar_op, forward_read_pos);
 	bool reverse_has_intron = (reverse_mate == NULL) ? false : find_spanning_intron(*reverse_mate, forward_gene_end, reverse_gene_start, reverse_cigar_op, reverse_read_pos);
 	if (forward_has_intron && (!reverse_has_intron || forward_read_pos < reverse_mate->l_seq - reverse_read_pos)) {
-		std::pair<fragment_table_t::iterator, bool> mates = fragments.insert(std::make_pair(read_name, Fragment()));
+		std::pair<fragment_table_t::iterator, bool> mates = name_taken ? std::make_pair(fragments.end(), false) : fragments.insert(std::make_pair(read_name, Fragment()));
 		if (mates.second) {
 			add_chimeric_alignment(mates.first->second, *forward_mate, false, forward_cigar_op + 1, CLIP_START);
 			add_chimeric_alignment(mates.first->second, *forward_mate, true, forward_cigar_op - 1, CLIP_END);
@@ -384,7 +387,7 @@ bool extract_read_through_alignment(fragment_table_t& fragments, const std::stri
 			return true;
 		}
 	} else if (reverse_has_intron) {
-		std::pair<fragment_table_t::iterator, bool> mates = fragments.insert(std::make_pair(read_name, Fragment()));
+		std::pair<fragment_table_t::iterator, bool> mates = name_taken ? std::make_pair(fragments.end(), false) : fragments.insert(std::make_pair(read_name, Fragment()));
 		if (mates.second) {
 			add_chimeric_alignment(mates.first->second, *reverse_mate, true, reverse_cigar_op + 1, CLIP_START);
 			add_chimeric_alignment(mates.first->second, *reverse_mate, false, reverse_cigar_op - 1, CLIP_END);
@@ -395,7 +398,7 @@ bool extract_read_through_alignment(fragment_table_t& fragments, const std::stri
 			return true;
 		}
 	} else if (forward_mate != NULL && reverse_mate != NULL && reverse_mate->pos >= reverse_gene_start && forward_mate->endpos() <= forward_gene_end) {
-		std::pair<fragment_table_t::iterator, bool> mates = fragments.insert(std::make_pair(read_name, Fragment()));
+		std::pair<fragment_table_t::iterator, bool> mates = name_taken ? std::make_pair(fragments.end(), false) : fragments.insert(std::make_pair(read_name, Fragment()));
 		if (mates.second) {
 			add_chimeric_alignment(mates.first->second, *forward_mate);
 			add_chimeric_alignment(mates.first->second, *reverse_mate);
@@ -819,6 +822,8 @@ struct IngestShared {
 	const Assembly& assembly; const Annotation& annotation; const FlatIndex& gene_index; const IngestOptions& options;
 	std::vector<contig_t> tid_to_contig; std::vector<bool> interesting_tids, viral_contigs;
 	Coverage& coverage;
+	int role; // INGEST_ROLE_*: the two booleans of the reference's read_chimeric_alignments
+	const std::unordered_set<std::string>* taken; // pass R of -c: the names of the fragments pass C left
 };
 
 struct IngestWorker {
@@ -835,23 +840,55 @@ struct IngestWorker {
 
 	void process(Record& record) {
 		const IngestOptions& options = shared.options;
-		if ((record.flag & BAM_FUNMAP) || (record.flag & BAM_FPAIRED) && (record.flag & BAM_FMUNMAP))
-			return;
+		const int role = shared.role;
+		if (role != INGEST_ROLE_SEPARATE_CHIMERIC) // (is_rna_bam_file)
+			if ((record.flag & BAM_FUNMAP) || (record.flag & BAM_FPAIRED) && (record.flag & BAM_FMUNMAP))
+				return;
 		int64_t hit_index = 1;
-		const uint8_t* hi_tag = record.aux_get('H', 'I');
-		if (hi_tag != NULL) {
-			hit_index = Record::aux_to_int(hi_tag);
-		} else if (record.flag & BAM_FSECONDARY) {
-			missing_hi_tag++;
-			return;
+		if (role == INGEST_ROLE_WHOLE) { // (!separate_chimeric_bam_file: with -c both passes ignore HI, :618)
+			const uint8_t* hi_tag = record.aux_get('H', 'I');
+			if (hi_tag != NULL) {
+				hit_index = Record::aux_to_int(hi_tag);
+			} else if (record.flag & BAM_FSECONDARY) {
+				missing_hi_tag++;
+				return;
+			}
 		}
 		read_name = record.qname;
 		read_name += "," + std::to_string(hit_index);
 		if (record.tid < 0 || (size_t) record.tid >= shared.tid_to_contig.size())
-			throw std::runtime_error("failed to load alignments");
+			throw std::runtime_error(role == INGEST_ROLE_SEPARATE_CHIMERIC ? "failed to load alignments: a record of the separate chimeric file (-c) is damaged or has no reference sequence" : "failed to load alignments");
 		record.tid = shared.tid_to_contig[record.tid];
 
+		if (role == INGEST_ROLE_SEPARATE_CHIMERIC) { // Chimeric.out.sam: load everything (:634-638, :670-698); no coverage, no counters
+			if (record.flag & BAM_FSECONDARY) {
+				add_chimeric_alignment(fragments[read_name], record, true);
+				no_chimeric_reads = false;
+				return;
+			}
+			Record mate;
+			bool have_mate = false;
+			if (record.flag & BAM_FPAIRED) {
+				std::unordered_map<std::string, Record>::iterator parked = collated.find(read_name);
+				if (parked == collated.end()) {
+					collated.emplace(read_name, std::move(record));
+					return;
+				}
+				mate = std::move(parked->second);
+				have_mate = true;
+				collated.erase(parked);
+			}
+			Fragment& mates = fragments[read_name];
+			add_chimeric_alignment(mates, record);
+			if (have_mate)
+				add_chimeric_alignment(mates, mate);
+			no_chimeric_reads = false;
+			return;
+		}
+
 		if (record.flag & BAM_FSUPPLEMENTARY) {
+			if (role == INGEST_ROLE_SEPARATE_RNA)
+				return; // don't load alignments twice
 			if (is_clipped_at_correct_end(record))
 				add_chimeric_alignment(fragments[read_name], record, true);
 			else
@@ -862,8 +899,10 @@ struct IngestWorker {
 		if (shared.interesting_tids[record.tid])
 			mapped_reads++;
 		if ((record.flag & BAM_FPAIRED) && !(record.flag & BAM_FPROPER_PAIR)) {
-			add_chimeric_alignment(fragments[read_name], record);
-			no_chimeric_reads = false;
+			if (role != INGEST_ROLE_SEPARATE_RNA) {
+				add_chimeric_alignment(fragments[read_name], record);
+				no_chimeric_reads = false;
+			}
 			if (!options.external_duplicate_marking || !(record.flag & BAM_FDUP))
 				add_fragment_to_coverage(shared.coverage, record, 0 /* flag &= !BAM_FPAIRED zeroes the word */, NULL, true);
 			return;
@@ -899,13 +938,15 @@ struct IngestWorker {
 		bool is_read_through = false;
 		if (record.aux_get('S', 'A') != NULL && is_clipped_at_correct_end(record) ||
 		    previous_mate != NULL && previous_mate->aux_get('S', 'A') != NULL && is_clipped_at_correct_end(*previous_mate)) {
-			Fragment& mates = fragments[read_name];
-			add_chimeric_alignment(mates, record);
-			if (previous_mate != NULL)
-				add_chimeric_alignment(mates, *previous_mate);
-			no_chimeric_reads = false;
+			if (role != INGEST_ROLE_SEPARATE_RNA) {
+				Fragment& mates = fragments[read_name];
+				add_chimeric_alignment(mates, record);
+				if (previous_mate != NULL)
+					add_chimeric_alignment(mates, *previous_mate);
+				no_chimeric_reads = false;
+			}
 		} else if (!is_tandem_alignment) {
-			is_read_through = extract_read_through_alignment(fragments, read_name, &record, previous_mate, shared.annotation, shared.gene_index);
+			is_read_through = extract_read_through_alignment(fragments, read_name, &record, previous_mate, shared.annotation, shared.gene_index, shared.taken);
 			if (shared.viral_contigs[record.tid])
 				for (const Record* mate = &record; mate != NULL; mate = (mate == previous_mate) ? NULL : previous_mate)
 					if (is_pristine_alignment(*mate))
@@ -1115,18 +1156,68 @@ ByteSource* open_bam_file(const std::string& path) {
 }
 
 // reference: source/read_chimeric_alignments.cpp:560-773
-void read_chimeric_alignments(ByteSource& source, const Assembly& assembly, Contigs& contigs, const Annotation& annotation, const FlatIndex& gene_index, const IngestOptions& options, IngestResult& result) {
-	BamStream stream(source);
-	std::vector<std::string> target_names;
-	stream.read_header(target_names);
+namespace {
 
-	IngestShared shared = { assembly, annotation, gene_index, options, std::vector<contig_t>(target_names.size()), std::vector<bool>(target_names.size()), std::vector<bool>(), result.coverage };
+typedef std::pair<const std::string*, Fragment*> SortedEntry;
+
+// one call of the reference's read_chimeric_alignments up to the end of its record loop: the workers with their tables (the fragments normalised and sorted per worker) and its counters
+struct IngestPass {
+	std::vector<std::unique_ptr<IngestWorker> > workers;
+	std::unique_ptr<IngestShared> shared; // (the workers refer to it)
+	std::vector<std::string> target_names;
+	bool no_chimeric_reads = true;
+	uint64_t mapped_reads = 0, records = 0;
+	unsigned int malformed_count = 0, missing_hi_tag = 0;
+	size_t n_fragments = 0;
+	std::chrono::steady_clock::time_point started; // of the pass, for the laps of ARRIBA_INGEST_TIMING
+	void lap(const char* phase) const { if (getenv("ARRIBA_INGEST_TIMING") != NULL) std::cerr << "ingest: " << phase << " at " << std::chrono::duration<double>(std::chrono::steady_clock::now() - started).count() << " s" << std::endl; }
+};
+
+// the name-sorted lists of the workers of `passes` as one (names are unique across workers and, with -c, across the passes: whatever pass R adds is absent from pass C)
+void merge_sorted_lists(const std::vector<IngestPass*>& passes, std::vector<SortedEntry>& sorted) {
+	std::vector<std::vector<SortedEntry>*> lists;
+	size_t total = 0;
+	for (size_t p = 0; p < passes.size(); ++p)
+		for (size_t w = 0; w < passes[p]->workers.size(); ++w)
+			if (!passes[p]->workers[w]->sorted.empty()) { lists.push_back(&passes[p]->workers[w]->sorted); total += lists.back()->size(); }
+	if (lists.size() == 1) { sorted.swap(*lists[0]); return; }
+	sorted.reserve(total);
+	std::vector<size_t> cursor(lists.size(), 0);
+	auto later = [&lists, &cursor](unsigned int a, unsigned int b) { return *(*lists[b])[cursor[b]].first < *(*lists[a])[cursor[a]].first; };
+	std::vector<unsigned int> heap;
+	for (unsigned int l = 0; l < lists.size(); ++l) heap.push_back(l);
+	std::make_heap(heap.begin(), heap.end(), later);
+	while (!heap.empty()) {
+		std::pop_heap(heap.begin(), heap.end(), later);
+		const unsigned int l = heap.back();
+		sorted.push_back((*lists[l])[cursor[l]]);
+		if (++cursor[l] < lists[l]->size()) std::push_heap(heap.begin(), heap.end(), later);
+		else heap.pop_back();
+	}
+}
+
+void free_passes(const std::vector<IngestPass*>& passes) { // the tables are millions of heap nodes: every worker's table is freed by a thread of its own
+	std::vector<std::unique_ptr<IngestWorker>*> all;
+	for (size_t p = 0; p < passes.size(); ++p) for (size_t w = 0; w < passes[p]->workers.size(); ++w) all.push_back(&passes[p]->workers[w]);
+	parallel_ranges(all.size(), all.size() > 1 ? all.size() : 0, [&all](size_t first, size_t last) { for (size_t w = first; w < last; ++w) all[w]->reset(); }, 2);
+}
+
+void run_ingest_pass(ByteSource& source, const Assembly& assembly, Contigs& contigs, const Annotation& annotation, const FlatIndex& gene_index, const IngestOptions& options, IngestResult& result, int role,
+                     const std::unordered_set<std::string>* taken, const std::vector<std::string>* expected_targets, IngestPass& pass) {
+	BamStream stream(source);
+	std::vector<std::string>& target_names = pass.target_names;
+	stream.read_header(target_names);
+	if (expected_targets != NULL && *expected_targets != target_names)
+		throw std::runtime_error("the headers of the separate chimeric file (-c) and of the main alignments (-x) do not list the same reference sequences in the same order");
+
+	pass.shared.reset(new IngestShared{ assembly, annotation, gene_index, options, std::vector<contig_t>(target_names.size()), std::vector<bool>(target_names.size()), std::vector<bool>(), result.coverage, role, taken });
+	IngestShared& shared = *pass.shared;
 	for (size_t target = 0; target < target_names.size(); ++target) {
 		std::string contig_name = remove_chr(target_names[target]);
 		shared.tid_to_contig[target] = contigs.add(target_names[target]);
 		if (shared.tid_to_contig[target] >= shared.interesting_tids.size())
 			shared.interesting_tids.resize(shared.tid_to_contig[target] + 1);
-		shared.interesting_tids[shared.tid_to_contig[target]] = is_interesting_contig(contig_name, options.interesting_contigs);
+		shared.interesting_tids[shared.tid_to_contig[target]] = role != INGEST_ROLE_SEPARATE_CHIMERIC && is_interesting_contig(contig_name, options.interesting_contigs); // (all false in pass C: mapped_reads does not move)
 	}
 	result.coverage.resize(contigs, assembly);
 	for (std::map<std::string, contig_t>::const_iterator contig = contigs.by_name.begin(); contig != contigs.by_name.end(); ++contig)
@@ -1139,8 +1230,9 @@ void read_chimeric_alignments(ByteSource& source, const Assembly& assembly, Cont
 	const unsigned int n_workers = ingest_threads();
 	const bool timing = getenv("ARRIBA_INGEST_TIMING") != NULL;
 	const std::chrono::steady_clock::time_point started = std::chrono::steady_clock::now();
+	pass.started = started;
 	auto lap = [&started, timing](const char* phase) { if (timing) std::cerr << "ingest: " << phase << " at " << std::chrono::duration<double>(std::chrono::steady_clock::now() - started).count() << " s" << std::endl; };
-	std::vector<std::unique_ptr<IngestWorker> > workers;
+	std::vector<std::unique_ptr<IngestWorker> >& workers = pass.workers;
 	for (unsigned int w = 0; w < n_workers; ++w)
 		workers.push_back(std::unique_ptr<IngestWorker>(new IngestWorker(shared, contigs.size())));
 
@@ -1214,56 +1306,85 @@ void read_chimeric_alignments(ByteSource& source, const Assembly& assembly, Cont
 	}
 
 	lap("records classified, fragments normalised and sorted per worker");
-	bool no_chimeric_reads = true;
-	result.mapped_viral_reads_by_contig.assign(contigs.size(), 0);
-	size_t n_fragments = 0;
+	result.mapped_viral_reads_by_contig.resize(contigs.size(), 0);
 	for (unsigned int w = 0; w < n_workers; ++w) {
 		const IngestWorker& worker = *workers[w];
-		result.mapped_reads += worker.mapped_reads;
-		result.malformed_count += worker.malformed_count;
-		result.missing_hi_tag += worker.missing_hi_tag;
-		no_chimeric_reads = no_chimeric_reads && worker.no_chimeric_reads;
+		pass.mapped_reads += worker.mapped_reads;
+		pass.malformed_count += worker.malformed_count;
+		pass.missing_hi_tag += worker.missing_hi_tag;
+		pass.no_chimeric_reads = pass.no_chimeric_reads && worker.no_chimeric_reads;
 		for (size_t contig = 0; contig < worker.mapped_viral_reads_by_contig.size(); ++contig)
 			result.mapped_viral_reads_by_contig[contig] += worker.mapped_viral_reads_by_contig[contig];
-		n_fragments += worker.sorted.size();
+		pass.n_fragments += worker.sorted.size();
 	}
+}
+
+}
+
+namespace {
+const char* const NO_CHIMERIC_READS = "no split reads or discordant mates found (STAR must either be run with '--chimOutType WithinBAM' or the file 'Chimeric.out.sam' must be passed to Arriba via the argument -c)";
+void warn_malformed(unsigned int count) { if (count > 0) std::cerr << "WARNING: " << count << " SAM records were malformed and ignored" << std::endl; }
+}
+
+void read_chimeric_alignments(ByteSource& source, const Assembly& assembly, Contigs& contigs, const Annotation& annotation, const FlatIndex& gene_index, const IngestOptions& options, IngestResult& result) {
+	IngestPass pass;
+	run_ingest_pass(source, assembly, contigs, annotation, gene_index, options, result, INGEST_ROLE_WHOLE, NULL, NULL, pass);
+	result.mapped_reads += pass.mapped_reads; result.malformed_count += pass.malformed_count; result.missing_hi_tag += pass.missing_hi_tag;
 	if (result.mapped_reads == 0)
 		throw std::runtime_error("no normal reads found");
-	if (result.malformed_count > 0)
-		std::cerr << "WARNING: " << result.malformed_count << " SAM records were malformed and ignored" << std::endl;
-	if (no_chimeric_reads)
-		throw std::runtime_error("no split reads or discordant mates found (STAR must either be run with '--chimOutType WithinBAM' or the file 'Chimeric.out.sam' must be passed to Arriba via the argument -c)");
+	warn_malformed(result.malformed_count);
+	if (pass.no_chimeric_reads)
+		throw std::runtime_error(NO_CHIMERIC_READS);
 	if (result.missing_hi_tag > 0)
 		std::cerr << "WARNING: " << result.missing_hi_tag << " secondary alignments lack the 'HI' tag and were ignored (STAR must be run with '--outSAMattributes HI' for Arriba to make use of multi-mapping reads for fusion detection)" << std::endl;
+	std::vector<IngestPass*> passes(1, &pass);
+	std::vector<SortedEntry> sorted;
+	merge_sorted_lists(passes, sorted);
+	pass.lap("lists merged");
+	pack_batch(sorted, result.batch, pass.workers.size());
+	pass.lap("batch packed");
+	free_passes(passes);
+	pass.lap("tables freed");
+}
 
-	// merge of the workers' name-sorted lists (names are unique across workers)
-	std::vector<std::pair<const std::string*, Fragment*> > sorted;
-	sorted.reserve(n_fragments);
-	if (n_workers == 1) {
-		sorted.swap(workers[0]->sorted);
-	} else {
-		typedef std::pair<const std::string*, Fragment*> Entry;
-		std::vector<size_t> cursor(n_workers, 0);
-		auto later = [&workers, &cursor](unsigned int a, unsigned int b) { return *workers[b]->sorted[cursor[b]].first < *workers[a]->sorted[cursor[a]].first; };
-		std::vector<unsigned int> heap;
-		for (unsigned int w = 0; w < n_workers; ++w)
-			if (!workers[w]->sorted.empty()) heap.push_back(w);
-		std::make_heap(heap.begin(), heap.end(), later);
-		while (!heap.empty()) {
-			std::pop_heap(heap.begin(), heap.end(), later);
-			const unsigned int w = heap.back();
-			const Entry& entry = workers[w]->sorted[cursor[w]];
-			sorted.push_back(entry);
-			if (++cursor[w] < workers[w]->sorted.size()) std::push_heap(heap.begin(), heap.end(), later);
-			else heap.pop_back();
+// reference: source/arriba.cpp:123-130 -- read_chimeric_alignments twice over one table of fragments: Chimeric.out.sam (pass C), then the main alignments (pass R)
+void read_chimeric_alignments_separate(ByteSource& chimeric_source, ByteSource& rna_source, const Assembly& assembly, Contigs& contigs, const Annotation& annotation, const FlatIndex& gene_index, const IngestOptions& options, IngestResult& result) {
+	IngestPass chimeric, rna;
+	run_ingest_pass(chimeric_source, assembly, contigs, annotation, gene_index, options, result, INGEST_ROLE_SEPARATE_CHIMERIC, NULL, NULL, chimeric);
+	result.separate_malformed_count = chimeric.malformed_count; result.separate_fragments = chimeric.n_fragments;
+	warn_malformed(chimeric.malformed_count);
+	if (chimeric.no_chimeric_reads)
+		throw std::runtime_error(NO_CHIMERIC_READS);
+	std::unordered_set<std::string> taken; // what pass R finds in chimeric_alignments: the fragments that passed the sanity check of pass C
+	taken.reserve(chimeric.n_fragments);
+	for (size_t w = 0; w < chimeric.workers.size(); ++w)
+		for (size_t k = 0; k < chimeric.workers[w]->sorted.size(); ++k) taken.insert(*chimeric.workers[w]->sorted[k].first);
+	run_ingest_pass(rna_source, assembly, contigs, annotation, gene_index, options, result, INGEST_ROLE_SEPARATE_RNA, &taken, &chimeric.target_names, rna);
+	result.mapped_reads += rna.mapped_reads; result.missing_hi_tag += rna.missing_hi_tag;
+	if (result.mapped_reads == 0)
+		throw std::runtime_error("no normal reads found");
+	// remove_malformed_alignments runs over everything: the fragments of pass C a second time (those of pass R were checked by their workers)
+	unsigned int malformed_again = 0;
+	for (size_t w = 0; w < chimeric.workers.size(); ++w) {
+		std::vector<SortedEntry>& list = chimeric.workers[w]->sorted;
+		size_t kept = 0;
+		for (size_t k = 0; k < list.size(); ++k) {
+			const Fragment& f = *list[k].second; // (behind the first run SPLIT_READ and SUPPLEMENTARY agree on first-in-pair unless both mates carry the same flag: the reference would swap the mates once more -- a deliberate limit, as on the device)
+			if (!f.single_end && f.alignments.size() == 3 && f.alignments[SPLIT_READ].first_in_pair != f.alignments[SUPPLEMENTARY].first_in_pair)
+				throw std::runtime_error("a paired split read of the separate chimeric file (-c) has two mates with the same first-in-pair flag: not supported");
+			if (normalize_fragment(*list[k].second)) list[kept++] = list[k];
+			else malformed_again++;
 		}
+		list.resize(kept);
 	}
-	lap("lists merged");
-	pack_batch(sorted, result.batch, n_workers);
-	lap("batch packed");
-	// the tables are millions of heap nodes: every worker's table is freed by a thread of its own
-	parallel_ranges(n_workers, n_workers > 1 ? n_workers : 0, [&workers](size_t first, size_t last) { for (size_t w = first; w < last; ++w) workers[w].reset(); }, 2);
-	lap("tables freed");
+	result.malformed_count = rna.malformed_count + malformed_again;
+	warn_malformed(result.malformed_count);
+	std::vector<IngestPass*> passes;
+	passes.push_back(&chimeric); passes.push_back(&rna);
+	std::vector<SortedEntry> sorted;
+	merge_sorted_lists(passes, sorted);
+	pack_batch(sorted, result.batch, std::max(chimeric.workers.size(), rna.workers.size()));
+	free_passes(passes);
 }
 
 

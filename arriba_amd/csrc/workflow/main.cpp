@@ -1,7 +1,8 @@
 // arriba_amd/csrc/workflow/main.cpp -- the command line of the reference (source/options.cpp:270-481: flags, defaults, checks and messages) in front of
 // arriba_workflow_run, so that run_arriba.sh can call this binary where it calls `arriba` (run_arriba.sh:42: STAR ... | arriba -x /dev/stdin -o ... -O ...).
 // Exit code 0 on success, 1 on any error ("ERROR: ..." on stderr, as crash() does in the reference).  -x takes what sam_open takes but CRAM: BAM or SAM text (told by the
-// content, never by the name: a file, a pipe, /dev/stdin or -; plain, gzip or BGZF).  Not supported and said so: -c (separate chimeric SAM file of old STAR versions),
+// content, never by the name: a file, a pipe, /dev/stdin or -; plain, gzip or BGZF).  -c (the separate chimeric file of STAR --chimOutType SeparateSAMold) takes the same; it
+// excludes the side outputs (--sorted-bam ... --rna-metrics), which read the records of one file.  Not supported and said so:
 // CRAM input (`samtools view -h x.cram | arriba_gpu_workflow -x /dev/stdin ...` reads one), -@ (the threads of the BAM decompression are chosen by the ingest).
 // The form `arriba_gpu_workflow assembly.fa annotation.gtf chimeric.bam fusions.tsv [discarded.tsv [...]]` of round 1 (no dash in front of the first
 // argument) is still understood.
@@ -52,6 +53,10 @@ void usage() {
 	             "Usage: arriba_gpu_workflow -x Aligned.out.bam -g annotation.gtf -a assembly.fa -o fusions.tsv [-b blacklists.tsv] [-k known_fusions.tsv] [-t tags.tsv] [-p protein_domains.gff3]\n"
 	             "                           [-d structural_variants.tsv] [-O fusions.discarded.tsv] [OPTIONS]\n\n"
 	             " -x FILE  main alignments of STAR run with --chimOutType WithinBAM: BAM or SAM text, told by content (BGZF, gzip or uncompressed; a file, a pipe, /dev/stdin or -)\n"
+	             " -c FILE  chimeric alignments of STAR run with --chimOutType SeparateSAMold (Chimeric.out.sam): read in front of -x, which then adds read-throughs and tandem duplications only;\n"
+	             "          takes what -x takes.  The headers of -c and -x must list the same references in the same order, every record of -c needs a reference, the mates of\n"
+	             "          a split read of -c different first-in-pair flags; not together with\n"
+	             "          --sorted-bam, --supporting-alignments, --virus-expression, --coverage, --gene-counts, --splice-junctions, --allele-counts, --realign-reads, --rna-metrics\n"
 	             " -g FILE  gene annotation (GTF)        -a FILE  assembly (FastA)          -o FILE  output file             -O FILE  discarded fusions\n"
 	             " -b FILE  blacklist                    -k FILE  known fusions             -t FILE  tags                    -p FILE  protein domains (GFF3)\n"
 	             " -d FILE  structural variants from WGS -D INT   max. distance to them (100000)\n"
@@ -146,7 +151,11 @@ int main(int argc, char** argv) {
 		if (c != '?') { require(!seen[(unsigned char) c], std::string("option -") + (char) c + " specified too often"); seen[(unsigned char) c] = true; }
 		uint32_t number = 0;
 		switch (c) {
-			case 'c': crash("option -c (chimeric alignments in a separate SAM file, STAR < 2.5.3a) is not supported: run STAR with --chimOutType WithinBAM and pass the main BAM file with -x");
+			case 'c': {
+				const std::string path(optarg);
+				require(!(path.size() >= 5 && path.substr(path.size() - 5) == ".cram"), "BAM and SAM text input are supported, CRAM is not (pipe it through `samtools view -h`): " + path);
+				options.separate_chimeric_file = optarg; readable(optarg); break;
+			}
 			case 'x': {
 				const std::string path(optarg);
 				require(!(path.size() >= 5 && path.substr(path.size() - 5) == ".cram"), "BAM and SAM text input are supported, CRAM is not (pipe it through `samtools view -h`): " + path);

@@ -25,6 +25,8 @@
 // transcoder's kernels, links all the same, and says so if it is given SAM text.  The product links libarriba_gpu.so, which has them.
 extern "C" int agpu_ingest_sam_targets(agpu_ctx* ctx, const char* names, const uint32_t* name_offset, uint32_t n_targets) __attribute__((weak));
 extern "C" int agpu_ingest_push_sam(agpu_ctx* ctx, const void* text, size_t size, uint64_t first_line_number) __attribute__((weak));
+extern "C" int agpu_separate_adopt(agpu_ctx* ctx) __attribute__((weak));
+extern "C" int agpu_separate_merge(agpu_ctx* ctx, agpu_ingest_result* result) __attribute__((weak));
 // ... and so are the four calls of --sorted-bam
 extern "C" int agpu_sorted_bam_begin(agpu_ctx* ctx, agpu_sorted_bam_info* info) __attribute__((weak));
 extern "C" int agpu_sorted_bam_next(agpu_ctx* ctx, void* pinned, uint64_t capacity, uint64_t* bytes) __attribute__((weak));
@@ -172,6 +174,7 @@ struct Run {
 		if (device) agpu_destroy(device); if (host) ahost_close(host);
 	}
 	Run(const Run&) = delete; Run& operator=(const Run&) = delete;
+	uint64_t separate_fragments = 0; std::string separate_chimeric_path; // -c: the "(total=N)" of the separate chimeric file; its path where the session owns it (arriba_workflow_sample_separate)
 	void note(const char* stage, uint64_t count) {
 		progress(stage, count);
 		if (!report || report->n_stages >= sizeof(report->stages) / sizeof(report->stages[0])) return;
@@ -313,10 +316,45 @@ bool check_rna_metrics(const Run& run) {
 	return true;
 }
 
+// -c (separate_chimeric_file): what is refused with it, before any input is read -- the side outputs read the resident stream of ONE file, the parts of a sample are cut from one file
+void check_separate_chimeric(const arriba_workflow_options& o, bool over_ranks) {
+	if (o.separate_chimeric_file == nullptr) return;
+	const std::string path(o.separate_chimeric_file);
+	if (path.size() >= 5 && path.substr(path.size() - 5) == ".cram") throw Failure{ "ERROR: BAM and SAM text input are supported, CRAM is not (pipe it through `samtools view -h`): " + path };
+	if (over_ranks) throw Failure{ "ERROR: -c (separate chimeric alignments) of one sample over several ranks is not supported" };
+	const struct { const char* value; const char* name; } excluded[] = { { o.sorted_bam_file, "--sorted-bam" }, { o.supporting_alignments_prefix, "--supporting-alignments" }, { o.virus_expression_file, "--virus-expression" },
+		{ o.coverage_file, "--coverage" }, { o.gene_counts_file, "--gene-counts" }, { o.splice_junctions_file, "--splice-junctions" }, { o.allele_counts_file, "--allele-counts" }, { o.realign_reads_file, "--realign-reads" },
+		{ o.rna_metrics_file, "--rna-metrics" } };
+	for (size_t k = 0; k < sizeof(excluded) / sizeof(excluded[0]); ++k)
+		if (excluded[k].value != nullptr) throw Failure{ std::string("ERROR: -c (separate chimeric alignments) and ") + excluded[k].name + " exclude each other: " + excluded[k].name + " reads the records of one file, the alignments of the sample are in two" };
+}
+
+void feed_one_file(Run& run, const char* path, int role);
+
+// -c on the device: pass C (the separate chimeric file) from its first byte to its batch, set aside on the device; then the main alignments are fed as pass R
 void feed_file(Run& run) {
 	const arriba_workflow_options& o = run.options;
+	check_separate_chimeric(o, run.ranks != nullptr);
+	if (o.separate_chimeric_file == nullptr) { feed_one_file(run, o.chimeric_bam_file, AGPU_ROLE_WHOLE); return; }
+	if (!agpu_separate_adopt || !agpu_separate_merge) throw Failure{ "ERROR: option -c (separate chimeric alignments) needs the device library (agpu_separate_adopt), which this build is not linked with" };
+	feed_one_file(run, o.separate_chimeric_file, AGPU_ROLE_SEPARATE_CHIMERIC);
+	{
+		struct Closer { Run& run; ~Closer() { if (run.bam_open) { ahost_bam_close(run.host); run.bam_open = false; } } } closer = { run };
+		agpu_ingest_result result;
+		device_check(agpu_ingest_finish(run.device, &result));
+		// reference: source/read_chimeric_alignments.cpp:761-767 of the first call
+		if (result.malformed_count > 0) std::cerr << "WARNING: " << result.malformed_count << " SAM records were malformed and ignored" << std::endl;
+		if (result.no_chimeric_reads) throw Failure{ "ERROR: no split reads or discordant mates found (STAR must either be run with '--chimOutType WithinBAM' or the file 'Chimeric.out.sam' must be passed to Arriba via the argument -c)" };
+		run.separate_fragments = result.fragments;
+		device_check(agpu_separate_adopt(run.device));
+	}
+	feed_one_file(run, o.chimeric_bam_file, AGPU_ROLE_SEPARATE_RNA);
+}
+
+void feed_one_file(Run& run, const char* path, int role) {
+	const arriba_workflow_options& o = run.options;
 	const double started = now_seconds();
-	run.feed_started = started;
+	if (role != AGPU_ROLE_SEPARATE_RNA) run.feed_started = started;
 	check_mark_duplicates(o);
 	if (o.mark_duplicates && (!agpu_sorted_bam_set_mark_duplicates || !agpu_markdup_stats)) throw Failure{ "ERROR: --mark-duplicates needs the device library (agpu_sorted_bam_set_mark_duplicates), which this build is not linked with" }; // (before the feed, not behind it)
 	if (run.ranks != nullptr && o.sorted_bam_file != nullptr) throw Failure{ "ERROR: a sorted BAM file of one sample over several GPUs is not supported" };
@@ -341,8 +379,9 @@ void feed_file(Run& run) {
 		host_check(ahost_region_track(run.host, o.rrna_intervals_file, &track, nullptr)); // (an interval file that does not parse is refused here; the track of the session is built once and kept)
 	}
 	agpu_ingest_config config;
-	if (run.ranks != nullptr) host_check(ahost_bam_open_part(run.host, o.chimeric_bam_file, o.device.external_duplicate_marking, o.device.max_itd_length, run.ranks->rank, run.ranks->size, &config)); // this rank's part of the records
-	else host_check(ahost_bam_open(run.host, o.chimeric_bam_file, o.device.external_duplicate_marking, o.device.max_itd_length, &config));
+	if (run.ranks != nullptr) host_check(ahost_bam_open_part(run.host, path, o.device.external_duplicate_marking, o.device.max_itd_length, run.ranks->rank, run.ranks->size, &config)); // this rank's part of the records
+	else if (role != AGPU_ROLE_WHOLE) host_check(ahost_bam_open_role(run.host, path, o.device.external_duplicate_marking, o.device.max_itd_length, role, &config));
+	else host_check(ahost_bam_open(run.host, path, o.device.external_duplicate_marking, o.device.max_itd_length, &config));
 	run.bam_open = true;
 	struct Closer { Run& run; bool armed; ~Closer() { if (armed && run.bam_open) { ahost_bam_close(run.host); run.bam_open = false; } } } closer = { run, true }; // (on every way out but the last line)
 	run.coverage_windows = config.n_contigs ? config.coverage_window_offset[config.n_contigs] : 0; // (the table belongs to the session: read before anything else touches it)
@@ -865,6 +904,7 @@ void finish_device_ingest(Run& run, double waited_since) {
 	const double fed = now_seconds();
 	agpu_ingest_result result;
 	together(run.ranks, [&] { device_check(agpu_ingest_finish(run.device, &result)); });
+	if (run.options.separate_chimeric_file != nullptr) device_check(agpu_separate_merge(run.device, &result)); // -c: the batch of the separate chimeric file and this one as one
 	run.sorted_bam_seconds = 0;
 	if (run.options.sorted_bam_file != nullptr) write_sorted_bam(run); // (before after_ingest: in a session of two lanes the stream belongs to the next feed after that)
 	run.virus_expression_seconds = 0;
@@ -1484,9 +1524,11 @@ void run_sample(Run& run, bool already_fed, double sample_started) {
 		if (run.ranks != nullptr) throw Failure{ "ERROR: one sample over several ranks needs read_chimeric_alignments on the device (host_ingest = 0): the parts of the batch are exchanged in device format" };
 		check_mark_duplicates(o);
 		if (check_allele_counts(run)) { ahost_allele_sites checked; host_check(ahost_allele_sites_load(o.allele_sites_file, nullptr, 0, &checked)); ahost_allele_sites_free(&checked); } // (refused before the input is read)
+		check_separate_chimeric(o, run.ranks != nullptr);
 		const bool realign = check_realign(run); // (refused before the input is read)
 		if (check_rna_metrics(run)) { agpu_region_track track; host_check(ahost_region_track(run.host, o.rrna_intervals_file, &track, nullptr)); } // (likewise)
-		host_check(ahost_ingest_bam_file(run.host, o.chimeric_bam_file, o.device.external_duplicate_marking, o.device.max_itd_length));
+		if (o.separate_chimeric_file != nullptr) host_check(ahost_ingest_separate(run.host, o.separate_chimeric_file, o.chimeric_bam_file, o.device.external_duplicate_marking, o.device.max_itd_length, &run.separate_fragments, nullptr));
+		else host_check(ahost_ingest_bam_file(run.host, o.chimeric_bam_file, o.device.external_duplicate_marking, o.device.max_itd_length));
 		if (o.sorted_bam_file != nullptr) { // (the host's stepping of the same code)
 			const double before = now_seconds();
 			agpu_markdup_counts counts;
@@ -1538,6 +1580,7 @@ void run_sample(Run& run, bool already_fed, double sample_started) {
 	}
 	run.mapped_reads = ahost_mapped_reads(run.host);
 	run.note("read_chimeric_alignments", run.n_fragments); // (the log line follows; `note` prints the lines of the stages behind it)
+	if (o.log_to_stdout && o.separate_chimeric_file != nullptr) std::cout << Run::time_string() << " Reading chimeric alignments from '" << o.separate_chimeric_file << "' (total=" << run.separate_fragments << ")" << std::endl; // (source/arriba.cpp:124-125)
 	if (o.log_to_stdout) std::cout << Run::time_string() << " Reading chimeric alignments from '" << o.chimeric_bam_file << "' (total=" << run.n_fragments << ")" << std::endl;
 	const double stages_started = now_seconds();
 	double mismappers_seconds = 0;
@@ -1698,6 +1741,7 @@ int arriba_workflow_run(const arriba_workflow_options* options, arriba_workflow_
 	if (report) report->n_stages = 0;
 	try {
 		if (!options->assembly_file || !options->gene_annotation_file || !options->chimeric_bam_file || !options->output_file) throw Failure{ "ERROR: assembly, gene annotation, alignments and output file are required" };
+		check_separate_chimeric(*options, false); // (what -c excludes is refused before anything is loaded)
 		Run run(*options);
 		run.report = report;
 		open_session(run);
@@ -2012,6 +2056,19 @@ int arriba_workflow_defer_output(arriba_workflow_session* session, int on) {
 	session->defer_output = on != 0;
 	return 0;
 }
+// -c through a resident session: one sample whose chimeric alignments come in a file of their own.  The two files go through the ingest one after the other on one lane, so
+// nothing may be submitted ahead and the ingest is not finished ahead.
+int arriba_workflow_sample_separate(arriba_workflow_session* session, const char* separate_chimeric_file, const char* chimeric_bam_file, const char* output_file, const char* discarded_output_file, arriba_workflow_report* report, arriba_workflow_timing* timing) {
+	if (!session || !separate_chimeric_file || !chimeric_bam_file) { g_error = "ERROR: null argument"; return -1; }
+	if (!session->queue.empty()) { g_error = "ERROR: arriba_workflow_sample_separate: samples are submitted already (-c and arriba_workflow_submit exclude each other)"; return -1; }
+	if (session->finish_ahead) { g_error = "ERROR: arriba_workflow_sample_separate: -c and arriba_workflow_finish_ahead exclude each other"; return -1; }
+	if (session->over_ranks) { g_error = "ERROR: -c (separate chimeric alignments) of one sample over several ranks is not supported"; return -1; }
+	for (int lane = 0; lane < 2; ++lane) if (session->lanes[lane]) { session->lanes[lane]->separate_chimeric_path = separate_chimeric_file; session->lanes[lane]->options.separate_chimeric_file = session->lanes[lane]->separate_chimeric_path.c_str(); }
+	const int status = arriba_workflow_sample(session, chimeric_bam_file, output_file, discarded_output_file, report, timing);
+	for (int lane = 0; lane < 2; ++lane) if (session->lanes[lane]) session->lanes[lane]->options.separate_chimeric_file = nullptr;
+	return status;
+}
+
 int arriba_workflow_finish_ahead(arriba_workflow_session* session, int on) {
 	if (!session) { g_error = "ERROR: null argument"; return -1; }
 	if (!session->queue.empty()) { g_error = "ERROR: arriba_workflow_finish_ahead: samples are submitted already"; return -1; }

@@ -111,9 +111,15 @@ class HostSession(object):
         except Exception:
             pass
 
-    def read_chimeric_alignments(self, bam, external_duplicate_marking=False, max_itd_length=100):
-        """bam: path to a BAM file, or a bytes-like object / numpy uint8 array holding the raw (inflated) BAM stream."""
-        if isinstance(bam, str):
+    def read_chimeric_alignments(self, bam, external_duplicate_marking=False, max_itd_length=100, separate_chimeric=None):
+        """bam: path to a BAM file, or a bytes-like object / numpy uint8 array holding the raw (inflated) BAM stream.
+        separate_chimeric (-c): path of the separate chimeric file of STAR --chimOutType SeparateSAMold, read in front of `bam` (a path, too) as source/arriba.cpp:123-130 does;
+        self.separate_counts then holds the (total=N) and the malformed count of that first pass."""
+        if separate_chimeric is not None:
+            fragments, malformed = ctypes.c_uint64(0), ctypes.c_uint64(0)
+            status = self._lib.ahost_ingest_separate(self._session, separate_chimeric.encode(), bam.encode(), int(external_duplicate_marking), max_itd_length, byref(fragments), byref(malformed))
+            self.separate_counts = (fragments.value, malformed.value)
+        elif isinstance(bam, str):
             status = self._lib.ahost_ingest_bam_file(self._session, bam.encode(), int(external_duplicate_marking), max_itd_length)
         else:
             array = np.frombuffer(bam, dtype=np.uint8) if not isinstance(bam, np.ndarray) else bam
@@ -150,6 +156,11 @@ class HostSession(object):
     @property
     def mapped_reads(self):
         return int(self._lib.ahost_mapped_reads(self._session))
+
+    @property
+    def viral_read_total(self):
+        """the pristine reads the ingest counted on viral contigs, over all of them"""
+        return int(self._lib.ahost_viral_read_total(self._session))
 
     @property
     def annotation_view(self):
@@ -379,6 +390,17 @@ class WorkflowSession(object):
         self.report = [(report.stages[k].stage.decode(), int(report.stages[k].count)) for k in range(report.n_stages)]
         return self.report
 
+    def sample_separate(self, separate_chimeric, bam, output_file, discarded_output_file=None):
+        """-c through the session (arriba_workflow_sample_separate): the chimeric alignments of the sample come in `separate_chimeric`, read in front of `bam`.  Refused with samples
+        submitted ahead and with finish_ahead on; the next `sample` is an ordinary one again."""
+        report, timing = _capi.WorkflowReport(), _capi.WorkflowTiming()
+        if self._lib.arriba_workflow_sample_separate(self._session, separate_chimeric.encode(), bam.encode(), output_file.encode(), discarded_output_file.encode() if discarded_output_file else None, byref(report), byref(timing)) != 0:
+            raise ArribaError(self._lib.arriba_workflow_last_error().decode())
+        self.ctx = self._lib.arriba_workflow_device(self._session)
+        self.timing = {name: getattr(timing, name) for name, _ in _capi.WorkflowTiming._fields_}
+        self.report = [(report.stages[k].stage.decode(), int(report.stages[k].count)) for k in range(report.n_stages)]
+        return self.report
+
     def set_profiling(self, enabled, only_new_lanes=False):
         for ctx in self._lane_contexts():
             if only_new_lanes and ctx in self._profiled:
@@ -430,7 +452,7 @@ class DevicePipeline(object):
     stepping harness of tests/emu instead.
     """
 
-    def __init__(self, session, params=None, api=None, device=0, batch_view=None, bam=None, external_duplicate_marking=False, max_itd_length=100, piece_bytes=64 << 20, profiling=False):
+    def __init__(self, session, params=None, api=None, device=0, batch_view=None, bam=None, external_duplicate_marking=False, max_itd_length=100, piece_bytes=64 << 20, profiling=False, separate_chimeric=None):
         """bam: path of the BAM file -> read_chimeric_alignments runs on the device (agpu_ingest_*): the host session only opens the file, parses the
         header and feeds the bytes; the batch never exists on the host.  Without it the batch of the session's host ingest is uploaded."""
         self.session = session
@@ -457,7 +479,9 @@ class DevicePipeline(object):
         self.ingest_result = None
         if profiling:
             self.set_profiling(True)  # before the ingest: its kernels are part of the profile
-        if self.device_ingest:
+        if self.device_ingest and separate_chimeric is not None:  # -c: the chimeric alignments in a file of their own, read in front of `bam`
+            self.read_chimeric_alignments_separate(separate_chimeric, bam, external_duplicate_marking, max_itd_length, piece_bytes)
+        elif self.device_ingest:
             self.read_chimeric_alignments(bam, external_duplicate_marking, max_itd_length, piece_bytes)
         else:
             self._check(self.api.upload_genome(self.ctx, session.genome_view))
@@ -493,13 +517,28 @@ class DevicePipeline(object):
         self.ingest_seconds = {"feed": fed - started, "device": finished - fed, "adopt": time.perf_counter() - finished}
         return self.n
 
-    def _ingest_records(self, bam, external_duplicate_marking, max_itd_length, piece_bytes, part=None, parts=None):
+    def read_chimeric_alignments_separate(self, separate_chimeric, bam, external_duplicate_marking=False, max_itd_length=100, piece_bytes=64 << 20):
+        """-c on the device (source/arriba.cpp:123-130): the separate chimeric file through the ingest as pass C, its batch set aside (agpu_separate_adopt), the main alignments as pass R,
+        both batches as one (agpu_separate_merge).  self.separate_result: what pass C reported -- fragments = its (total=N), malformed_count = its WARNING."""
+        _, self.separate_result, _ = self._ingest_records(separate_chimeric, external_duplicate_marking, max_itd_length, piece_bytes, role=_capi.ROLE_SEPARATE_CHIMERIC)
+        if self.separate_result.no_chimeric_reads:
+            raise ArribaError("ERROR: no split reads or discordant mates found (STAR must either be run with '--chimOutType WithinBAM' or the file 'Chimeric.out.sam' must be passed to Arriba via the argument -c)")
+        self._check(self.api.separate_adopt(self.ctx))
+        config, result, _ = self._ingest_records(bam, external_duplicate_marking, max_itd_length, piece_bytes, role=_capi.ROLE_SEPARATE_RNA)
+        self._check(self.api.separate_merge(self.ctx, byref(result)))
+        self._record("read_chimeric_alignments")
+        self._adopt_ingest(config, result)
+        return self.n
+
+    def _ingest_records(self, bam, external_duplicate_marking, max_itd_length, piece_bytes, part=None, parts=None, role=0):
         """opens the file (or part `part` of `parts` of its records), feeds the pieces, runs agpu_ingest_finish; returns (config, result, time the last piece was fed)"""
         import time
         lib, handle = self.session._lib, self.session._session
         host_error = lambda: ArribaError("ERROR: " + lib.ahost_last_error().decode())
         config = _capi.IngestConfig()
-        if part is None:
+        if role != 0:
+            status = lib.ahost_bam_open_role(handle, bam.encode(), int(external_duplicate_marking), max_itd_length, role, byref(config))
+        elif part is None:
             status = lib.ahost_bam_open(handle, bam.encode(), int(external_duplicate_marking), max_itd_length, byref(config))
         else:
             status = lib.ahost_bam_open_part(handle, bam.encode(), int(external_duplicate_marking), max_itd_length, part, parts, byref(config))

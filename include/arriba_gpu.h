@@ -213,7 +213,23 @@ typedef struct {
 	uint32_t max_itd_length;                /* -l */
 	uint8_t part_of_sample;                 /* the stream holds a part of the sample's records, other contexts hold the rest: agpu_shard_export / agpu_shard_merge follow */
 	uint8_t host_buffers;                   /* buffers the caller pushes from in turn: 0 or 2 = two (see above) */
+	uint8_t role;                           /* AGPU_ROLE_*: what the stream is to the loop of the reference; 0 = the one file of STAR --chimOutType WithinBAM (see "-c" below) */
 } agpu_ingest_config;
+/* -c: the chimeric alignments of STAR --chimOutType SeparateSAMold come in a file of their own (Chimeric.out.sam), and read_chimeric_alignments runs twice over one table of
+ * fragments (source/arriba.cpp:123-130): pass C over that file (separate_chimeric_bam_file, !is_rna_bam_file), pass R over the main alignments (both true).
+ *   agpu_ingest_begin / push / finish   with role = AGPU_ROLE_SEPARATE_CHIMERIC: pass C.  Both passes are done behind the last piece (as a part of a sample is), so only one stream
+ *                                       is ever resident.  A record without a reference makes agpu_ingest_finish fail ("failed to load alignments").
+ *   agpu_separate_adopt                 behind the finish of pass C: its batch is set aside on the device (the block agpu_shard_export makes of it) together with the sorted
+ *                                       name keys of its fragments; the stream is free for pass R.
+ *   agpu_ingest_begin / push / finish   with role = AGPU_ROLE_SEPARATE_RNA: pass R.  A read-through whose name is a fragment of pass C is not inserted (key look-up by binary
+ *                                       search, confirmed on the bytes of the name).
+ *   agpu_separate_merge                 both batches as one, in name order, with the read-name groups numbered again (one QNAME may be in both: "X,1" of pass C, "X,1ITD" of
+ *                                       pass R); coverage_t, mapped reads and viral counts are those of pass R.  The second run of remove_malformed_alignments over the fragments
+ *                                       of pass C is replayed: it removes the single-end ones (their three alignments fail its size test) and counts them; a paired fragment that
+ *                                       passed once passes again unchanged.  result: records of both streams, everything else as the reference's second call
+ *                                       has it (malformed_count without that of pass C, no_chimeric_reads = 0: that check belongs to pass C).
+ * AGPU_ERR_INVALID when the calls come in another order, or when the two passes saw different windows of coverage_t. */
+enum { AGPU_ROLE_WHOLE = 0, AGPU_ROLE_SEPARATE_CHIMERIC = 1, AGPU_ROLE_SEPARATE_RNA = 2 };
 /* A BGZF block of a pushed piece (offsets inside the piece / inside the piece's part of the stream).  isize == 0: a stored block -- payload_offset / payload_size are its data
  * as they are (already cut to the records of a part of the file where the block is the first or last of a part), crc32 the CRC-32 of the whole data, 0 = not to be checked.
  * isize != 0: a deflated block -- payload_offset / payload_size are its DEFLATE stream, isize what it inflates to (the ISIZE of the gzip trailer), and of that the bytes
@@ -242,6 +258,8 @@ int agpu_ingest_begin(agpu_ctx* ctx, const agpu_ingest_config* config);
 int agpu_ingest_push(agpu_ctx* ctx, const void* bytes, size_t size);
 int agpu_ingest_push_bgzf(agpu_ctx* ctx, const void* raw, size_t raw_size, const agpu_bgzf_block* blocks, uint32_t n_blocks, size_t stream_bytes);
 int agpu_ingest_finish(agpu_ctx* ctx, agpu_ingest_result* result);
+int agpu_separate_adopt(agpu_ctx* ctx);
+int agpu_separate_merge(agpu_ctx* ctx, agpu_ingest_result* result);
 /* SAM text instead of BAM (sam_open reads both: source/read_chimeric_alignments.cpp:563): the lines are turned into the BAM records `samtools view -b` writes for them
  * (SAMv1 section 4.2) on the device, in front of the ingest above (arriba_amd/csrc/device/agpu_sam.hip, sam_core.hpp), and appended to the stream; the stream holds records
  * only (agpu_ingest_config.first_record_offset = 0; the host has read the header lines).

@@ -28,6 +28,11 @@ void ahost_close(ahost_session* session);
 /* read_chimeric_alignments for -x (source/read_chimeric_alignments.cpp:560-773); data = raw (inflated) BAM stream, or SAM text (told by content, as sam_open does) */
 int ahost_ingest_bam_file(ahost_session* session, const char* bam_path, int external_duplicate_marking, unsigned int max_itd_length);
 int ahost_ingest_bam_memory(ahost_session* session, const uint8_t* data, size_t size, int external_duplicate_marking, unsigned int max_itd_length);
+/* -c: the chimeric alignments of STAR --chimOutType SeparateSAMold come in a file of their own: read_chimeric_alignments twice over one table of fragments, as source/arriba.cpp:123-130
+ * calls it -- `chimeric_path` with (separate_chimeric_bam_file, !is_rna_bam_file), then `rna_path` with both true.  Both take what ahost_ingest_bam_file takes.  The two WARNING lines
+ * of the reference go to stderr; chimeric_fragments / chimeric_malformed (may be NULL): the "(total=N)" and the WARNING count of the first call.  The batch view then holds the union
+ * as the second call leaves it.  Fails if the two headers do not list the same reference names in the same order, or if a record of `chimeric_path` has no reference. */
+int ahost_ingest_separate(ahost_session* session, const char* chimeric_path, const char* rna_path, int external_duplicate_marking, unsigned int max_itd_length, uint64_t* chimeric_fragments, uint64_t* chimeric_malformed);
 /* The result of an ingest (batch, counters, coverage) as a file, and back into a session opened on the same assembly and annotation: repeated
  * benchmark and profiling runs over one batch skip the parse.  Tooling; not a step of the reference. */
 int ahost_save_ingest(ahost_session* session, const char* path);
@@ -56,6 +61,9 @@ typedef struct { int stored_bgzf; /* the KIND of the piece (the name is from whe
 unsigned int ahost_cpu_budget(void);
 void ahost_limit_threads_of_this_thread(unsigned int n);
 int ahost_bam_open(ahost_session* session, const char* bam_path, int external_duplicate_marking, unsigned int max_itd_length, agpu_ingest_config* config);
+/* -c on the device: as ahost_bam_open, with config->role set (include/arriba_gpu.h: AGPU_ROLE_*).  The file opened with AGPU_ROLE_SEPARATE_CHIMERIC leaves its reference names
+ * with the session; the one opened with AGPU_ROLE_SEPARATE_RNA behind it must list the same names in the same order. */
+int ahost_bam_open_role(ahost_session* session, const char* bam_path, int external_duplicate_marking, unsigned int max_itd_length, int role, agpu_ingest_config* config);
 /* One sample over several GPUs: as ahost_bam_open, but the pieces that follow hold only part `part` of `parts` of the records -- the file (BGZF or
  * uncompressed BAM on disk; the alignments of a read name next to each other, as STAR writes them) is cut between read names near the byte offsets
  * size * k / parts, at places every rank finds by itself from the bytes of the file.  config->part_of_sample is set: agpu_shard_export / agpu_shard_merge
@@ -356,6 +364,7 @@ const agpu_batch_view* ahost_batch_slice_view(ahost_session* session, uint64_t f
 
 uint64_t ahost_fragment_count(ahost_session* session);
 uint64_t ahost_mapped_reads(ahost_session* session);
+uint64_t ahost_viral_read_total(ahost_session* session); /* the pristine reads the ingest counted on viral contigs (mapped_viral_reads_by_contig, source/read_chimeric_alignments.cpp:736-739), summed */
 /* FNV-1a over coverage_t as the ingest built it (coverage windows, fragment start/end flags of every contig; reference: coverage_t,
  * source/read_stats.hpp:17-27) -- a fingerprint for tests and for comparing runs, e.g. with different numbers of ingest threads. */
 uint64_t ahost_coverage_checksum(ahost_session* session);

@@ -102,6 +102,9 @@ typedef struct {
 	                                         from the record stream in HBM (include/arriba_gpu.h: agpu_rna_metrics; with host_ingest: the same code stepped on the host).
 	                                         rrna_intervals_file: BED intervals whose bases are ribosomal; a file that does not parse is refused before the feed starts.  Of
 	                                         arriba_workflow_run's sample; the samples of a session say theirs with arriba_workflow_rna_metrics.  Not for one sample over several ranks. */
+	const char* separate_chimeric_file;   /* -c: the chimeric alignments of STAR --chimOutType SeparateSAMold (Chimeric.out.sam, or its BAM), read in front of chimeric_bam_file as the
+	                                         reference reads them (source/arriba.cpp:123-130); NULL (and a zero-initialised struct) = none.  Takes what chimeric_bam_file takes.  Refused
+	                                         with any of the side outputs above, over several ranks, and when the two headers do not list the same references in the same order. */
 } arriba_workflow_options;
 
 /* what the reference prints as "(remaining=N)" / "(total=N)" / "(marked=N)", in the order of the stages; stage names as in the reference's source */
@@ -158,6 +161,10 @@ int arriba_workflow_sample(arriba_workflow_session* session, const char* chimeri
  * session + sibling device context, agpu_create_sibling) is made for it at the first call.  Samples are worked on in the order they were submitted; at most one can be submitted
  * ahead of the one at work.  arriba_workflow_sample(bam) with nothing submitted submits bam itself (the behaviour without this call).  A sample that was submitted and never
  * asked for is thrown away by arriba_workflow_close.  Returns 0, or a negative number with the text in arriba_workflow_last_error(). */
+/* -c through a session: arriba_workflow_sample with the chimeric alignments in `separate_chimeric_file` (options.separate_chimeric_file of arriba_workflow_run).  Not with samples
+ * submitted ahead, not with arriba_workflow_finish_ahead, not over several ranks. */
+int arriba_workflow_sample_separate(arriba_workflow_session* session, const char* separate_chimeric_file, const char* chimeric_bam_file, const char* output_file, const char* discarded_output_file /* may be NULL */,
+                                    arriba_workflow_report* report /* may be NULL */, arriba_workflow_timing* timing /* may be NULL */);
 int arriba_workflow_submit(arriba_workflow_session* session, const char* chimeric_bam_file);
 /* --sorted-bam of the sample that is submitted NEXT (by arriba_workflow_submit, or by an arriba_workflow_sample with nothing submitted); NULL: none.  The file is written by the thread
  * that finishes the ingest of that sample, before the stream in HBM goes to the feed of the sample behind it; if it cannot be written the sample fails with the message, FILE.tmp and
