@@ -20,7 +20,9 @@
 #include <string>
 #include <vector>
 #include <rocprim/rocprim.hpp>
-#include "agpu_context.hpp"
+#define AGPU_OPTION "--allele-counts"
+#define ALLOC(buffer, bytes) AGPU_ALLOC(buffer, bytes, state.note_peak())
+#include "resident_stream.hpp"
 #include "device_utils.hpp"
 #include "allele_core.hpp"
 
@@ -28,20 +30,7 @@ using namespace agpu;
 
 namespace {
 
-const int BLOCK = 256;
-const uint64_t LAUNCH_ITEMS = 1ull << 30; // one lane per record, launched in pieces that stay below 2^32 work-items
-
-#define HIP_CHECK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { set_last_error(std::string(#call) + ": " + hipGetErrorString(e_)); return AGPU_ERR_DEVICE; } } while (0)
-#define ALLOC(buffer, bytes) do { if (!(buffer).allocate(bytes)) { set_last_error("--allele-counts: hipMalloc failed (" #buffer ")"); return AGPU_ERR_NO_MEMORY; } state.note_peak(); } while (0)
-
-inline unsigned int grid_for(uint64_t n) { return (unsigned int) std::max<uint64_t>((n + BLOCK - 1) / BLOCK, 1); }
-
 enum { PASS_SITES = 0, PASS_COUNT = 1, PASS_ROWS = 2, PASSES = 3 };
-
-__device__ __forceinline__ unsigned int wave_sum(unsigned int mine) {
-	for (int offset = 32; offset > 0; offset >>= 1) mine += __shfl_down(mine, offset);
-	return mine; // (of lane 0)
-}
 
 // keys: the sorted placed sites.  The bitmap has a word for every 32 windows of window_offset[n_ref] and is zero before.
 __global__ void __launch_bounds__(BLOCK) allele_bitmap_kernel(const uint64_t* __restrict__ keys, uint64_t placed, const uint64_t* __restrict__ window_offset, uint32_t n_ref, uint32_t* bitmap) {
@@ -106,12 +95,10 @@ __global__ void __launch_bounds__(BLOCK) allele_ref_kernel(const agpu_allele_sit
 
 bool knob(const char* name) { const char* value = getenv(name); return value != nullptr && value[0] == '1'; } // (for the measurements of DESIGN.md 4.17)
 
-unsigned int bits_of(uint64_t below) { unsigned int bits = 1; while (bits < 32 && (1ull << bits) < below) ++bits; return bits; } // enough for every value < below
-
-int count(agpu_ctx* ctx, const agpu_allele_site* sites, uint64_t n_sites, const uint32_t* ref_length, uint32_t n_ref, uint32_t min_mapq, uint32_t min_baseq, hipEvent_t* events) {
+int count(agpu_ctx* ctx, const ResidentStream& resident, const agpu_allele_site* sites, uint64_t n_sites, const uint32_t* ref_length, uint32_t n_ref, uint32_t min_mapq, uint32_t min_baseq, hipEvent_t* events) {
 	AlleleState& state = ctx->allele;
 	hipStream_t s = ctx->stream;
-	const uint64_t size = ctx->last_ingest_stream_size, n = ctx->last_ingest_records;
+	const uint64_t size = resident.stream_size, n = resident.records;
 	state.stats.records = n; state.stats.sites = n_sites;
 	// the placed sites as keys with their lines; the first window of every reference
 	std::vector<uint64_t> keys; std::vector<uint32_t> lines; std::vector<uint64_t> window_offset((size_t) n_ref + 1, 0);
@@ -161,16 +148,15 @@ int count(agpu_ctx* ctx, const agpu_allele_site* sites, uint64_t n_sites, const 
 	// the count over the records
 	HIP_CHECK(hipEventRecord(events[PASS_COUNT], s));
 	if (n > 0) { // (also without a placed site: `contributing` is the number of records that pass the filter, whatever the sites are)
-		const uint8_t* stream = ctx->ingest_stream.as<uint8_t>();
-		const uint64_t* record_offset = ctx->scratch("ingest.record_offset").as<uint64_t>();
+		const uint8_t* stream = resident.stream;
+		const uint64_t* record_offset = resident.record_offset;
 		const AlleleSites view = { placed > 0 ? sorted_keys.as<uint64_t>() : nullptr, placed, with_bitmap ? bitmap.as<uint32_t>() : nullptr, windows.as<uint64_t>() };
 		const bool plain = knob("ARRIBA_ALLELE_PLAIN_ATOMICS");
 		KernelTimer timer(ctx, "allele_count_kernel", n * 72);
-		for (uint64_t first = 0; first < n; first += LAUNCH_ITEMS) {
-			const unsigned int grid = grid_for(std::min(LAUNCH_ITEMS, n - first));
+		for_each_launch_piece(n, [&](uint64_t first, unsigned int grid) {
 			if (plain) allele_count_kernel<false><<<grid, BLOCK, 0, s>>>(stream, size, record_offset, n, first, lengths.as<uint32_t>(), n_ref, view, min_mapq, min_baseq, counts.as<uint32_t>(), contributing.as<unsigned long long>());
 			else allele_count_kernel<true><<<grid, BLOCK, 0, s>>>(stream, size, record_offset, n, first, lengths.as<uint32_t>(), n_ref, view, min_mapq, min_baseq, counts.as<uint32_t>(), contributing.as<unsigned long long>());
-		}
+		});
 	}
 	// REF and the rows in the order of the lines
 	HIP_CHECK(hipEventRecord(events[PASS_ROWS], s));
@@ -203,35 +189,19 @@ int agpu_allele_counts(agpu_ctx* ctx, const agpu_allele_site* sites, uint64_t n_
 	if (stats) memset(stats, 0, sizeof(*stats));
 	if (min_mapq > 255 || min_baseq > 255) { set_last_error("agpu_allele_counts: a threshold above 255"); return AGPU_ERR_INVALID; }
 	if (n_sites > ALLELE_MAX_SITES) { set_last_error("agpu_allele_counts: more than 2^29-1 sites"); return AGPU_ERR_INVALID; }
-	if (ctx->ingest_active) { set_last_error("agpu_allele_counts: an ingest is under way on this context (it comes behind agpu_ingest_finish)"); return AGPU_ERR_INVALID; }
-	if (ctx->last_ingest_part_of_sample) { set_last_error("allele counts of one sample over several GPUs are not supported"); return AGPU_ERR_INVALID; }
-	const uint64_t size = ctx->last_ingest_stream_size, base = ctx->last_ingest_first_record, n = ctx->last_ingest_records;
-	DeviceBuffer& record_offset = ctx->scratch("ingest.record_offset");
-	if (!ctx->batch_from_ingest || !ctx->last_ingest_kept || ctx->ingest_stream.ptr == nullptr || record_offset.ptr == nullptr || ctx->ingest_stream.capacity < (size + 3) / 4 * 4 || record_offset.capacity < n * 8) {
-		set_last_error("agpu_allele_counts: the record stream of the last ingest is not on the device any more (it was given back under memory pressure, another ingest has begun, or there was no ingest)");
-		return AGPU_ERR_INVALID;
-	}
-	if (n >= 0xFFFFFFF0ull || base > size) { set_last_error("agpu_allele_counts: more than 2^32-16 alignment records"); return AGPU_ERR_INVALID; }
-	if (!ctx->have_genome) { set_last_error("agpu_allele_counts: agpu_upload_genome must run first"); return AGPU_ERR_INVALID; }
-	if (n_ref != ctx->ingest_n_targets || (n_ref > 0 && ctx->ingest_tid_to_contig.ptr == nullptr)) { set_last_error("agpu_allele_counts: the lengths are not those of the references of the last ingest"); return AGPU_ERR_INVALID; }
+	ResidentStream resident;
+	TRY(resident_stream(ctx, "agpu_allele_counts", "allele counts of one sample over several GPUs are not supported", nullptr, resident, NEEDS_GENOME | NEEDS_REFERENCES, n_ref));
 	HIP_CHECK(hipSetDevice(ctx->device));
 	AlleleState& state = ctx->allele;
-	state.active = true; // (the stream is read from here on: nothing of this context is given back when an allocation fails)
 	memset(&state.stats, 0, sizeof(state.stats));
 	state.rows.clear(); state.peak = 0;
-	hipEvent_t events[PASSES + 1] = {};
-	int status = AGPU_OK;
-	for (int k = 0; k <= PASSES && status == AGPU_OK; ++k) if (hipEventCreate(&events[k]) != hipSuccess) { set_last_error("--allele-counts: hipEventCreate failed"); status = AGPU_ERR_DEVICE; }
-	if (status == AGPU_OK) status = count(ctx, sites, n_sites, ref_length, n_ref, min_mapq, min_baseq, events);
-	(void) hipStreamSynchronize(ctx->stream); // (nothing of a failed call is in flight when its buffers go)
-	if (status == AGPU_OK) for (int k = 0; k < PASSES; ++k) { float ms = 0; if (hipEventElapsedTime(&ms, events[k], events[k + 1]) == hipSuccess) state.stats.seconds[k] = ms / 1000.0; }
-	for (int k = 0; k <= PASSES; ++k) if (events[k]) (void) hipEventDestroy(events[k]);
-	state.stats.peak_bytes = state.peak;
-	state.release_all();
-	state.active = false;
-	collect_kernel_samples(ctx);
+	const int status = one_shot<PASSES + 1>(ctx, state, "agpu_allele_counts", [&](hipEvent_t* events) {
+		const int counted = count(ctx, resident, sites, n_sites, ref_length, n_ref, min_mapq, min_baseq, events);
+		(void) hipStreamSynchronize(ctx->stream); // (the events of a call without sites and records have happened)
+		if (counted == AGPU_OK) for (int k = 0; k < PASSES; ++k) { float ms = 0; if (hipEventElapsedTime(&ms, events[k], events[k + 1]) == hipSuccess) state.stats.seconds[k] = ms / 1000.0; }
+		return counted;
+	}, [&](int) { state.stats.peak_bytes = state.peak; state.release_all(); });
 	if (status != AGPU_OK) { state.rows.clear(); return status; }
-	{ std::lock_guard<std::mutex> lock(ctx->profile_mutex); if (!ctx->failed_launch.empty()) { state.rows.clear(); set_last_error("agpu_allele_counts: " + ctx->failed_launch); return AGPU_ERR_DEVICE; } }
 	*rows = state.rows.data();
 	if (stats) *stats = state.stats;
 	return AGPU_OK;

@@ -65,14 +65,9 @@ bool DeviceBuffer::release_idle_buffers() {
 		// the largest reservation, fall back to fewer workgroups by themselves (agpu_mismappers.hip)
 		if (ctx->pool.use_count() > 1) continue;
 		if (ctx->sorted_bam_active) continue; // (between agpu_sorted_bam_begin and _end the stream of the last ingest and the "sortedbam.*" buffers are in use)
-		if (ctx->virus.active) continue; // (agpu_virus_expression reads the stream)
-		if (ctx->depth.active) continue; // (between agpu_depth_begin and _end: the mark kernel reads the stream)
-		if (ctx->genecount.active) continue; // (agpu_gene_counts reads the stream)
-		if (ctx->rnametrics.active) continue; // (agpu_rna_metrics reads the stream)
-		if (ctx->junction.active) continue; // (agpu_splice_junctions reads the stream)
-		if (ctx->allele.active) continue; // (agpu_allele_counts reads the stream)
-		if (ctx->realign.active) continue; // (between agpu_realign_begin and _end: the text kernels read the stream)
-		if (ctx->support.active) continue; // (agpu_support_pool_build reads the stream; between agpu_supporting_begin and _end nothing of the context moves either)
+		// (a consumer of the stream of the last ingest is at work -- inside a call that does it all, or between its begin and its end: its kernels read the stream, and between
+		//  agpu_supporting_begin and _end nothing of the context moves either)
+		if (ctx->consumer_active()) continue;
 		(void) hipStreamSynchronize(ctx->stream);
 		if (!ctx->ingest_active && !ctx->ingest_finishing) { if (release_ingest_buffers(ctx)) released = true; }
 		else { // an ingest runs: nothing of the stages of the sample before is needed any more

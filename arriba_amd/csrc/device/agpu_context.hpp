@@ -102,37 +102,43 @@ struct ScratchPool {
 	DeviceBuffer& get(const char* name) { std::lock_guard<std::mutex> lock(mutex); return buffers[name]; }
 };
 struct PoolSlots { DeviceBuffer* slot[AGPU_PIECE_SLOTS]; DeviceBuffer& operator[](size_t k) { return *slot[k]; } };
-// --supporting-alignments (agpu_supporting.hip): the records of the listed read names, copied out of the stream behind the ingest, until the rows of fusions.tsv are known.  The
-// "support.*" buffers are the context's own: not in the pool the lanes of a session share, not among the buffers that change hands between them (take_sample_buffers), not given
-// back under memory pressure (release_ingest_buffers) -- the pool of a sample lives until agpu_support_pool_release or the next build on the context.
-struct SupportState {
+// A view of the record stream that the last ingest left in HBM, as the guard in front of every consumer hands it out (resident_stream.hpp: resident_stream)
+struct ResidentStream { const uint8_t* stream = nullptr; uint64_t stream_size = 0, first_record = 0, records = 0; const uint64_t* record_offset = nullptr; };
+// What every consumer of that stream keeps with its context: buffers of its own, addressed by name -- not in the pool the lanes of a session share, not among the buffers that
+// change hands between them (take_sample_buffers), not given back under memory pressure (release_ingest_buffers) -- and `active`: set while the consumer reads the stream, when
+// nothing of the context may be given back (DeviceBuffer::release_idle_buffers asks every consumer of the context: each one enters itself in the list it is constructed with)
+struct StreamConsumer {
+	explicit StreamConsumer(std::vector<const StreamConsumer*>& of_context) { of_context.push_back(this); }
+	StreamConsumer(const StreamConsumer&) = delete; StreamConsumer& operator=(const StreamConsumer&) = delete;
 	std::map<std::string, DeviceBuffer> buffers;
 	DeviceBuffer& buffer(const char* name) { return buffers[name]; }
-	void release_all() { for (std::map<std::string, DeviceBuffer>::iterator b = buffers.begin(); b != buffers.end(); ++b) b->second.release(); built = false; }
+	void release_all() { for (std::map<std::string, DeviceBuffer>::iterator b = buffers.begin(); b != buffers.end(); ++b) b->second.release(); }
 	void release_prefix(const char* prefix) { for (std::map<std::string, DeviceBuffer>::iterator b = buffers.begin(); b != buffers.end(); ++b) if (b->first.compare(0, strlen(prefix), prefix) == 0) b->second.release(); }
+	void release_all_but(const char* kept) { for (std::map<std::string, DeviceBuffer>::iterator b = buffers.begin(); b != buffers.end(); ++b) if (b->first != kept) b->second.release(); }
 	uint64_t allocated() const { uint64_t sum = 0; for (std::map<std::string, DeviceBuffer>::const_iterator b = buffers.begin(); b != buffers.end(); ++b) sum += b->second.capacity; return sum; }
-	bool built = false, strip_hit_index = false, active = false, index_ready = false;
+	bool active = false;
+	uint64_t peak = 0;
+	void note_peak() { const uint64_t now = allocated(); if (now > peak) peak = now; }
+};
+// --supporting-alignments (agpu_supporting.hip): the records of the listed read names, copied out of the stream behind the ingest, until the rows of fusions.tsv are known.  The
+// pool of a sample ("support.*") lives until agpu_support_pool_release or the next build on the context.
+struct SupportState : StreamConsumer {
+	using StreamConsumer::StreamConsumer;
+	void release_all() { StreamConsumer::release_all(); built = false; }
+	bool built = false, strip_hit_index = false, index_ready = false;
 	uint64_t n_names = 0, table_slots = 0, records = 0 /* of the pool */, bytes = 0; uint32_t hash_bits = 64;
 	// between agpu_supporting_begin and agpu_supporting_end
 	uint32_t n_rows = 0; uint64_t emissions = 0, blocks = 0, window_blocks = 0, next_block = 0, gathered_block = ~0ull, index_first = 0;
 	std::vector<uint64_t> row_first, row_bytes, row_block_begin, row_out_offset; // [n_rows + 1]: first record, payload bytes, first block, first byte of the framed blocks
 };
-// --virus-expression (agpu_virus.hip): the "virus.*" buffers are the context's own and live inside one agpu_virus_expression; what the call returns stays in host memory here
-struct VirusState {
-	std::map<std::string, DeviceBuffer> buffers;
-	DeviceBuffer& buffer(const char* name) { return buffers[name]; }
-	void release_all() { for (std::map<std::string, DeviceBuffer>::iterator b = buffers.begin(); b != buffers.end(); ++b) b->second.release(); }
-	uint64_t allocated() const { uint64_t sum = 0; for (std::map<std::string, DeviceBuffer>::const_iterator b = buffers.begin(); b != buffers.end(); ++b) sum += b->second.capacity; return sum; }
-	bool active = false;
+// --virus-expression (agpu_virus.hip): the "virus.*" buffers live inside one agpu_virus_expression; what the call returns stays in host memory here
+struct VirusState : StreamConsumer {
+	using StreamConsumer::StreamConsumer;
 	std::vector<uint64_t> reads, covered, kmer_count, shared; std::vector<uint32_t> active_slots;
 };
-// --coverage (agpu_depth.hip): the "depth.*" buffers are the context's own and live from agpu_depth_begin to agpu_depth_end
-struct DepthState {
-	std::map<std::string, DeviceBuffer> buffers;
-	DeviceBuffer& buffer(const char* name) { return buffers[name]; }
-	void release_all() { for (std::map<std::string, DeviceBuffer>::iterator b = buffers.begin(); b != buffers.end(); ++b) b->second.release(); }
-	uint64_t allocated() const { uint64_t sum = 0; for (std::map<std::string, DeviceBuffer>::const_iterator b = buffers.begin(); b != buffers.end(); ++b) sum += b->second.capacity; return sum; }
-	bool active = false;
+// --coverage (agpu_depth.hip): the "depth.*" buffers live from agpu_depth_begin to agpu_depth_end
+struct DepthState : StreamConsumer {
+	using StreamConsumer::StreamConsumer;
 	uint32_t n_ref = 0;
 	uint64_t slots = 0, window = 0, text_window = 0; // slots of the array of depths; positions per window of runs; bytes per window of text
 	uint64_t next_slot = 0;                           // where the next window of positions begins
@@ -142,57 +148,34 @@ struct DepthState {
 	agpu_depth_stats stats = {};
 	hipEvent_t events[2] = { nullptr, nullptr };
 };
-// --mark-duplicates (agpu_markdup.hip): the "markdup.*" buffers are the context's own; all but "markdup.flag" (one byte per record) are released before agpu_sorted_bam_begin
-// allocates "sortedbam.*", that one by agpu_sorted_bam_end
-struct MarkdupState {
-	std::map<std::string, DeviceBuffer> buffers;
-	DeviceBuffer& buffer(const char* name) { return buffers[name]; }
-	void release_all() { for (std::map<std::string, DeviceBuffer>::iterator b = buffers.begin(); b != buffers.end(); ++b) b->second.release(); }
-	void release_all_but(const char* kept) { for (std::map<std::string, DeviceBuffer>::iterator b = buffers.begin(); b != buffers.end(); ++b) if (b->first != kept) b->second.release(); }
-	uint64_t allocated() const { uint64_t sum = 0; for (std::map<std::string, DeviceBuffer>::const_iterator b = buffers.begin(); b != buffers.end(); ++b) sum += b->second.capacity; return sum; }
+// --mark-duplicates (agpu_markdup.hip): all of "markdup.*" but "markdup.flag" (one byte per record) is released before agpu_sorted_bam_begin allocates "sortedbam.*", that one
+// by agpu_sorted_bam_end.  It runs inside agpu_sorted_bam_begin: sorted_bam_active of the context stands for its `active`
+struct MarkdupState : StreamConsumer {
+	using StreamConsumer::StreamConsumer;
 	bool next = false, on = false; // agpu_sorted_bam_set_mark_duplicates: of the next agpu_sorted_bam_begin; of the begin ... end under way
 	agpu_markdup_counts counts = {};
 };
-// --gene-counts (agpu_genecount.hip): the "genecount.*" buffers are the context's own and live inside one agpu_gene_counts
-struct GenecountState {
-	std::map<std::string, DeviceBuffer> buffers;
-	DeviceBuffer& buffer(const char* name) { return buffers[name]; }
-	void release_all() { for (std::map<std::string, DeviceBuffer>::iterator b = buffers.begin(); b != buffers.end(); ++b) b->second.release(); }
-	uint64_t allocated() const { uint64_t sum = 0; for (std::map<std::string, DeviceBuffer>::const_iterator b = buffers.begin(); b != buffers.end(); ++b) sum += b->second.capacity; return sum; }
-	bool active = false;
+// --gene-counts (agpu_genecount.hip): the "genecount.*" buffers live inside one agpu_gene_counts
+struct GenecountState : StreamConsumer {
+	using StreamConsumer::StreamConsumer;
 	agpu_gene_count_stats stats = {};
 };
-// --splice-junctions (agpu_junctions.hip): the "junction.*" buffers are the context's own and live inside one agpu_splice_junctions; the rows stay until the next call
-struct JunctionState {
-	std::map<std::string, DeviceBuffer> buffers;
-	DeviceBuffer& buffer(const char* name) { return buffers[name]; }
-	void release_all() { for (std::map<std::string, DeviceBuffer>::iterator b = buffers.begin(); b != buffers.end(); ++b) b->second.release(); }
-	uint64_t allocated() const { uint64_t sum = 0; for (std::map<std::string, DeviceBuffer>::const_iterator b = buffers.begin(); b != buffers.end(); ++b) sum += b->second.capacity; return sum; }
-	bool active = false;
-	uint64_t peak = 0;
-	void note_peak() { const uint64_t now = allocated(); if (now > peak) peak = now; }
+// --splice-junctions (agpu_junctions.hip): the "junction.*" buffers live inside one agpu_splice_junctions; the rows stay until the next call
+struct JunctionState : StreamConsumer {
+	using StreamConsumer::StreamConsumer;
 	agpu_junction_stats stats = {};
 	std::vector<agpu_junction_row> rows;
 };
-// --allele-counts (agpu_alleles.hip): the "allele.*" buffers are the context's own and live inside one agpu_allele_counts; the rows stay until the next call
-struct AlleleState {
-	std::map<std::string, DeviceBuffer> buffers;
-	DeviceBuffer& buffer(const char* name) { return buffers[name]; }
-	void release_all() { for (std::map<std::string, DeviceBuffer>::iterator b = buffers.begin(); b != buffers.end(); ++b) b->second.release(); }
-	uint64_t allocated() const { uint64_t sum = 0; for (std::map<std::string, DeviceBuffer>::const_iterator b = buffers.begin(); b != buffers.end(); ++b) sum += b->second.capacity; return sum; }
-	bool active = false;
-	uint64_t peak = 0;
-	void note_peak() { const uint64_t now = allocated(); if (now > peak) peak = now; }
+// --allele-counts (agpu_alleles.hip): the "allele.*" buffers live inside one agpu_allele_counts; the rows stay until the next call
+struct AlleleState : StreamConsumer {
+	using StreamConsumer::StreamConsumer;
 	agpu_allele_stats stats = {};
 	std::vector<agpu_allele_row> rows;
 };
-// --realign-reads (agpu_realign.hip): the "realign.*" buffers are the context's own and live between agpu_realign_begin and _end
-struct RealignState {
-	std::map<std::string, DeviceBuffer> buffers;
-	DeviceBuffer& buffer(const char* name) { return buffers[name]; }
-	void release_all() { for (std::map<std::string, DeviceBuffer>::iterator b = buffers.begin(); b != buffers.end(); ++b) b->second.release(); }
-	uint64_t allocated() const { uint64_t sum = 0; for (std::map<std::string, DeviceBuffer>::const_iterator b = buffers.begin(); b != buffers.end(); ++b) sum += b->second.capacity; return sum; }
-	bool active = false;
+// --realign-reads (agpu_realign.hip): the "realign.*" buffers live between agpu_realign_begin and _end
+struct RealignState : StreamConsumer {
+	using StreamConsumer::StreamConsumer;
+	ResidentStream stream; // of agpu_realign_begin, for the windows of text behind it
 	bool paired = false, want_kept = false, wave_form = true;
 	uint32_t n_ref = 0;
 	uint64_t records = 0, window = 0, launch_items = 0; // records of the stream; bytes of a window of text; work-items of a launch
@@ -200,14 +183,10 @@ struct RealignState {
 	agpu_realign_stats stats = {};
 	hipEvent_t events[2] = { nullptr, nullptr };
 };
-// --rna-metrics (agpu_rnametrics.hip): the "rnametrics.*" buffers are the context's own.  The copy of the region track stays from the first agpu_rna_metrics that brings it until
-// another track comes or the context goes; the counter block and the lengths live inside one call
-struct RnametricsState {
-	std::map<std::string, DeviceBuffer> buffers;
-	DeviceBuffer& buffer(const char* name) { return buffers[name]; }
-	void release_all() { for (std::map<std::string, DeviceBuffer>::iterator b = buffers.begin(); b != buffers.end(); ++b) b->second.release(); }
-	uint64_t allocated() const { uint64_t sum = 0; for (std::map<std::string, DeviceBuffer>::const_iterator b = buffers.begin(); b != buffers.end(); ++b) sum += b->second.capacity; return sum; }
-	bool active = false;
+// --rna-metrics (agpu_rnametrics.hip): the copy of the region track ("rnametrics.track.*") stays from the first agpu_rna_metrics that brings it until another track comes or the
+// context goes; the counter block and the lengths live inside one call
+struct RnametricsState : StreamConsumer {
+	using StreamConsumer::StreamConsumer;
 	uint64_t track_id = 0; // of the track on the device (0: none)
 	agpu_region_track track = {}; // ... with device pointers
 	agpu_rna_metrics_stats stats = {};
@@ -303,15 +282,19 @@ struct agpu_ctx {
 	uint64_t sorted_bam_chunks = 0, sorted_bam_intervals = 0, sorted_bam_no_coor = 0; uint32_t sorted_bam_n_ref = 0;
 	int sorted_bam_level_next = 0, sorted_bam_level = 0; // agpu_sorted_bam_set_compression: of the next agpu_sorted_bam_begin; of the begin ... end under way
 	uint64_t sorted_bam_compressed_bytes = 0;            // of the windows fetched so far
-	agpu::SupportState support; // --supporting-alignments (agpu_supporting.hip)
-	agpu::VirusState virus;     // --virus-expression (agpu_virus.hip)
-	agpu::DepthState depth;     // --coverage (agpu_depth.hip)
-	agpu::MarkdupState markdup; // --mark-duplicates (agpu_markdup.hip)
-	agpu::GenecountState genecount; // --gene-counts (agpu_genecount.hip)
-	agpu::JunctionState junction;   // --splice-junctions (agpu_junctions.hip)
-	agpu::AlleleState allele;       // --allele-counts (agpu_alleles.hip)
-	agpu::RnametricsState rnametrics; // --rna-metrics (agpu_rnametrics.hip)
-	agpu::RealignState realign;     // --realign-reads (agpu_realign.hip)
+	agpu::ResidentStream sorted_bam_stream;              // of agpu_sorted_bam_begin, for the gathers behind it
+	// the other consumers of that stream: each enters itself in `consumers` (which therefore stands in front of them)
+	std::vector<const agpu::StreamConsumer*> consumers;
+	bool consumer_active() const { for (size_t k = 0; k < consumers.size(); ++k) if (consumers[k]->active) return true; return false; }
+	agpu::SupportState support{consumers};       // --supporting-alignments (agpu_supporting.hip)
+	agpu::VirusState virus{consumers};           // --virus-expression (agpu_virus.hip)
+	agpu::DepthState depth{consumers};           // --coverage (agpu_depth.hip)
+	agpu::MarkdupState markdup{consumers};       // --mark-duplicates (agpu_markdup.hip)
+	agpu::GenecountState genecount{consumers};   // --gene-counts (agpu_genecount.hip)
+	agpu::JunctionState junction{consumers};     // --splice-junctions (agpu_junctions.hip)
+	agpu::AlleleState allele{consumers};         // --allele-counts (agpu_alleles.hip)
+	agpu::RnametricsState rnametrics{consumers}; // --rna-metrics (agpu_rnametrics.hip)
+	agpu::RealignState realign{consumers};       // --realign-reads (agpu_realign.hip)
 	// A pushed piece: copied on the context's stream (piece_copied: the caller's buffer is free), unwrapped and CRC-checked on a stream of its own (piece_stream; piece_ready: its
 	// bytes are in the stream, piece_done: the raw bytes are not needed any more), so that the copy of the next piece never waits for a kernel; AGPU_PIECE_SLOTS raw buffers in turn
 	hipStream_t piece_stream = nullptr, piece_stream2 = nullptr /* deflated pieces take the two in turn */; hipEvent_t piece_copied[AGPU_PIECE_SLOTS] = {}, piece_ready[AGPU_PIECE_SLOTS] = {}, piece_done[AGPU_PIECE_SLOTS] = {};
@@ -378,7 +361,7 @@ int ingest_piece_pushed(agpu_ctx* ctx);
 // agpu_sam.hip, for agpu_ingest_finish: AGPU_ERR_INVALID with "failed to load alignments: SAM line N: <reason>" if a line of the SAM text of this ingest was malformed
 int sam_ingest_verdict(agpu_ctx* ctx);
 // agpu_markdup.hip, for agpu_sorted_bam_begin: one byte per record of the stream of the last ingest (MDUP_FLAG_MASK or 0) into "markdup.flag", everything else of "markdup.*" released
-int markdup_find(agpu_ctx* ctx);
+int markdup_find(agpu_ctx* ctx, const ResidentStream& stream);
 // agpu_api.hip: the buffers that hold a sample (batch, gene sets, candidates, read lists, k-mer index, ...) change hands between the lanes of a session: `ctx`, about to build
 // its batch, takes what its sibling -- whose sample is done on the device -- holds wherever that is the larger buffer; the sibling's sample is gone afterwards
 void take_sample_buffers(agpu_ctx* ctx, bool batch_group = true, bool stage_group = true);

@@ -17,7 +17,8 @@
 #include <string>
 #include <vector>
 #include <rocprim/rocprim.hpp>
-#include "agpu_context.hpp"
+#define AGPU_OPTION "--coverage"
+#include "resident_stream.hpp"
 #include "device_utils.hpp"
 #include "depth_core.hpp"
 
@@ -25,22 +26,10 @@ using namespace agpu;
 
 namespace {
 
-const int BLOCK = 256;
 const uint64_t DEFAULT_WINDOW = 1ull << 25;      // positions whose runs are found at a time
 const uint64_t DEFAULT_TEXT_WINDOW = 16ull << 20; // bytes of a staging window
 
-#define HIP_CHECK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { set_last_error(std::string(#call) + ": " + hipGetErrorString(e_)); return AGPU_ERR_DEVICE; } } while (0)
-#define ALLOC(buffer, bytes) do { if (!(buffer).allocate(bytes)) { set_last_error("--coverage: hipMalloc failed (" #buffer ")"); return AGPU_ERR_NO_MEMORY; } } while (0)
-#define TRY(call) do { int s_ = (call); if (s_ != AGPU_OK) return s_; } while (0)
-
-inline unsigned int grid_for(uint64_t n) { return (unsigned int) std::max<uint64_t>((n + BLOCK - 1) / BLOCK, 1); }
-
 enum { COUNTER_RECORDS = 0, COUNTER_SEGMENTS = 1, COUNTER_COVERED = 2, COUNTER_ALIGNED = 3, COUNTER_MAX_DEPTH = 4, COUNTER_WORDS = 5 }; // 64-bit words
-
-__device__ __forceinline__ unsigned long long wave_sum(unsigned long long mine) {
-	for (int offset = 32; offset > 0; offset >>= 1) mine += __shfl_down(mine, offset);
-	return mine; // (of lane 0)
-}
 
 struct DifferenceMark {
 	uint32_t* slots; // of the contig
@@ -133,33 +122,16 @@ __global__ void __launch_bounds__(BLOCK) depth_text_kernel(const uint4* __restri
 	depth_line(names + name_offset[run.x], name_offset[run.x + 1] - name_offset[run.x], run.y, run.z, run.w, put);
 }
 
-template <class Call> int with_temporary(agpu_ctx* ctx, const char* name, uint64_t bytes, Call call) {
-	DeviceBuffer& temporary_buffer = ctx->depth.buffer("depth.rocprim");
-	size_t temporary = 0;
-	HIP_CHECK(call(nullptr, temporary));
-	if (temporary > temporary_buffer.capacity) ALLOC(temporary_buffer, temporary);
-	KernelTimer timer(ctx, name, bytes);
-	HIP_CHECK(call(temporary_buffer.ptr, temporary));
-	return AGPU_OK;
-}
-
 void note_peak(DepthState& state) { state.stats.peak_bytes = std::max<uint64_t>(state.stats.peak_bytes, state.allocated()); }
 
 // behind a hipStreamSynchronize: the milliseconds between the two events of the state go to seconds[part]
 void add_seconds(DepthState& state, int part) { float ms = 0; if (hipEventElapsedTime(&ms, state.events[0], state.events[1]) == hipSuccess) state.stats.seconds[part] += ms / 1000.0; }
 
-uint64_t knob_of(const char* name, uint64_t otherwise, uint64_t most) {
-	const char* knob = getenv(name);
-	uint64_t value = otherwise;
-	if (knob != nullptr && knob[0] != 0) value = std::max<uint64_t>(strtoull(knob, nullptr, 10), 1);
-	return std::min(value, most);
-}
-
 // the marks and the scan: "depth.depth" holds the depth of every slot
-int mark_and_scan(agpu_ctx* ctx, const uint32_t* ref_length, const char* names, const uint32_t* name_offset, uint32_t n_ref) {
+int mark_and_scan(agpu_ctx* ctx, const ResidentStream& resident, const uint32_t* ref_length, const char* names, const uint32_t* name_offset, uint32_t n_ref) {
 	hipStream_t s = ctx->stream;
 	DepthState& state = ctx->depth;
-	const uint64_t size = ctx->last_ingest_stream_size, n = ctx->last_ingest_records;
+	const uint64_t size = resident.stream_size, n = resident.records;
 	std::vector<uint64_t> host_offset((size_t) n_ref + 1, 0);
 	for (uint32_t t = 0; t < n_ref; ++t) host_offset[t + 1] = host_offset[t] + ref_length[t] + 1;
 	const uint64_t slots = host_offset[n_ref], name_bytes = n_ref > 0 ? name_offset[n_ref] : 0;
@@ -185,14 +157,14 @@ int mark_and_scan(agpu_ctx* ctx, const uint32_t* ref_length, const char* names, 
 	HIP_CHECK(hipEventRecord(state.events[0], s));
 	HIP_CHECK(hipMemsetAsync(depth.ptr, 0, std::max<uint64_t>(slots, 1) * 4, s));
 	if (n > 0 && slots > 0) { KernelTimer timer(ctx, "depth_mark_kernel", n * 8 + n * 64);
-	  depth_mark_kernel<<<grid_for(n), BLOCK, 0, s>>>(ctx->ingest_stream.as<uint8_t>(), size, ctx->scratch("ingest.record_offset").as<uint64_t>(), n, contig_offset.as<uint64_t>(), lengths.as<uint32_t>(), n_ref, depth.as<uint32_t>(),
+	  depth_mark_kernel<<<grid_for(n), BLOCK, 0, s>>>(resident.stream, size, resident.record_offset, n, contig_offset.as<uint64_t>(), lengths.as<uint32_t>(), n_ref, depth.as<uint32_t>(),
 	    counters.as<unsigned long long>()); }
 	HIP_CHECK(hipEventRecord(state.events[1], s));
 	HIP_CHECK(hipStreamSynchronize(s));
 	HIP_CHECK(hipGetLastError());
 	add_seconds(state, 0);
 	HIP_CHECK(hipEventRecord(state.events[0], s));
-	if (slots > 0) TRY(with_temporary(ctx, "depth rocprim::inclusive_scan(marks)", slots * 8, [&](void* t, size_t& b) { return rocprim::inclusive_scan(t, b, depth.as<uint32_t>(), depth.as<uint32_t>(), (size_t) slots, rocprim::plus<uint32_t>(), s); }));
+	if (slots > 0) TRY(with_temporary(ctx, state.buffer("depth.rocprim"), "depth rocprim::inclusive_scan(marks)", slots * 8, [&](void* t, size_t& b) { return rocprim::inclusive_scan(t, b, depth.as<uint32_t>(), depth.as<uint32_t>(), (size_t) slots, rocprim::plus<uint32_t>(), s); }));
 	note_peak(state);
 	HIP_CHECK(hipEventRecord(state.events[1], s));
 	HIP_CHECK(hipStreamSynchronize(s));
@@ -211,7 +183,7 @@ int find_runs(agpu_ctx* ctx) {
 	HIP_CHECK(hipEventRecord(state.events[0], s));
 	{ KernelTimer timer(ctx, "depth_flag_kernel", count * 12);
 	  depth_flag_kernel<<<grid_for(count + 1), BLOCK, 0, s>>>(depth.as<uint32_t>(), state.slots, first, count, flags.as<uint64_t>()); }
-	TRY(with_temporary(ctx, "depth rocprim::exclusive_scan(flags)", count * 16, [&](void* t, size_t& b) { return rocprim::exclusive_scan(t, b, flags.as<uint64_t>(), place.as<uint64_t>(), (uint64_t) 0, (size_t) count + 1, rocprim::plus<uint64_t>(), s); }));
+	TRY(with_temporary(ctx, state.buffer("depth.rocprim"), "depth rocprim::exclusive_scan(flags)", count * 16, [&](void* t, size_t& b) { return rocprim::exclusive_scan(t, b, flags.as<uint64_t>(), place.as<uint64_t>(), (uint64_t) 0, (size_t) count + 1, rocprim::plus<uint64_t>(), s); }));
 	uint64_t totals = 0;
 	HIP_CHECK(hipMemcpyAsync(&totals, place.as<uint64_t>() + count, 8, hipMemcpyDeviceToHost, s));
 	HIP_CHECK(hipStreamSynchronize(s));
@@ -232,7 +204,7 @@ int find_runs(agpu_ctx* ctx) {
 		{ KernelTimer timer(ctx, "depth_line_kernel", ends * 40);
 		  depth_line_kernel<<<grid_for(ends + 1), BLOCK, 0, s>>>(runs.ptr, ends, depth.as<uint32_t>(), state.buffer("depth.contig_offset").as<uint64_t>(), state.n_ref, state.buffer("depth.name_offset").as<uint32_t>(), line_bytes.as<uint32_t>(),
 		    counters.as<unsigned long long>()); }
-		TRY(with_temporary(ctx, "depth rocprim::exclusive_scan(line bytes)", ends * 12, [&](void* t, size_t& b) { return rocprim::exclusive_scan(t, b, line_bytes.as<uint32_t>(), line_offset.as<uint64_t>(), (uint64_t) 0, (size_t) ends + 1, rocprim::plus<uint64_t>(), s); }));
+		TRY(with_temporary(ctx, state.buffer("depth.rocprim"), "depth rocprim::exclusive_scan(line bytes)", ends * 12, [&](void* t, size_t& b) { return rocprim::exclusive_scan(t, b, line_bytes.as<uint32_t>(), line_offset.as<uint64_t>(), (uint64_t) 0, (size_t) ends + 1, rocprim::plus<uint64_t>(), s); }));
 		HIP_CHECK(hipMemcpyAsync(&text, line_offset.as<uint64_t>() + ends, 8, hipMemcpyDeviceToHost, s));
 	}
 	HIP_CHECK(hipEventRecord(state.events[1], s));
@@ -287,23 +259,15 @@ extern "C" {
 
 int agpu_depth_begin(agpu_ctx* ctx, const uint32_t* ref_length, const char* names, const uint32_t* name_offset, uint32_t n_ref, agpu_depth_info* info) {
 	if (!ctx || !info || (n_ref > 0 && (!ref_length || !names || !name_offset))) { set_last_error("null argument"); return AGPU_ERR_INVALID; }
-	if (ctx->ingest_active) { set_last_error("agpu_depth_begin: an ingest is under way on this context (it comes behind agpu_ingest_finish)"); return AGPU_ERR_INVALID; }
-	if (ctx->depth.active) { set_last_error("agpu_depth_begin: agpu_depth_end must run first"); return AGPU_ERR_INVALID; }
-	if (ctx->last_ingest_part_of_sample) { set_last_error("a coverage track of one sample over several GPUs is not supported"); return AGPU_ERR_INVALID; }
-	const uint64_t size = ctx->last_ingest_stream_size, base = ctx->last_ingest_first_record, n = ctx->last_ingest_records;
-	DeviceBuffer& record_offset = ctx->scratch("ingest.record_offset");
-	if (!ctx->batch_from_ingest || !ctx->last_ingest_kept || ctx->ingest_stream.ptr == nullptr || record_offset.ptr == nullptr || ctx->ingest_stream.capacity < (size + 3) / 4 * 4 || record_offset.capacity < n * 8) {
-		set_last_error("agpu_depth_begin: the record stream of the last ingest is not on the device any more (it was given back under memory pressure, another ingest has begun, or there was no ingest)");
-		return AGPU_ERR_INVALID;
-	}
-	if (n >= 0xFFFFFFF0ull || base > size) { set_last_error("agpu_depth_begin: more than 2^32-16 alignment records"); return AGPU_ERR_INVALID; }
+	ResidentStream resident;
+	TRY(resident_stream(ctx, "agpu_depth_begin", "a coverage track of one sample over several GPUs is not supported", ctx->depth.active ? "agpu_depth_end must run first" : nullptr, resident));
 	if (n_ref >= 0x7FFFFFFFu) { set_last_error("agpu_depth_begin: too many references"); return AGPU_ERR_INVALID; }
 	for (uint32_t t = 0; t < n_ref; ++t) if (name_offset[t + 1] < name_offset[t]) { set_last_error("agpu_depth_begin: the offsets of the names must ascend"); return AGPU_ERR_INVALID; }
 	HIP_CHECK(hipSetDevice(ctx->device));
 	ctx->depth.active = true; // (the stream is read from here on: nothing of this context is given back when an allocation fails)
 	struct Guard { agpu_ctx* ctx; bool keep; ~Guard() { if (!keep) leave(ctx); } } guard = { ctx, false };
 	for (int k = 0; k < 2; ++k) HIP_CHECK(hipEventCreate(&ctx->depth.events[k]));
-	const int status = mark_and_scan(ctx, ref_length, names, name_offset, n_ref);
+	const int status = mark_and_scan(ctx, resident, ref_length, names, name_offset, n_ref);
 	collect_kernel_samples(ctx);
 	if (status != AGPU_OK) return status;
 	{ std::lock_guard<std::mutex> lock(ctx->profile_mutex); if (!ctx->failed_launch.empty()) { set_last_error("agpu_depth_begin: " + ctx->failed_launch); return AGPU_ERR_DEVICE; } }

@@ -16,7 +16,8 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
-#include "agpu_context.hpp"
+#define AGPU_OPTION "--gene-counts"
+#include "resident_stream.hpp"
 #include "device_utils.hpp"
 #include "genecount_core.hpp"
 
@@ -24,20 +25,7 @@ using namespace agpu;
 
 namespace {
 
-const int BLOCK = 256;
-const uint64_t LAUNCH_ITEMS = 1ull << 30; // one lane per record, launched in pieces that stay below 2^32 work-items
-
-#define HIP_CHECK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { set_last_error(std::string(#call) + ": " + hipGetErrorString(e_)); return AGPU_ERR_DEVICE; } } while (0)
-#define ALLOC(buffer, bytes) do { if (!(buffer).allocate(bytes)) { set_last_error("--gene-counts: hipMalloc failed (" #buffer ")"); return AGPU_ERR_NO_MEMORY; } } while (0)
-
-inline unsigned int grid_for(uint64_t n) { return (unsigned int) std::max<uint64_t>((n + BLOCK - 1) / BLOCK, 1); }
-
 enum { COUNT_TEMPLATES = 0, COUNT_WITHOUT_PRIMARY = 1, COUNT_ENDS = 2, COUNT_BLOCKS = 3, COUNT_WORDS = 4 }; // 64-bit words
-
-__device__ __forceinline__ unsigned long long wave_sum(unsigned long long mine) {
-	for (int offset = 32; offset > 0; offset >>= 1) mine += __shfl_down(mine, offset);
-	return mine; // (of lane 0)
-}
 
 __global__ void __launch_bounds__(BLOCK) genecount_name_kernel(const uint8_t* __restrict__ stream, uint64_t stream_size, const uint64_t* __restrict__ record_offset, uint64_t n, uint64_t first, unsigned long long* table, uint64_t slots,
 		uint32_t hash_bits, uint32_t* name_id, uint32_t* slot_first) {
@@ -92,18 +80,12 @@ template <bool LEADER> __global__ void __launch_bounds__(BLOCK) genecount_assign
 	}
 }
 
-uint32_t hash_bits_knob() {
-	const char* knob = getenv("ARRIBA_GENECOUNT_HASH_BITS");
-	if (knob == nullptr || knob[0] == 0) return 64;
-	const long bits = atol(knob);
-	return bits < 0 ? 0u : bits > 64 ? 64u : (uint32_t) bits;
-}
 bool plain_atomics_knob() { const char* knob = getenv("ARRIBA_GENECOUNT_PLAIN_ATOMICS"); return knob != nullptr && knob[0] == '1'; } // (for the measurement of DESIGN.md 4.15: one atomic per lane)
 
-int count(agpu_ctx* ctx, const uint32_t* ref_length, uint32_t n_ref, uint64_t* counts_out, hipEvent_t* events) {
+int count(agpu_ctx* ctx, const ResidentStream& resident, const uint32_t* ref_length, uint32_t n_ref, uint64_t* counts_out, hipEvent_t* events) {
 	GenecountState& state = ctx->genecount;
 	hipStream_t s = ctx->stream;
-	const uint64_t size = ctx->last_ingest_stream_size, n = ctx->last_ingest_records;
+	const uint64_t size = resident.stream_size, n = resident.records;
 	const uint64_t stride = (uint64_t) ctx->annotation.n_genes + GCOUNT_SPECIAL, words = GCOUNT_COLUMNS * stride;
 	DeviceBuffer& counts = state.buffer("genecount.counts"); DeviceBuffer& counters = state.buffer("genecount.counters");
 	ALLOC(counts, words * 8); ALLOC(counters, COUNT_WORDS * 8);
@@ -118,23 +100,22 @@ int count(agpu_ctx* ctx, const uint32_t* ref_length, uint32_t n_ref, uint64_t* c
 		if (n_ref > 0) { HIP_CHECK(hipMemcpyAsync(lengths.ptr, ref_length, (size_t) n_ref * 4, hipMemcpyHostToDevice, s)); HIP_CHECK(hipStreamSynchronize(s)); } // (the source is pageable memory of the caller)
 		HIP_CHECK(hipMemsetAsync(slot_first.ptr, 0xFF, n * 8, s));
 		HIP_CHECK(hipMemsetAsync(table.ptr, 0, slots * 8, s));
-		const uint8_t* stream = ctx->ingest_stream.as<uint8_t>();
-		const uint64_t* record_offset = ctx->scratch("ingest.record_offset").as<uint64_t>();
+		const uint8_t* stream = resident.stream;
+		const uint64_t* record_offset = resident.record_offset;
 		HIP_CHECK(hipEventRecord(events[0], s));
 		{ KernelTimer timer(ctx, "genecount_name_kernel", n * 64 + slots * 8);
-		  for (uint64_t first = 0; first < n; first += LAUNCH_ITEMS)
-			genecount_name_kernel<<<grid_for(std::min(LAUNCH_ITEMS, n - first)), BLOCK, 0, s>>>(stream, size, record_offset, n, first, table.as<unsigned long long>(), slots, hash_bits_knob(), name_id.as<uint32_t>(), slot_first.as<uint32_t>()); }
+		  for_each_launch_piece(n, [&](uint64_t first, unsigned int grid) {
+			genecount_name_kernel<<<grid, BLOCK, 0, s>>>(stream, size, record_offset, n, first, table.as<unsigned long long>(), slots, hash_bits_knob("ARRIBA_GENECOUNT_HASH_BITS"), name_id.as<uint32_t>(), slot_first.as<uint32_t>()); }); }
 		HIP_CHECK(hipEventRecord(events[1], s));
 		GcountInput in;
 		in.stream = stream; in.stream_size = size; in.record_offset = record_offset; in.ann = ctx->annotation;
 		in.tid_to_contig = ctx->ingest_tid_to_contig.as<uint32_t>(); in.ref_length = lengths.as<uint32_t>(); in.n_ref = n_ref;
 		const bool plain = plain_atomics_knob();
 		{ KernelTimer timer(ctx, "genecount_assign_kernel", n * 8 + n * 64);
-		  for (uint64_t first = 0; first < n; first += LAUNCH_ITEMS) {
-			const unsigned int grid = grid_for(std::min(LAUNCH_ITEMS, n - first));
+		  for_each_launch_piece(n, [&](uint64_t first, unsigned int grid) {
 			if (plain) genecount_assign_kernel<false><<<grid, BLOCK, 0, s>>>(in, name_id.as<uint32_t>(), slot_first.as<uint32_t>(), n, first, counts.as<unsigned long long>(), counters.as<unsigned long long>());
 			else genecount_assign_kernel<true><<<grid, BLOCK, 0, s>>>(in, name_id.as<uint32_t>(), slot_first.as<uint32_t>(), n, first, counts.as<unsigned long long>(), counters.as<unsigned long long>());
-		  } }
+		  }); }
 		HIP_CHECK(hipEventRecord(events[2], s));
 	}
 	unsigned long long host_counters[COUNT_WORDS] = {};
@@ -157,32 +138,12 @@ extern "C" {
 int agpu_gene_counts(agpu_ctx* ctx, const uint32_t* ref_length, uint32_t n_ref, uint64_t* counts, agpu_gene_count_stats* stats) {
 	if (!ctx || !counts || (n_ref > 0 && !ref_length)) { set_last_error("null argument"); return AGPU_ERR_INVALID; }
 	if (stats) memset(stats, 0, sizeof(*stats));
-	if (ctx->ingest_active) { set_last_error("agpu_gene_counts: an ingest is under way on this context (it comes behind agpu_ingest_finish)"); return AGPU_ERR_INVALID; }
-	if (ctx->last_ingest_part_of_sample) { set_last_error("gene counts of one sample over several GPUs are not supported"); return AGPU_ERR_INVALID; }
-	const uint64_t size = ctx->last_ingest_stream_size, base = ctx->last_ingest_first_record, n = ctx->last_ingest_records;
-	DeviceBuffer& record_offset = ctx->scratch("ingest.record_offset");
-	if (!ctx->batch_from_ingest || !ctx->last_ingest_kept || ctx->ingest_stream.ptr == nullptr || record_offset.ptr == nullptr || ctx->ingest_stream.capacity < (size + 3) / 4 * 4 || record_offset.capacity < n * 8) {
-		set_last_error("agpu_gene_counts: the record stream of the last ingest is not on the device any more (it was given back under memory pressure, another ingest has begun, or there was no ingest)");
-		return AGPU_ERR_INVALID;
-	}
-	if (n >= 0xFFFFFFF0ull || base > size) { set_last_error("agpu_gene_counts: more than 2^32-16 alignment records"); return AGPU_ERR_INVALID; }
-	if (!ctx->have_annotation) { set_last_error("agpu_gene_counts: agpu_upload_annotation must run first"); return AGPU_ERR_INVALID; }
-	if (n_ref != ctx->ingest_n_targets || (n_ref > 0 && ctx->ingest_tid_to_contig.ptr == nullptr)) { set_last_error("agpu_gene_counts: the lengths are not those of the references of the last ingest"); return AGPU_ERR_INVALID; }
+	ResidentStream resident;
+	TRY(resident_stream(ctx, "agpu_gene_counts", "gene counts of one sample over several GPUs are not supported", nullptr, resident, NEEDS_ANNOTATION | NEEDS_REFERENCES, n_ref));
 	HIP_CHECK(hipSetDevice(ctx->device));
 	GenecountState& state = ctx->genecount;
-	state.active = true; // (the stream is read from here on: nothing of this context is given back when an allocation fails)
 	memset(&state.stats, 0, sizeof(state.stats));
-	hipEvent_t events[3] = { nullptr, nullptr, nullptr };
-	int status = AGPU_OK;
-	for (int k = 0; k < 3 && status == AGPU_OK; ++k) if (hipEventCreate(&events[k]) != hipSuccess) { set_last_error("--gene-counts: hipEventCreate failed"); status = AGPU_ERR_DEVICE; }
-	if (status == AGPU_OK) status = count(ctx, ref_length, n_ref, counts, events);
-	if (status != AGPU_OK) (void) hipStreamSynchronize(ctx->stream); // (nothing of a failed count is in flight when its buffers go)
-	for (int k = 0; k < 3; ++k) if (events[k]) (void) hipEventDestroy(events[k]);
-	state.release_all();
-	state.active = false;
-	collect_kernel_samples(ctx);
-	if (status != AGPU_OK) return status;
-	{ std::lock_guard<std::mutex> lock(ctx->profile_mutex); if (!ctx->failed_launch.empty()) { set_last_error("agpu_gene_counts: " + ctx->failed_launch); return AGPU_ERR_DEVICE; } }
+	TRY(one_shot<3>(ctx, state, "agpu_gene_counts", [&](hipEvent_t* events) { return count(ctx, resident, ref_length, n_ref, counts, events); }, [&](int) { state.release_all(); }));
 	if (stats) *stats = state.stats;
 	return AGPU_OK;
 }

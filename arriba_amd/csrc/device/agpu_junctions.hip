@@ -20,7 +20,9 @@
 #include <cstring>
 #include <string>
 #include <rocprim/rocprim.hpp>
-#include "agpu_context.hpp"
+#define AGPU_OPTION "--splice-junctions"
+#define ALLOC(buffer, bytes) AGPU_ALLOC(buffer, bytes, state.note_peak())
+#include "resident_stream.hpp"
 #include "device_utils.hpp"
 #include "junction_core.hpp"
 
@@ -28,22 +30,9 @@ using namespace agpu;
 
 namespace {
 
-const int BLOCK = 256;
-const uint64_t LAUNCH_ITEMS = 1ull << 30; // one lane per record, launched in pieces that stay below 2^32 work-items
-
-#define HIP_CHECK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { set_last_error(std::string(#call) + ": " + hipGetErrorString(e_)); return AGPU_ERR_DEVICE; } } while (0)
-#define ALLOC(buffer, bytes) do { if (!(buffer).allocate(bytes)) { set_last_error("--splice-junctions: hipMalloc failed (" #buffer ")"); return AGPU_ERR_NO_MEMORY; } state.note_peak(); } while (0)
-#define TRY(call) do { int s_ = (call); if (s_ != AGPU_OK) return s_; } while (0)
-
-inline unsigned int grid_for(uint64_t n) { return (unsigned int) std::max<uint64_t>((n + BLOCK - 1) / BLOCK, 1); }
-
 enum { COUNT_CONTRIBUTING = 0, COUNT_PAIRS = 1, COUNT_ANNOTATED = 2, COUNT_WORDS = 4 }; // 64-bit words
 enum { PASS_COUNT = 0, PASS_NAMES = 1, PASS_EMIT = 2, PASS_ORDER = 3, PASS_CLASS = 4, PASSES = 5 };
 
-__device__ __forceinline__ unsigned int wave_sum(unsigned int mine) {
-	for (int offset = 32; offset > 0; offset >>= 1) mine += __shfl_down(mine, offset);
-	return mine; // (of lane 0)
-}
 // No lane leaves before it.
 __device__ __forceinline__ void wave_count(unsigned long long* counter, unsigned int mine) {
 	const unsigned int sum = wave_sum(mine);
@@ -176,13 +165,6 @@ __global__ void __launch_bounds__(BLOCK) junction_class_kernel(JuncRows rows, ui
 	wave_count(&counters[COUNT_ANNOTATED], annotated);
 }
 
-uint32_t hash_bits_knob() {
-	const char* knob = getenv("ARRIBA_JUNCTION_HASH_BITS");
-	if (knob == nullptr || knob[0] == 0) return 64;
-	const long bits = atol(knob);
-	return bits < 0 ? 0u : bits > 64 ? 64u : (uint32_t) bits;
-}
-
 // `count` < 2^32 items ordered by (high, low): a stable radix sort by the low word, then one by the high word gathered in that order.  order_out: the items in their order;
 // sorted_high_out: the high words in that order.  Both point into "junction.order*" / "junction.sort_out" of the state.
 int sort_by_two_words(agpu_ctx* ctx, const uint64_t* low, const uint64_t* high, unsigned int high_bits, uint64_t count, const char* what, const uint32_t*& order_out, const uint64_t*& sorted_high_out) {
@@ -208,16 +190,14 @@ int sort_by_two_words(agpu_ctx* ctx, const uint64_t* low, const uint64_t* high, 
 	return AGPU_OK;
 }
 
-unsigned int bits_of(uint64_t below) { unsigned int bits = 1; while (bits < 32 && (1ull << bits) < below) ++bits; return bits; } // enough for every value < below
-
-int find(agpu_ctx* ctx, const uint32_t* ref_length, uint32_t n_ref, hipEvent_t* events) {
+int find(agpu_ctx* ctx, const ResidentStream& resident, const uint32_t* ref_length, uint32_t n_ref, hipEvent_t* events) {
 	JunctionState& state = ctx->junction;
 	hipStream_t s = ctx->stream;
-	const uint64_t size = ctx->last_ingest_stream_size, n = ctx->last_ingest_records;
+	const uint64_t size = resident.stream_size, n = resident.records;
 	state.stats.records = n;
 	if (n == 0) { for (int k = 0; k <= PASSES; ++k) HIP_CHECK(hipEventRecord(events[k], s)); return AGPU_OK; }
-	const uint8_t* stream = ctx->ingest_stream.as<uint8_t>();
-	const uint64_t* record_offset = ctx->scratch("ingest.record_offset").as<uint64_t>();
+	const uint8_t* stream = resident.stream;
+	const uint64_t* record_offset = resident.record_offset;
 	const uint32_t* tid_to_contig = ctx->ingest_tid_to_contig.as<uint32_t>();
 	DeviceBuffer& counters = state.buffer("junction.counters"); DeviceBuffer& lengths = state.buffer("junction.ref_length"); DeviceBuffer& kept = state.buffer("junction.kept"); DeviceBuffer& place = state.buffer("junction.place");
 	DeviceBuffer& temporary_storage = state.buffer("junction.rocprim");
@@ -228,8 +208,8 @@ int find(agpu_ctx* ctx, const uint32_t* ref_length, uint32_t n_ref, hipEvent_t* 
 	// count and offsets
 	HIP_CHECK(hipEventRecord(events[0], s));
 	{ KernelTimer timer(ctx, "junction_count_kernel", n * 72);
-	  for (uint64_t first = 0; first < n; first += LAUNCH_ITEMS)
-		junction_count_kernel<<<grid_for(std::min(LAUNCH_ITEMS, n - first)), BLOCK, 0, s>>>(stream, size, record_offset, n, first, lengths.as<uint32_t>(), n_ref, kept.as<uint32_t>(), counters.as<unsigned long long>()); }
+	  for_each_launch_piece(n, [&](uint64_t first, unsigned int grid) {
+		junction_count_kernel<<<grid, BLOCK, 0, s>>>(stream, size, record_offset, n, first, lengths.as<uint32_t>(), n_ref, kept.as<uint32_t>(), counters.as<unsigned long long>()); }); }
 	{ size_t temporary = 0;
 	  HIP_CHECK(rocprim::exclusive_scan(nullptr, temporary, kept.as<uint32_t>(), place.as<uint64_t>(), (uint64_t) 0, (size_t) (n + 1), rocprim::plus<uint64_t>(), s));
 	  if (temporary > temporary_storage.capacity) ALLOC(temporary_storage, temporary);
@@ -252,8 +232,8 @@ int find(agpu_ctx* ctx, const uint32_t* ref_length, uint32_t n_ref, hipEvent_t* 
 	  ALLOC(name_id, n * 4); ALLOC(table, slots * 8);
 	  HIP_CHECK(hipMemsetAsync(table.ptr, 0, slots * 8, s));
 	  { KernelTimer timer(ctx, "junction_name_kernel", n * 64 + slots * 8);
-	    for (uint64_t first = 0; first < n; first += LAUNCH_ITEMS)
-		junction_name_kernel<<<grid_for(std::min(LAUNCH_ITEMS, n - first)), BLOCK, 0, s>>>(stream, size, record_offset, n, first, table.as<unsigned long long>(), slots, hash_bits_knob(), name_id.as<uint32_t>()); }
+	    for_each_launch_piece(n, [&](uint64_t first, unsigned int grid) {
+		junction_name_kernel<<<grid, BLOCK, 0, s>>>(stream, size, record_offset, n, first, table.as<unsigned long long>(), slots, hash_bits_knob("ARRIBA_JUNCTION_HASH_BITS"), name_id.as<uint32_t>()); }); }
 	  HIP_CHECK(hipEventRecord(events[2], s));
 	  HIP_CHECK(hipStreamSynchronize(s));
 	  table.release(); }
@@ -261,9 +241,9 @@ int find(agpu_ctx* ctx, const uint32_t* ref_length, uint32_t n_ref, hipEvent_t* 
 	DeviceBuffer& key_high = state.buffer("junction.key_high"); DeviceBuffer& key_low = state.buffer("junction.key_low"); DeviceBuffer& overhang = state.buffer("junction.overhang");
 	ALLOC(key_high, crossings * 8); ALLOC(key_low, crossings * 8); ALLOC(overhang, crossings * 4);
 	{ KernelTimer timer(ctx, "junction_emit_kernel", n * 84 + crossings * 20);
-	  for (uint64_t first = 0; first < n; first += LAUNCH_ITEMS)
-		junction_emit_kernel<<<grid_for(std::min(LAUNCH_ITEMS, n - first)), BLOCK, 0, s>>>(stream, size, record_offset, n, first, lengths.as<uint32_t>(), n_ref, kept.as<uint32_t>(), place.as<uint64_t>(), name_id.as<uint32_t>(),
-		                                                                                     key_high.as<uint64_t>(), key_low.as<uint64_t>(), overhang.as<uint32_t>()); }
+	  for_each_launch_piece(n, [&](uint64_t first, unsigned int grid) {
+		junction_emit_kernel<<<grid, BLOCK, 0, s>>>(stream, size, record_offset, n, first, lengths.as<uint32_t>(), n_ref, kept.as<uint32_t>(), place.as<uint64_t>(), name_id.as<uint32_t>(), key_high.as<uint64_t>(), key_low.as<uint64_t>(),
+		                                            overhang.as<uint32_t>()); }); }
 	HIP_CHECK(hipEventRecord(events[3], s));
 	HIP_CHECK(hipStreamSynchronize(s));
 	kept.release(); place.release(); name_id.release();
@@ -295,8 +275,8 @@ int find(agpu_ctx* ctx, const uint32_t* ref_length, uint32_t n_ref, hipEvent_t* 
 	HIP_CHECK(hipMemsetAsync(row_counts.ptr, 0, n_rows * 12, s));
 	const JuncRows rows = { row_high.as<uint64_t>(), row_end.as<uint32_t>(), row_counts.as<uint32_t>(), row_counts.as<uint32_t>() + n_rows, row_counts.as<uint32_t>() + 2 * n_rows };
 	{ KernelTimer timer(ctx, "junction_reduce_kernel", crossings * 24);
-	  for (uint64_t first = 0; first < crossings; first += LAUNCH_ITEMS)
-		junction_reduce_kernel<<<grid_for(std::min(LAUNCH_ITEMS, crossings - first)), BLOCK, 0, s>>>(sorted_high, sorted_low.as<uint64_t>(), sorted_overhang.as<uint32_t>(), row_of.as<uint32_t>(), crossings, first, rows, counters.as<unsigned long long>()); }
+	  for_each_launch_piece(crossings, [&](uint64_t first, unsigned int grid) {
+		junction_reduce_kernel<<<grid, BLOCK, 0, s>>>(sorted_high, sorted_low.as<uint64_t>(), sorted_overhang.as<uint32_t>(), row_of.as<uint32_t>(), crossings, first, rows, counters.as<unsigned long long>()); }); }
 	HIP_CHECK(hipEventRecord(events[4], s));
 	HIP_CHECK(hipStreamSynchronize(s));
 	row_of.release();
@@ -336,36 +316,19 @@ int agpu_splice_junctions(agpu_ctx* ctx, const uint32_t* ref_length, uint32_t n_
 	if (!ctx || !rows || !n_rows || (n_ref > 0 && !ref_length)) { set_last_error("null argument"); return AGPU_ERR_INVALID; }
 	*rows = nullptr; *n_rows = 0;
 	if (stats) memset(stats, 0, sizeof(*stats));
-	if (ctx->ingest_active) { set_last_error("agpu_splice_junctions: an ingest is under way on this context (it comes behind agpu_ingest_finish)"); return AGPU_ERR_INVALID; }
-	if (ctx->last_ingest_part_of_sample) { set_last_error("splice junctions of one sample over several GPUs are not supported"); return AGPU_ERR_INVALID; }
-	const uint64_t size = ctx->last_ingest_stream_size, base = ctx->last_ingest_first_record, n = ctx->last_ingest_records;
-	DeviceBuffer& record_offset = ctx->scratch("ingest.record_offset");
-	if (!ctx->batch_from_ingest || !ctx->last_ingest_kept || ctx->ingest_stream.ptr == nullptr || record_offset.ptr == nullptr || ctx->ingest_stream.capacity < (size + 3) / 4 * 4 || record_offset.capacity < n * 8) {
-		set_last_error("agpu_splice_junctions: the record stream of the last ingest is not on the device any more (it was given back under memory pressure, another ingest has begun, or there was no ingest)");
-		return AGPU_ERR_INVALID;
-	}
-	if (n >= 0xFFFFFFF0ull || base > size) { set_last_error("agpu_splice_junctions: more than 2^32-16 alignment records"); return AGPU_ERR_INVALID; }
-	if (!ctx->have_annotation) { set_last_error("agpu_splice_junctions: agpu_upload_annotation must run first"); return AGPU_ERR_INVALID; }
-	if (!ctx->have_genome) { set_last_error("agpu_splice_junctions: agpu_upload_genome must run first"); return AGPU_ERR_INVALID; }
-	if (n_ref != ctx->ingest_n_targets || (n_ref > 0 && ctx->ingest_tid_to_contig.ptr == nullptr)) { set_last_error("agpu_splice_junctions: the lengths are not those of the references of the last ingest"); return AGPU_ERR_INVALID; }
+	ResidentStream resident;
+	TRY(resident_stream(ctx, "agpu_splice_junctions", "splice junctions of one sample over several GPUs are not supported", nullptr, resident, NEEDS_ANNOTATION | NEEDS_GENOME | NEEDS_REFERENCES, n_ref));
 	HIP_CHECK(hipSetDevice(ctx->device));
 	JunctionState& state = ctx->junction;
-	state.active = true; // (the stream is read from here on: nothing of this context is given back when an allocation fails)
 	memset(&state.stats, 0, sizeof(state.stats));
 	state.rows.clear(); state.peak = 0;
-	hipEvent_t events[PASSES + 1] = {};
-	int status = AGPU_OK;
-	for (int k = 0; k <= PASSES && status == AGPU_OK; ++k) if (hipEventCreate(&events[k]) != hipSuccess) { set_last_error("--splice-junctions: hipEventCreate failed"); status = AGPU_ERR_DEVICE; }
-	if (status == AGPU_OK) status = find(ctx, ref_length, n_ref, events);
-	(void) hipStreamSynchronize(ctx->stream); // (nothing of a failed call is in flight when its buffers go; the events of a call without crossings have happened)
-	if (status == AGPU_OK) for (int k = 0; k < PASSES; ++k) { float ms = 0; if (hipEventElapsedTime(&ms, events[k], events[k + 1]) == hipSuccess) state.stats.seconds[k] = ms / 1000.0; }
-	for (int k = 0; k <= PASSES; ++k) if (events[k]) (void) hipEventDestroy(events[k]);
-	state.stats.peak_bytes = state.peak;
-	state.release_all();
-	state.active = false;
-	collect_kernel_samples(ctx);
+	const int status = one_shot<PASSES + 1>(ctx, state, "agpu_splice_junctions", [&](hipEvent_t* events) {
+		const int found = find(ctx, resident, ref_length, n_ref, events);
+		(void) hipStreamSynchronize(ctx->stream); // (the events of a call without crossings have happened)
+		if (found == AGPU_OK) for (int k = 0; k < PASSES; ++k) { float ms = 0; if (hipEventElapsedTime(&ms, events[k], events[k + 1]) == hipSuccess) state.stats.seconds[k] = ms / 1000.0; }
+		return found;
+	}, [&](int) { state.stats.peak_bytes = state.peak; state.release_all(); });
 	if (status != AGPU_OK) { state.rows.clear(); return status; }
-	{ std::lock_guard<std::mutex> lock(ctx->profile_mutex); if (!ctx->failed_launch.empty()) { state.rows.clear(); set_last_error("agpu_splice_junctions: " + ctx->failed_launch); return AGPU_ERR_DEVICE; } }
 	*rows = state.rows.data(); *n_rows = state.rows.size();
 	if (stats) *stats = state.stats;
 	return AGPU_OK;

@@ -17,22 +17,14 @@
 #include <cstring>
 #include <string>
 #include <rocprim/rocprim.hpp>
-#include "agpu_context.hpp"
+#define AGPU_OPTION "--mark-duplicates"
+#include "resident_stream.hpp"
 #include "device_utils.hpp"
 #include "markdup_core.hpp"
 
 using namespace agpu;
 
 namespace {
-
-const int BLOCK = 256;
-const uint64_t LAUNCH_ITEMS = 1ull << 30; // one lane per slot: two slots per record, launched in pieces that stay below 2^32 work-items
-
-#define HIP_CHECK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { set_last_error(std::string(#call) + ": " + hipGetErrorString(e_)); return AGPU_ERR_DEVICE; } } while (0)
-#define ALLOC(buffer, bytes) do { if (!(buffer).allocate(bytes)) { set_last_error("--mark-duplicates: hipMalloc failed (" #buffer ")"); return AGPU_ERR_NO_MEMORY; } } while (0)
-#define TRY(call) do { int s_ = (call); if (s_ != AGPU_OK) return s_; } while (0)
-
-inline unsigned int grid_for(uint64_t n) { return (unsigned int) std::max<uint64_t>((n + BLOCK - 1) / BLOCK, 1); }
 
 enum { COUNT_TEMPLATES = 0, COUNT_PAIRS = 1, COUNT_ENTRIES = 2, COUNT_DUPLICATE_PAIRS = 3, COUNT_DUPLICATE_FRAGMENTS = 4, COUNT_FLAGGED = 5, COUNT_CHANGED = 6, COUNT_WORDS = 8 }; // 64-bit words
 
@@ -154,13 +146,6 @@ __global__ void __launch_bounds__(BLOCK) markdup_flag_kernel(const uint32_t* __r
 	wave_count(&counters[COUNT_CHANGED], changed);
 }
 
-uint32_t hash_bits_knob() {
-	const char* knob = getenv("ARRIBA_MARKDUP_HASH_BITS");
-	if (knob == nullptr || knob[0] == 0) return 64;
-	const long bits = atol(knob);
-	return bits < 0 ? 0u : bits > 64 ? 64u : (uint32_t) bits;
-}
-
 struct SortWord { const uint64_t* words; unsigned int end_bit; };
 
 // `count` items ordered by their words, words[0] the least significant: one stable radix sort per word over (the word gathered in the order so far, the order).  order_out: the
@@ -185,12 +170,12 @@ int sort_by_words(agpu_ctx* ctx, const SortWord* words, int n_words, uint64_t co
 	return AGPU_OK;
 }
 
-int find(agpu_ctx* ctx, hipEvent_t* events) {
+int find(agpu_ctx* ctx, const ResidentStream& resident, hipEvent_t* events) {
 	MarkdupState& state = ctx->markdup;
 	hipStream_t s = ctx->stream;
-	const uint64_t size = ctx->last_ingest_stream_size, n = ctx->last_ingest_records;
-	const uint8_t* stream = ctx->ingest_stream.as<uint8_t>();
-	const uint64_t* record_offset = ctx->scratch("ingest.record_offset").as<uint64_t>();
+	const uint64_t size = resident.stream_size, n = resident.records;
+	const uint8_t* stream = resident.stream;
+	const uint64_t* record_offset = resident.record_offset;
 	uint64_t peak = 0;
 	DeviceBuffer& flag = state.buffer("markdup.flag");
 	ALLOC(flag, std::max<uint64_t>(n, 1));
@@ -207,7 +192,7 @@ int find(agpu_ctx* ctx, hipEvent_t* events) {
 		HIP_CHECK(hipMemsetAsync(table.ptr, 0, slots * 8, s));
 		peak = std::max(peak, state.allocated());
 		{ KernelTimer timer(ctx, "markdup_name_kernel", n * 64 + slots * 8);
-		  markdup_name_kernel<<<grid_for(n), BLOCK, 0, s>>>(stream, size, record_offset, n, table.as<unsigned long long>(), slots, hash_bits_knob(), name_id.as<uint32_t>(), slot_first.as<uint32_t>(), flag.as<uint8_t>()); }
+		  markdup_name_kernel<<<grid_for(n), BLOCK, 0, s>>>(stream, size, record_offset, n, table.as<unsigned long long>(), slots, hash_bits_knob("ARRIBA_MARKDUP_HASH_BITS"), name_id.as<uint32_t>(), slot_first.as<uint32_t>(), flag.as<uint8_t>()); }
 		HIP_CHECK(hipEventRecord(events[1], s));
 		HIP_CHECK(hipStreamSynchronize(s));
 		table.release();
@@ -215,8 +200,8 @@ int find(agpu_ctx* ctx, hipEvent_t* events) {
 	DeviceBuffer& end_key = state.buffer("markdup.end_key"); DeviceBuffer& end_score = state.buffer("markdup.end_score");
 	ALLOC(end_key, n * 16); ALLOC(end_score, n * 8);
 	{ KernelTimer timer(ctx, "markdup_end_kernel", n * 24 + size / 2);
-	  for (uint64_t first = 0; first < 2 * n; first += LAUNCH_ITEMS)
-		markdup_end_kernel<<<grid_for(std::min(LAUNCH_ITEMS, 2 * n - first)), BLOCK, 0, s>>>(stream, size, record_offset, slot_first.as<uint32_t>(), 2 * n, first, end_key.as<uint64_t>(), end_score.as<uint32_t>()); }
+	  for_each_launch_piece(2 * n, [&](uint64_t first, unsigned int grid) { // (one lane per slot: two slots per record)
+		markdup_end_kernel<<<grid, BLOCK, 0, s>>>(stream, size, record_offset, slot_first.as<uint32_t>(), 2 * n, first, end_key.as<uint64_t>(), end_score.as<uint32_t>()); }); }
 	HIP_CHECK(hipEventRecord(events[2], s));
 	// pairs and fragments: a pair has two records of its own and a fragment one, so there are at most n / 2 pairs and n entries
 	const uint64_t pair_room = n / 2 + 1, entry_room = n + 1;
@@ -273,12 +258,12 @@ int find(agpu_ctx* ctx, hipEvent_t* events) {
 
 namespace agpu {
 
-int markdup_find(agpu_ctx* ctx) {
+int markdup_find(agpu_ctx* ctx, const ResidentStream& stream) {
 	MarkdupState& state = ctx->markdup;
 	memset(&state.counts, 0, sizeof(state.counts));
 	hipEvent_t events[4] = { nullptr, nullptr, nullptr, nullptr };
 	for (int k = 0; k < 4; ++k) if (hipEventCreate(&events[k]) != hipSuccess) { for (int j = 0; j < k; ++j) (void) hipEventDestroy(events[j]); set_last_error("--mark-duplicates: hipEventCreate failed"); return AGPU_ERR_DEVICE; }
-	const int status = find(ctx, events);
+	const int status = find(ctx, stream, events);
 	if (status != AGPU_OK) (void) hipStreamSynchronize(ctx->stream); // (nothing of a failed search is in flight when its buffers go)
 	for (int k = 0; k < 4; ++k) (void) hipEventDestroy(events[k]);
 	if (status == AGPU_OK) state.release_all_but("markdup.flag"); else state.release_all();

@@ -19,7 +19,8 @@
 #include <cstring>
 #include <string>
 #include <rocprim/rocprim.hpp>
-#include "agpu_context.hpp"
+#define AGPU_OPTION "--realign-reads"
+#include "resident_stream.hpp"
 #include "device_utils.hpp"
 #include "realign_core.hpp"
 
@@ -27,15 +28,7 @@ using namespace agpu;
 
 namespace {
 
-const int BLOCK = 256;
-const uint64_t LAUNCH_ITEMS = 1ull << 30;          // one lane per record, launched in pieces that stay below 2^32 work-items
 const uint64_t DEFAULT_TEXT_WINDOW = 16ull << 20;  // bytes of a staging window
-
-#define HIP_CHECK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { set_last_error(std::string(#call) + ": " + hipGetErrorString(e_)); return AGPU_ERR_DEVICE; } } while (0)
-#define ALLOC(buffer, bytes) do { if (!(buffer).allocate(bytes)) { set_last_error("--realign-reads: hipMalloc failed (" #buffer ")"); return AGPU_ERR_NO_MEMORY; } } while (0)
-#define TRY(call) do { int s_ = (call); if (s_ != AGPU_OK) return s_; } while (0)
-
-inline unsigned int grid_for(uint64_t n) { return (unsigned int) std::max<uint64_t>((n + BLOCK - 1) / BLOCK, 1); }
 
 enum { COUNT_TEMPLATES = 0, COUNT_REALIGN = 1, COUNT_KEPT = 2, COUNT_ORPHANS = 3, COUNT_DROPPED = 4, COUNT_EXTRA = 5, COUNT_PLACEHOLDER = 6, COUNT_MALFORMED = 7, COUNT_REALIGN_BYTES = 8, COUNT_KEPT_BYTES = 9,
        COUNT_WORDS = 10 }; // 64-bit words
@@ -46,11 +39,6 @@ struct RealignInput {
 	const uint8_t* in_assembly; RealignNames names;
 	bool paired;
 };
-
-__device__ __forceinline__ unsigned long long wave_sum(unsigned long long mine) {
-	for (int offset = 32; offset > 0; offset >>= 1) mine += __shfl_down(mine, offset);
-	return mine; // (of lane 0)
-}
 
 // records [first, upto)
 __global__ void __launch_bounds__(BLOCK) realign_name_kernel(const uint8_t* __restrict__ stream, uint64_t stream_size, const uint64_t* __restrict__ record_offset, uint64_t first, uint64_t upto, unsigned long long* table, uint64_t slots,
@@ -171,29 +159,6 @@ template <bool WAVE> __global__ void __launch_bounds__(BLOCK) realign_text_kerne
 	}
 }
 
-uint64_t knob_of(const char* name, uint64_t otherwise, uint64_t most) {
-	const char* knob = getenv(name);
-	uint64_t value = otherwise;
-	if (knob != nullptr && knob[0] != 0) value = std::max<uint64_t>(strtoull(knob, nullptr, 10), 1);
-	return std::min(value, most);
-}
-uint32_t hash_bits_knob() {
-	const char* knob = getenv("ARRIBA_REALIGN_HASH_BITS");
-	if (knob == nullptr || knob[0] == 0) return 64;
-	const long bits = atol(knob);
-	return bits < 0 ? 0u : bits > 64 ? 64u : (uint32_t) bits;
-}
-
-template <class Call> int with_temporary(agpu_ctx* ctx, const char* name, uint64_t bytes, Call call) {
-	DeviceBuffer& temporary_buffer = ctx->realign.buffer("realign.rocprim");
-	size_t temporary = 0;
-	HIP_CHECK(call(nullptr, temporary));
-	if (temporary > temporary_buffer.capacity) ALLOC(temporary_buffer, temporary);
-	KernelTimer timer(ctx, name, bytes);
-	HIP_CHECK(call(temporary_buffer.ptr, temporary));
-	return AGPU_OK;
-}
-
 void note_peak(RealignState& state) { state.stats.peak_bytes = std::max<uint64_t>(state.stats.peak_bytes, state.allocated()); }
 // behind a hipStreamSynchronize: the milliseconds between the two events of the state go to seconds[part]
 void add_seconds(RealignState& state, int part) { float ms = 0; if (hipEventElapsedTime(&ms, state.events[0], state.events[1]) == hipSuccess) state.stats.seconds[part] += ms / 1000.0; }
@@ -201,7 +166,7 @@ void add_seconds(RealignState& state, int part) { float ms = 0; if (hipEventElap
 RealignInput input_of(agpu_ctx* ctx) {
 	RealignState& state = ctx->realign;
 	RealignInput in;
-	in.stream = ctx->ingest_stream.as<uint8_t>(); in.stream_size = ctx->last_ingest_stream_size; in.record_offset = ctx->scratch("ingest.record_offset").as<uint64_t>(); in.n = state.records;
+	in.stream = state.stream.stream; in.stream_size = state.stream.stream_size; in.record_offset = state.stream.record_offset; in.n = state.records;
 	in.in_assembly = state.buffer("realign.in_assembly").as<uint8_t>();
 	in.names.names = state.buffer("realign.names").as<char>(); in.names.name_offset = state.buffer("realign.name_offset").as<uint32_t>(); in.names.n_ref = state.n_ref;
 	in.paired = state.paired;
@@ -212,9 +177,9 @@ RealignInput input_of(agpu_ctx* ctx) {
 int split(agpu_ctx* ctx, const uint8_t* in_assembly, const char* names, const uint32_t* name_offset, uint32_t n_ref) {
 	hipStream_t s = ctx->stream;
 	RealignState& state = ctx->realign;
-	const uint64_t size = ctx->last_ingest_stream_size, n = ctx->last_ingest_records, name_bytes = n_ref > 0 ? name_offset[n_ref] : 0;
-	const uint8_t* stream = ctx->ingest_stream.as<uint8_t>();
-	const uint64_t* record_offset = ctx->scratch("ingest.record_offset").as<uint64_t>();
+	const uint64_t size = state.stream.stream_size, n = state.stream.records, name_bytes = n_ref > 0 ? name_offset[n_ref] : 0;
+	const uint8_t* stream = state.stream.stream;
+	const uint64_t* record_offset = state.stream.record_offset;
 	state.records = n; state.n_ref = n_ref; state.paired = false;
 	state.window = knob_of("ARRIBA_REALIGN_TEXT_WINDOW", DEFAULT_TEXT_WINDOW, 1ull << 31);
 	state.launch_items = (knob_of("ARRIBA_REALIGN_LAUNCH_ITEMS", LAUNCH_ITEMS, LAUNCH_ITEMS) + BLOCK - 1) / BLOCK * BLOCK; // (whole blocks: no record is visited twice)
@@ -261,7 +226,7 @@ int split(agpu_ctx* ctx, const uint8_t* in_assembly, const char* names, const ui
 		KernelTimer timer(ctx, "realign_name_kernel", n * 64 + slots * 8);
 		for (uint64_t first = 0; first < n; first += state.launch_items) {
 			const uint64_t upto = std::min(n, first + state.launch_items);
-			realign_name_kernel<<<grid_for(upto - first), BLOCK, 0, s>>>(stream, size, record_offset, first, upto, table.as<unsigned long long>(), slots, hash_bits_knob(), name_id.as<uint32_t>(), slot_first.as<uint32_t>());
+			realign_name_kernel<<<grid_for(upto - first), BLOCK, 0, s>>>(stream, size, record_offset, first, upto, table.as<unsigned long long>(), slots, hash_bits_knob("ARRIBA_REALIGN_HASH_BITS"), name_id.as<uint32_t>(), slot_first.as<uint32_t>());
 		}
 	}
 	HIP_CHECK(hipEventRecord(state.events[1], s));
@@ -287,8 +252,8 @@ int split(agpu_ctx* ctx, const uint8_t* in_assembly, const char* names, const ui
 	if (host_counters[COUNT_MALFORMED] != 0) { set_last_error("agpu_realign_begin: failed to load alignments (a record is cut short, has no name or names a reference the header does not have)"); return AGPU_ERR_INVALID; }
 	// the scans
 	HIP_CHECK(hipEventRecord(state.events[0], s));
-	TRY(with_temporary(ctx, "realign rocprim::exclusive_scan(realign bytes)", (n + 1) * 12, [&](void* t, size_t& b) { return rocprim::exclusive_scan(t, b, length_realign.as<uint32_t>(), offset_realign.as<uint64_t>(), (uint64_t) 0, (size_t) n + 1, rocprim::plus<uint64_t>(), s); }));
-	if (state.want_kept) TRY(with_temporary(ctx, "realign rocprim::exclusive_scan(kept bytes)", (n + 1) * 12, [&](void* t, size_t& b) { return rocprim::exclusive_scan(t, b, length_kept.as<uint32_t>(), offset_kept.as<uint64_t>(), (uint64_t) 0, (size_t) n + 1, rocprim::plus<uint64_t>(), s); }));
+	TRY(with_temporary(ctx, state.buffer("realign.rocprim"), "realign rocprim::exclusive_scan(realign bytes)", (n + 1) * 12, [&](void* t, size_t& b) { return rocprim::exclusive_scan(t, b, length_realign.as<uint32_t>(), offset_realign.as<uint64_t>(), (uint64_t) 0, (size_t) n + 1, rocprim::plus<uint64_t>(), s); }));
+	if (state.want_kept) TRY(with_temporary(ctx, state.buffer("realign.rocprim"), "realign rocprim::exclusive_scan(kept bytes)", (n + 1) * 12, [&](void* t, size_t& b) { return rocprim::exclusive_scan(t, b, length_kept.as<uint32_t>(), offset_kept.as<uint64_t>(), (uint64_t) 0, (size_t) n + 1, rocprim::plus<uint64_t>(), s); }));
 	note_peak(state);
 	uint64_t totals[2] = { 0, 0 };
 	HIP_CHECK(hipMemcpyAsync(&totals[0], offset_realign.as<uint64_t>() + n, 8, hipMemcpyDeviceToHost, s));
@@ -322,21 +287,13 @@ extern "C" {
 int agpu_realign_begin(agpu_ctx* ctx, const uint8_t* in_assembly, const char* names, const uint32_t* name_offset, uint32_t n_ref, int want_kept, agpu_realign_info* info) {
 	if (!ctx || !info || (n_ref > 0 && (!in_assembly || !names || !name_offset))) { set_last_error("null argument"); return AGPU_ERR_INVALID; }
 	memset(info, 0, sizeof(*info));
-	if (ctx->ingest_active) { set_last_error("agpu_realign_begin: an ingest is under way on this context (it comes behind agpu_ingest_finish)"); return AGPU_ERR_INVALID; }
-	if (ctx->realign.active) { set_last_error("agpu_realign_begin: agpu_realign_end must run first"); return AGPU_ERR_INVALID; }
-	if (ctx->last_ingest_part_of_sample) { set_last_error("a split for realignment of one sample over several GPUs is not supported"); return AGPU_ERR_INVALID; }
-	const uint64_t size = ctx->last_ingest_stream_size, base = ctx->last_ingest_first_record, n = ctx->last_ingest_records;
-	DeviceBuffer& record_offset = ctx->scratch("ingest.record_offset");
-	if (!ctx->batch_from_ingest || !ctx->last_ingest_kept || ctx->ingest_stream.ptr == nullptr || record_offset.ptr == nullptr || ctx->ingest_stream.capacity < (size + 3) / 4 * 4 || record_offset.capacity < n * 8) {
-		set_last_error("agpu_realign_begin: the record stream of the last ingest is not on the device any more (it was given back under memory pressure, another ingest has begun, or there was no ingest)");
-		return AGPU_ERR_INVALID;
-	}
-	if (n >= 0xFFFFFFF0ull || base > size) { set_last_error("agpu_realign_begin: more than 2^32-16 alignment records"); return AGPU_ERR_INVALID; }
+	ResidentStream resident;
+	TRY(resident_stream(ctx, "agpu_realign_begin", "a split for realignment of one sample over several GPUs is not supported", ctx->realign.active ? "agpu_realign_end must run first" : nullptr, resident));
 	if (n_ref != ctx->ingest_n_targets) { set_last_error("agpu_realign_begin: the references are not those of the header of the last ingest"); return AGPU_ERR_INVALID; }
 	for (uint32_t t = 0; t < n_ref; ++t) if (name_offset[t + 1] < name_offset[t]) { set_last_error("agpu_realign_begin: the offsets of the names must ascend"); return AGPU_ERR_INVALID; }
 	HIP_CHECK(hipSetDevice(ctx->device));
 	ctx->realign.active = true; // (the stream is read from here on: nothing of this context is given back when an allocation fails)
-	ctx->realign.want_kept = want_kept != 0;
+	ctx->realign.want_kept = want_kept != 0; ctx->realign.stream = resident;
 	struct Guard { agpu_ctx* ctx; bool keep; ~Guard() { if (!keep) leave(ctx); } } guard = { ctx, false };
 	for (int k = 0; k < 2; ++k) HIP_CHECK(hipEventCreate(&ctx->realign.events[k]));
 	const int status = split(ctx, in_assembly, names, name_offset, n_ref);

@@ -12,7 +12,8 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
-#include "agpu_context.hpp"
+#define AGPU_OPTION "--rna-metrics"
+#include "resident_stream.hpp"
 #include "device_utils.hpp"
 #include "rnametrics_core.hpp"
 
@@ -20,17 +21,8 @@ using namespace agpu;
 
 namespace {
 
-const int BLOCK = 256;
 const uint64_t LAUNCH_RECORDS = 1ull << 30; // the records of one launch: its grid stays far below 2^30 work-items
 const unsigned int BLOCKS_PER_CU = 4;       // persistent workgroups: what the registers of the kernel let a CU hold (3 wavefronts per SIMD), and one more to fill in behind the first that is done
-
-#define HIP_CHECK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { set_last_error(std::string(#call) + ": " + hipGetErrorString(e_)); return AGPU_ERR_DEVICE; } } while (0)
-#define ALLOC(buffer, bytes) do { if (!(buffer).allocate(bytes)) { set_last_error("--rna-metrics: hipMalloc failed (" #buffer ")"); return AGPU_ERR_NO_MEMORY; } } while (0)
-
-__device__ __forceinline__ unsigned long long wave_sum(unsigned long long mine) {
-	for (int offset = 32; offset > 0; offset >>= 1) mine += __shfl_down(mine, offset);
-	return mine; // (of lane 0)
-}
 
 // the three histograms of a counter block in LDS or in global memory: 64-bit atomics either way
 struct AtomicBins {
@@ -57,7 +49,7 @@ template <bool PLAIN> __global__ void __launch_bounds__(BLOCK) rnametrics_record
 		return;
 	}
 	AGPU_UNROLL for (int k = 0; k < RNAM_SCALARS; ++k) { // (no lane has left: the shuffles see the whole wavefront)
-		const unsigned long long sum = wave_sum(lane.c[k]);
+		const unsigned long long sum = wave_sum((unsigned long long) lane.c[k]);
 		if ((threadIdx.x & 63u) == 0 && sum != 0) atomicAdd(&shared[k], sum);
 	}
 	__syncthreads();
@@ -71,7 +63,6 @@ template <class T> int upload(DeviceBuffer& buffer, const T* from, size_t n, hip
 	if (n > 0) HIP_CHECK(hipMemcpyAsync(buffer.ptr, from, n * sizeof(T), hipMemcpyHostToDevice, s));
 	return AGPU_OK;
 }
-#define TRY(call) do { const int status_ = (call); if (status_ != AGPU_OK) return status_; } while (0)
 
 // the track on the device: copied when the context sees its id for the first time
 int bring_track(agpu_ctx* ctx, const agpu_region_track* track) {
@@ -103,10 +94,10 @@ bool track_is_sound(const agpu_region_track* track) {
 	return true;
 }
 
-int count(agpu_ctx* ctx, const agpu_region_track* track, const uint32_t* ref_length, uint32_t n_ref, uint64_t* counters_out, hipEvent_t* events) {
+int count(agpu_ctx* ctx, const ResidentStream& resident, const agpu_region_track* track, const uint32_t* ref_length, uint32_t n_ref, uint64_t* counters_out, hipEvent_t* events) {
 	RnametricsState& state = ctx->rnametrics;
 	hipStream_t s = ctx->stream;
-	const uint64_t size = ctx->last_ingest_stream_size, n = ctx->last_ingest_records;
+	const uint64_t size = resident.stream_size, n = resident.records;
 	TRY(bring_track(ctx, track));
 	DeviceBuffer& counters = state.buffer("rnametrics.counters"); DeviceBuffer& lengths = state.buffer("rnametrics.ref_length");
 	ALLOC(counters, RNAM_WORDS * 8); ALLOC(lengths, std::max<size_t>(n_ref, 1) * 4);
@@ -119,9 +110,9 @@ int count(agpu_ctx* ctx, const agpu_region_track* track, const uint32_t* ref_len
 		HIP_CHECK(hipDeviceGetAttribute(&compute_units, hipDeviceAttributeMultiprocessorCount, ctx->device));
 		const uint64_t persistent = (uint64_t) std::max(compute_units, 1) * BLOCKS_PER_CU;
 		RnamInput in;
-		in.stream = ctx->ingest_stream.as<uint8_t>(); in.stream_size = size; in.track = state.track;
+		in.stream = resident.stream; in.stream_size = size; in.track = state.track;
 		in.tid_to_contig = ctx->ingest_tid_to_contig.as<uint32_t>(); in.ref_length = lengths.as<uint32_t>(); in.n_ref = n_ref;
-		const uint64_t* record_offset = ctx->scratch("ingest.record_offset").as<uint64_t>();
+		const uint64_t* record_offset = resident.record_offset;
 		const bool plain = plain_atomics_knob();
 		KernelTimer timer(ctx, "rnametrics_record_kernel", n * 8 + n * 72);
 		for (uint64_t first = 0; first < n; first += LAUNCH_RECORDS) {
@@ -151,33 +142,16 @@ extern "C" {
 int agpu_rna_metrics(agpu_ctx* ctx, const agpu_region_track* track, const uint32_t* ref_length, uint32_t n_ref, uint64_t* counters, agpu_rna_metrics_stats* stats) {
 	if (!ctx || !track || !counters || (n_ref > 0 && !ref_length)) { set_last_error("null argument"); return AGPU_ERR_INVALID; }
 	if (stats) memset(stats, 0, sizeof(*stats));
-	if (ctx->ingest_active) { set_last_error("agpu_rna_metrics: an ingest is under way on this context (it comes behind agpu_ingest_finish)"); return AGPU_ERR_INVALID; }
-	if (ctx->last_ingest_part_of_sample) { set_last_error("rna metrics of one sample over several GPUs are not supported"); return AGPU_ERR_INVALID; }
-	const uint64_t size = ctx->last_ingest_stream_size, base = ctx->last_ingest_first_record, n = ctx->last_ingest_records;
-	DeviceBuffer& record_offset = ctx->scratch("ingest.record_offset");
-	if (!ctx->batch_from_ingest || !ctx->last_ingest_kept || ctx->ingest_stream.ptr == nullptr || record_offset.ptr == nullptr || ctx->ingest_stream.capacity < (size + 3) / 4 * 4 || record_offset.capacity < n * 8) {
-		set_last_error("agpu_rna_metrics: the record stream of the last ingest is not on the device any more (it was given back under memory pressure, another ingest has begun, or there was no ingest)");
-		return AGPU_ERR_INVALID;
-	}
-	if (n >= 0xFFFFFFF0ull || base > size) { set_last_error("agpu_rna_metrics: more than 2^32-16 alignment records"); return AGPU_ERR_INVALID; }
-	if (n_ref != ctx->ingest_n_targets || (n_ref > 0 && ctx->ingest_tid_to_contig.ptr == nullptr)) { set_last_error("agpu_rna_metrics: the lengths are not those of the references of the last ingest"); return AGPU_ERR_INVALID; }
+	ResidentStream resident;
+	TRY(resident_stream(ctx, "agpu_rna_metrics", "rna metrics of one sample over several GPUs are not supported", nullptr, resident, NEEDS_REFERENCES, n_ref));
 	if (!track_is_sound(track)) { set_last_error("agpu_rna_metrics: the region track is not one ahost_region_track built (a contig without a run, starts that do not ascend from 0, or no id)"); return AGPU_ERR_INVALID; }
 	HIP_CHECK(hipSetDevice(ctx->device));
 	RnametricsState& state = ctx->rnametrics;
-	state.active = true; // (the stream is read from here on: nothing of this context is given back when an allocation fails)
 	memset(&state.stats, 0, sizeof(state.stats));
-	hipEvent_t events[2] = { nullptr, nullptr };
-	int status = AGPU_OK;
-	for (int k = 0; k < 2 && status == AGPU_OK; ++k) if (hipEventCreate(&events[k]) != hipSuccess) { set_last_error("--rna-metrics: hipEventCreate failed"); status = AGPU_ERR_DEVICE; }
-	if (status == AGPU_OK) status = count(ctx, track, ref_length, n_ref, counters, events);
-	if (status != AGPU_OK) (void) hipStreamSynchronize(ctx->stream); // (nothing of a failed count is in flight when its buffers go)
-	for (int k = 0; k < 2; ++k) if (events[k]) (void) hipEventDestroy(events[k]);
-	state.buffer("rnametrics.counters").release(); state.buffer("rnametrics.ref_length").release();
-	if (status != AGPU_OK && state.track_id == 0) state.release_all(); // (a track that did not arrive whole)
-	state.active = false;
-	collect_kernel_samples(ctx);
-	if (status != AGPU_OK) return status;
-	{ std::lock_guard<std::mutex> lock(ctx->profile_mutex); if (!ctx->failed_launch.empty()) { set_last_error("agpu_rna_metrics: " + ctx->failed_launch); return AGPU_ERR_DEVICE; } }
+	TRY(one_shot<2>(ctx, state, "agpu_rna_metrics", [&](hipEvent_t* events) { return count(ctx, resident, track, ref_length, n_ref, counters, events); }, [&](int status) {
+		state.buffer("rnametrics.counters").release(); state.buffer("rnametrics.ref_length").release();
+		if (status != AGPU_OK && state.track_id == 0) state.release_all(); // (a track that did not arrive whole)
+	}));
 	if (stats) *stats = state.stats;
 	return AGPU_OK;
 }

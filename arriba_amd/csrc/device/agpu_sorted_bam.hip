@@ -17,7 +17,9 @@
 #include <cstring>
 #include <string>
 #include <rocprim/rocprim.hpp>
-#include "agpu_context.hpp"
+#define AGPU_OPTION "--sorted-bam"
+#define AGPU_ALLOC_MESSAGE(buffer) "hipMalloc failed (" buffer ")"
+#include "resident_stream.hpp"
 #include "crc32_core.hpp"
 #include "deflate_out_core.hpp"
 #include "markdup_core.hpp"
@@ -29,16 +31,9 @@ using namespace agpu;
 
 namespace {
 
-const int BLOCK = 256;
 const int GATHER_THREADS = SBAM_GATHER_THREADS; // (the frame of a block and the copy of a record: sorted_bam_device.hpp, shared with agpu_supporting.hip)
 const uint32_t GATHER_BATCH = 512;        // records whose source and destination are looked up together
 const uint64_t DEFAULT_WINDOW_BYTES = 256ull << 20;
-
-#define HIP_CHECK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { set_last_error(std::string(#call) + ": " + hipGetErrorString(e_)); return AGPU_ERR_DEVICE; } } while (0)
-#define ALLOC(buffer, bytes) do { if (!(buffer).allocate(bytes)) { set_last_error("hipMalloc failed (" #buffer ")"); return AGPU_ERR_NO_MEMORY; } } while (0)
-#define TRY(call) do { int s_ = (call); if (s_ != AGPU_OK) return s_; } while (0)
-
-inline unsigned int grid_for(uint64_t n) { return (unsigned int) std::max<uint64_t>((n + BLOCK - 1) / BLOCK, 1); }
 
 // end_flag: the end coordinate (0 .. 2^29), bit 31: the record is unmapped (flag 0x4)
 __global__ void __launch_bounds__(BLOCK) sorted_bam_key_kernel(const uint8_t* stream, uint64_t stream_size, const uint64_t* record_offset, uint64_t n, uint64_t* keys, uint32_t* sizes, uint32_t* end_flag) {
@@ -397,7 +392,7 @@ int launch_gather(agpu_ctx* ctx, uint64_t first_block) {
 	const uint8_t* const duplicate = ctx->markdup.on ? ctx->markdup.buffer("markdup.flag").as<uint8_t>() : nullptr; // (--mark-duplicates off: the kernels do what they did without it)
 	if (ctx->sorted_bam_level == 0) {
 		KernelTimer timer(ctx, "sorted_bam_gather_kernel", 2 * bytes + blocks * (SBAM_HEAD + SBAM_TAIL));
-		sorted_bam_gather_kernel<<<(unsigned int) blocks, GATHER_THREADS, 0, ctx->stream>>>(ctx->ingest_stream.as<uint8_t>(), ctx->scratch("ingest.record_offset").as<uint64_t>(), ctx->scratch("sortedbam.order").as<uint32_t>(),
+		sorted_bam_gather_kernel<<<(unsigned int) blocks, GATHER_THREADS, 0, ctx->stream>>>(ctx->sorted_bam_stream.stream, ctx->sorted_bam_stream.record_offset, ctx->scratch("sortedbam.order").as<uint32_t>(),
 			ctx->scratch("sortedbam.out_offset").as<uint64_t>(), ctx->scratch("sortedbam.block_first").as<uint32_t>(), ctx->sorted_bam_records, ctx->sorted_bam_bytes, ctx->sorted_bam_blocks, first_block,
 			ctx->scratch("sortedbam.crc_tables").as<Crc32Tables>(), ctx->scratch("sortedbam.staging").as<uint8_t>(), duplicate);
 	} else { // compressed blocks into their staging slots, their sizes scanned, the blocks packed
@@ -405,7 +400,7 @@ int launch_gather(agpu_ctx* ctx, uint64_t first_block) {
 		DeviceBuffer& block_bytes = ctx->scratch("sortedbam.block_bytes"); DeviceBuffer& window_offset = ctx->scratch("sortedbam.window_offset"); DeviceBuffer& rocprim_scratch = ctx->scratch("sortedbam.rocprim");
 		{ KernelTimer timer(ctx, "sorted_bam_deflate_kernel", 2 * bytes);
 		  for (uint64_t done = 0; done < blocks; done += DEFLATE_GRID)
-		  sorted_bam_deflate_kernel<<<(unsigned int) std::min<uint64_t>(blocks - done, DEFLATE_GRID), GATHER_THREADS, 0, s>>>(ctx->ingest_stream.as<uint8_t>(), ctx->scratch("ingest.record_offset").as<uint64_t>(), ctx->scratch("sortedbam.order").as<uint32_t>(),
+		  sorted_bam_deflate_kernel<<<(unsigned int) std::min<uint64_t>(blocks - done, DEFLATE_GRID), GATHER_THREADS, 0, s>>>(ctx->sorted_bam_stream.stream, ctx->sorted_bam_stream.record_offset, ctx->scratch("sortedbam.order").as<uint32_t>(),
 			ctx->scratch("sortedbam.out_offset").as<uint64_t>(), ctx->scratch("sortedbam.block_first").as<uint32_t>(), ctx->sorted_bam_records, ctx->sorted_bam_bytes, ctx->sorted_bam_blocks, first_block, (uint32_t) done,
 			ctx->scratch("sortedbam.crc_tables").as<Crc32Tables>(), ctx->scratch("sortedbam.staging").as<uint8_t>(), ctx->scratch("sortedbam.tokens").as<uint32_t>(), block_bytes.as<uint32_t>(), duplicate); }
 		size_t temporary = 0;
@@ -502,23 +497,16 @@ extern "C" {
 
 int agpu_sorted_bam_begin(agpu_ctx* ctx, agpu_sorted_bam_info* info) {
 	if (!ctx || !info) { set_last_error("null argument"); return AGPU_ERR_INVALID; }
-	if (ctx->ingest_active) { set_last_error("agpu_sorted_bam_begin: an ingest is under way on this context (it comes behind agpu_ingest_finish)"); return AGPU_ERR_INVALID; }
-	if (ctx->sorted_bam_active) { set_last_error("agpu_sorted_bam_begin: agpu_sorted_bam_end must run first"); return AGPU_ERR_INVALID; }
-	if (ctx->last_ingest_part_of_sample) { set_last_error("a sorted BAM file of one sample over several GPUs is not supported"); return AGPU_ERR_INVALID; }
-	const uint64_t size = ctx->last_ingest_stream_size, base = ctx->last_ingest_first_record, n = ctx->last_ingest_records;
-	DeviceBuffer& record_offset = ctx->scratch("ingest.record_offset");
-	if (!ctx->batch_from_ingest || !ctx->last_ingest_kept || ctx->ingest_stream.ptr == nullptr || record_offset.ptr == nullptr || ctx->ingest_stream.capacity < (size + 3) / 4 * 4 || record_offset.capacity < n * 8) {
-		set_last_error("agpu_sorted_bam_begin: the record stream of the last ingest is not on the device any more (it was given back under memory pressure, another ingest has begun, or there was no ingest)");
-		return AGPU_ERR_INVALID;
-	}
-	if (n >= 0xFFFFFFF0ull || base > size) { set_last_error("agpu_sorted_bam_begin: more than 2^32-16 alignment records"); return AGPU_ERR_INVALID; }
+	ResidentStream& resident = ctx->sorted_bam_stream;
+	TRY(resident_stream(ctx, "agpu_sorted_bam_begin", "a sorted BAM file of one sample over several GPUs is not supported", ctx->sorted_bam_active ? "agpu_sorted_bam_end must run first" : nullptr, resident));
+	const uint64_t size = resident.stream_size, base = resident.first_record, n = resident.records;
 	HIP_CHECK(hipSetDevice(ctx->device));
 	hipStream_t s = ctx->stream;
 	ctx->sorted_bam_active = true; // (from here on nothing of this context is given back when an allocation fails: DeviceBuffer::release_idle_buffers)
 	struct Guard { agpu_ctx* ctx; bool keep; ~Guard() { if (!keep) { ctx->sorted_bam_active = false; ctx->markdup.on = false; ctx->markdup.release_all(); } } } guard = { ctx, false };
 	// --mark-duplicates: one byte per record, found now -- its working buffers are gone before those of the file are allocated, so the two peaks do not add
 	const bool mark_duplicates = ctx->markdup.next;
-	if (mark_duplicates) TRY(markdup_find(ctx));
+	if (mark_duplicates) TRY(markdup_find(ctx, resident));
 	const uint64_t bytes = size - base, n_blocks = sbam_block_count(bytes);
 	uint64_t window_bytes = DEFAULT_WINDOW_BYTES;
 	{ const char* knob = getenv("ARRIBA_SORTED_BAM_WINDOW"); if (knob != nullptr && knob[0] != 0) window_bytes = strtoull(knob, nullptr, 10); }
@@ -546,7 +534,7 @@ int agpu_sorted_bam_begin(agpu_ctx* ctx, agpu_sorted_bam_info* info) {
 	uint64_t total = 0;
 	if (n > 0) {
 		{ KernelTimer timer(ctx, "sorted_bam_key_kernel", n * 24 + bytes / 4);
-		  sorted_bam_key_kernel<<<grid_for(n), BLOCK, 0, s>>>(ctx->ingest_stream.as<uint8_t>(), size, record_offset.as<uint64_t>(), n, keys.as<uint64_t>(), sizes.as<uint32_t>(), end_flag.as<uint32_t>()); }
+		  sorted_bam_key_kernel<<<grid_for(n), BLOCK, 0, s>>>(resident.stream, size, resident.record_offset, n, keys.as<uint64_t>(), sizes.as<uint32_t>(), end_flag.as<uint32_t>()); }
 		size_t temporary = 0;
 		HIP_CHECK(rocprim::radix_sort_pairs(nullptr, temporary, keys.as<uint64_t>(), keys_sorted.as<uint64_t>(), rocprim::counting_iterator<uint32_t>(0), order.as<uint32_t>(), (size_t) n, 0, 64, s));
 		if (temporary > rocprim_scratch.capacity) ALLOC(rocprim_scratch, temporary);

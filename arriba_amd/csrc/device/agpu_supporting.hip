@@ -21,7 +21,9 @@
 #include <cstring>
 #include <string>
 #include <rocprim/rocprim.hpp>
-#include "agpu_context.hpp"
+#define AGPU_OPTION "--supporting-alignments"
+#define AGPU_ALLOC_MESSAGE(buffer) "hipMalloc failed (" buffer "): the pool of " AGPU_OPTION " does not fit the device"
+#include "resident_stream.hpp"
 #include "crc32_core.hpp"
 #include "supporting_core.hpp"
 #include "sorted_bam_device.hpp"
@@ -30,16 +32,9 @@ using namespace agpu;
 
 namespace {
 
-const int BLOCK = 256;
 const int GATHER_THREADS = SBAM_GATHER_THREADS;
 const uint32_t GATHER_BATCH = 512;        // records whose source and destination are looked up together
 const uint64_t DEFAULT_WINDOW_BYTES = 64ull << 20;
-
-#define HIP_CHECK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { set_last_error(std::string(#call) + ": " + hipGetErrorString(e_)); return AGPU_ERR_DEVICE; } } while (0)
-#define ALLOC(buffer, bytes) do { if (!(buffer).allocate(bytes)) { set_last_error("hipMalloc failed (" #buffer "): the pool of --supporting-alignments does not fit the device"); return AGPU_ERR_NO_MEMORY; } } while (0)
-#define TRY(call) do { int s_ = (call); if (s_ != AGPU_OK) return s_; } while (0)
-
-inline unsigned int grid_for(uint64_t n) { return (unsigned int) std::max<uint64_t>((n + BLOCK - 1) / BLOCK, 1); }
 
 // ---- phase 1: the pool ----
 
@@ -218,17 +213,6 @@ __global__ void __launch_bounds__(BLOCK) supporting_index_kernel(const uint64_t*
 	begin[e] = sbam_voffset(first_block_file_offset, emission_offset[e] - row_byte[row]); end[e] = sbam_voffset(first_block_file_offset, emission_offset[e + 1] - row_byte[row]);
 }
 
-// rocPRIM calls with their temporary storage in "support.tmp.rocprim"
-template <class Call> int with_temporary(agpu_ctx* ctx, const char* name, uint64_t bytes, Call call) {
-	DeviceBuffer& temporary_buffer = ctx->support.buffer("support.tmp.rocprim");
-	size_t temporary = 0;
-	HIP_CHECK(call(nullptr, temporary));
-	if (temporary > temporary_buffer.capacity) ALLOC(temporary_buffer, temporary);
-	KernelTimer timer(ctx, name, bytes);
-	HIP_CHECK(call(temporary_buffer.ptr, temporary));
-	return AGPU_OK;
-}
-
 uint32_t hash_bits_knob() {
 	const char* knob = getenv("ARRIBA_SUPPORT_HASH_BITS");
 	if (knob == nullptr || knob[0] == 0) return 64;
@@ -262,16 +246,9 @@ extern "C" {
 
 int agpu_support_pool_build(agpu_ctx* ctx, const char* names, const uint64_t* name_offset, uint64_t n_names, agpu_support_pool_info* info) {
 	if (!ctx || !info || (names != nullptr && n_names > 0 && !name_offset)) { set_last_error("null argument"); return AGPU_ERR_INVALID; }
-	if (ctx->ingest_active) { set_last_error("agpu_support_pool_build: an ingest is under way on this context (it comes behind agpu_ingest_finish)"); return AGPU_ERR_INVALID; }
-	if (ctx->support.active) { set_last_error("agpu_support_pool_build: agpu_supporting_end must run first"); return AGPU_ERR_INVALID; }
-	if (ctx->last_ingest_part_of_sample) { set_last_error("supporting alignments of one sample over several GPUs are not supported"); return AGPU_ERR_INVALID; }
-	const uint64_t size = ctx->last_ingest_stream_size, base = ctx->last_ingest_first_record, n = ctx->last_ingest_records;
-	DeviceBuffer& record_offset = ctx->scratch("ingest.record_offset");
-	if (!ctx->batch_from_ingest || !ctx->last_ingest_kept || ctx->ingest_stream.ptr == nullptr || record_offset.ptr == nullptr || ctx->ingest_stream.capacity < (size + 3) / 4 * 4 || record_offset.capacity < n * 8) {
-		set_last_error("agpu_support_pool_build: the record stream of the last ingest is not on the device any more (it was given back under memory pressure, another ingest has begun, or there was no ingest)");
-		return AGPU_ERR_INVALID;
-	}
-	if (n >= 0xFFFFFFF0ull || base > size) { set_last_error("agpu_support_pool_build: more than 2^32-16 alignment records"); return AGPU_ERR_INVALID; }
+	ResidentStream resident;
+	TRY(resident_stream(ctx, "agpu_support_pool_build", "supporting alignments of one sample over several GPUs are not supported", ctx->support.active ? "agpu_supporting_end must run first" : nullptr, resident));
+	const uint64_t size = resident.stream_size, base = resident.first_record, n = resident.records;
 	const bool of_batch = names == nullptr;
 	if (of_batch) { if (!ctx->have_batch) { set_last_error("agpu_support_pool_build: no batch whose names could be taken"); return AGPU_ERR_INVALID; } n_names = ctx->n; }
 	if (n_names >= SUPPORT_MAX_NAMES) { set_last_error("agpu_support_pool_build: too many names"); return AGPU_ERR_INVALID; }
@@ -304,9 +281,9 @@ int agpu_support_pool_build(agpu_ctx* ctx, const char* names, const uint64_t* na
 	DeviceBuffer& marked = state.buffer("support.tmp.marked"); DeviceBuffer& compact_index = state.buffer("support.tmp.compact_index");
 	ALLOC(keys, room * 8); ALLOC(sizes, room * 4); ALLOC(end_flag, room * 4); ALLOC(record_name, room * 4); ALLOC(marked, (room + 1) * 4); ALLOC(compact_index, (room + 1) * 4);
 	{ KernelTimer timer(ctx, "support_mark_kernel", n * 28 + (size - base) / 4);
-	  support_mark_kernel<<<grid_for(n + 1), BLOCK, 0, s>>>(ctx->ingest_stream.as<uint8_t>(), size, record_offset.as<uint64_t>(), n, view, table.as<unsigned long long>(), state.table_slots, state.hash_bits,
+	  support_mark_kernel<<<grid_for(n + 1), BLOCK, 0, s>>>(resident.stream, size, resident.record_offset, n, view, table.as<unsigned long long>(), state.table_slots, state.hash_bits,
 		keys.as<uint64_t>(), sizes.as<uint32_t>(), end_flag.as<uint32_t>(), record_name.as<uint32_t>(), marked.as<uint32_t>()); }
-	TRY(with_temporary(ctx, "support rocprim::exclusive_scan(marks)", n * 8, [&](void* t, size_t& b) { return rocprim::exclusive_scan(t, b, marked.as<uint32_t>(), compact_index.as<uint32_t>(), 0u, (size_t) n + 1, rocprim::plus<uint32_t>(), s); }));
+	TRY(with_temporary(ctx, state.buffer("support.tmp.rocprim"), "support rocprim::exclusive_scan(marks)", n * 8, [&](void* t, size_t& b) { return rocprim::exclusive_scan(t, b, marked.as<uint32_t>(), compact_index.as<uint32_t>(), 0u, (size_t) n + 1, rocprim::plus<uint32_t>(), s); }));
 	uint32_t m32 = 0;
 	HIP_CHECK(hipMemcpyAsync(&m32, compact_index.as<uint32_t>() + n, 4, hipMemcpyDeviceToHost, s));
 	HIP_CHECK(hipStreamSynchronize(s));
@@ -323,18 +300,18 @@ int agpu_support_pool_build(agpu_ctx* ctx, const char* names, const uint64_t* na
 	if (m > 0) {
 		{ KernelTimer timer(ctx, "support_compact_kernel", n * 8 + m * 12);
 		  support_compact_kernel<<<grid_for(n), BLOCK, 0, s>>>(marked.as<uint32_t>(), compact_index.as<uint32_t>(), keys.as<uint64_t>(), n, compact_keys.as<uint64_t>(), compact_record.as<uint32_t>()); }
-		TRY(with_temporary(ctx, "support rocprim::radix_sort_pairs(pool)", m * 24, [&](void* t, size_t& b) { return rocprim::radix_sort_pairs(t, b, compact_keys.as<uint64_t>(), keys_sorted.as<uint64_t>(), compact_record.as<uint32_t>(), record_sorted.as<uint32_t>(), (size_t) m, 0, 64, s); }));
+		TRY(with_temporary(ctx, state.buffer("support.tmp.rocprim"), "support rocprim::radix_sort_pairs(pool)", m * 24, [&](void* t, size_t& b) { return rocprim::radix_sort_pairs(t, b, compact_keys.as<uint64_t>(), keys_sorted.as<uint64_t>(), compact_record.as<uint32_t>(), record_sorted.as<uint32_t>(), (size_t) m, 0, 64, s); }));
 		{ KernelTimer timer(ctx, "support_meta_kernel", m * 48);
-		  support_meta_kernel<<<grid_for(m + 1), BLOCK, 0, s>>>(keys_sorted.as<uint64_t>(), record_sorted.as<uint32_t>(), m, record_offset.as<uint64_t>(), sizes.as<uint32_t>(), end_flag.as<uint32_t>(), record_name.as<uint32_t>(),
+		  support_meta_kernel<<<grid_for(m + 1), BLOCK, 0, s>>>(keys_sorted.as<uint64_t>(), record_sorted.as<uint32_t>(), m, resident.record_offset, sizes.as<uint32_t>(), end_flag.as<uint32_t>(), record_name.as<uint32_t>(),
 			pool_size.as<uint32_t>(), pool_source.as<uint64_t>(), pool_ref.as<int32_t>(), pool_pos.as<int32_t>(), pool_end_flag.as<uint32_t>(), pool_name.as<uint32_t>()); }
-		TRY(with_temporary(ctx, "support rocprim::exclusive_scan(pool sizes)", m * 12, [&](void* t, size_t& b) { return rocprim::exclusive_scan(t, b, pool_size.as<uint32_t>(), pool_offset.as<uint64_t>(), (uint64_t) 0, (size_t) m + 1, rocprim::plus<uint64_t>(), s); }));
+		TRY(with_temporary(ctx, state.buffer("support.tmp.rocprim"), "support rocprim::exclusive_scan(pool sizes)", m * 12, [&](void* t, size_t& b) { return rocprim::exclusive_scan(t, b, pool_size.as<uint32_t>(), pool_offset.as<uint64_t>(), (uint64_t) 0, (size_t) m + 1, rocprim::plus<uint64_t>(), s); }));
 		HIP_CHECK(hipMemcpyAsync(&total, pool_offset.as<uint64_t>() + m, 8, hipMemcpyDeviceToHost, s));
 		HIP_CHECK(hipStreamSynchronize(s));
 		if (total > size - base) { set_last_error("agpu_support_pool_build: the pooled records are larger than the stream"); return AGPU_ERR_INVALID; }
 	} else { HIP_CHECK(hipMemsetAsync(pool_offset.ptr, 0, 8, s)); HIP_CHECK(hipMemsetAsync(pool_size.ptr, 0, 4, s)); }
 	ALLOC(pool, (total + 3) / 4 * 4 + 16);
 	if (m > 0) { KernelTimer timer(ctx, "support_pool_copy_kernel", 2 * total + m * 24);
-	  support_pool_copy_kernel<<<(unsigned int) ((m + BLOCK / 64 - 1) / (BLOCK / 64)), BLOCK, 0, s>>>(ctx->ingest_stream.as<uint8_t>(), pool_source.as<uint64_t>(), pool_offset.as<uint64_t>(), m, pool.as<uint8_t>()); }
+	  support_pool_copy_kernel<<<(unsigned int) ((m + BLOCK / 64 - 1) / (BLOCK / 64)), BLOCK, 0, s>>>(resident.stream, pool_source.as<uint64_t>(), pool_offset.as<uint64_t>(), m, pool.as<uint8_t>()); }
 	HIP_CHECK(hipStreamSynchronize(s));
 	HIP_CHECK(hipGetLastError());
 	state.records = m; state.bytes = total; state.built = true;
@@ -394,11 +371,11 @@ int agpu_supporting_begin(agpu_ctx* ctx, const agpu_supporting_rows* rows, int64
 	if (n_entries > 0 && m > 0) {
 		{ KernelTimer timer(ctx, "support_pair_kernel", n_entries * 20);
 		  support_pair_kernel<<<grid_for(n_entries), BLOCK, 0, s>>>(entry_name_d.as<uint32_t>(), entry_row_d.as<uint32_t>(), n_entries, state.buffer("support.name_id").as<uint32_t>(), pairs.as<uint64_t>()); }
-		TRY(with_temporary(ctx, "support rocprim::radix_sort_keys(pairs)", n_entries * 16, [&](void* t, size_t& b) { return rocprim::radix_sort_keys(t, b, pairs.as<uint64_t>(), pairs_sorted.as<uint64_t>(), (size_t) n_entries, 0, 64, s); }));
+		TRY(with_temporary(ctx, state.buffer("support.tmp.rocprim"), "support rocprim::radix_sort_keys(pairs)", n_entries * 16, [&](void* t, size_t& b) { return rocprim::radix_sort_keys(t, b, pairs.as<uint64_t>(), pairs_sorted.as<uint64_t>(), (size_t) n_entries, 0, 64, s); }));
 		ALLOC(counts, (pool_room + 1) * 4); ALLOC(offsets, (pool_room + 1) * 8);
 		{ KernelTimer timer(ctx, "support_join_kernel(count)", m * 20);
 		  support_join_kernel<false><<<grid_for(m + 1), BLOCK, 0, s>>>(pairs_sorted.as<uint64_t>(), n_entries, row_ref.as<int32_t>(), row_breakpoint.as<int32_t>(), window, pool_ref, pool_pos, pool_end_flag, pool_name, m, counts.as<uint32_t>(), nullptr, nullptr); }
-		TRY(with_temporary(ctx, "support rocprim::exclusive_scan(emissions)", m * 12, [&](void* t, size_t& b) { return rocprim::exclusive_scan(t, b, counts.as<uint32_t>(), offsets.as<uint64_t>(), (uint64_t) 0, (size_t) m + 1, rocprim::plus<uint64_t>(), s); }));
+		TRY(with_temporary(ctx, state.buffer("support.tmp.rocprim"), "support rocprim::exclusive_scan(emissions)", m * 12, [&](void* t, size_t& b) { return rocprim::exclusive_scan(t, b, counts.as<uint32_t>(), offsets.as<uint64_t>(), (uint64_t) 0, (size_t) m + 1, rocprim::plus<uint64_t>(), s); }));
 		HIP_CHECK(hipMemcpyAsync(&n_emissions, offsets.as<uint64_t>() + m, 8, hipMemcpyDeviceToHost, s));
 		HIP_CHECK(hipStreamSynchronize(s));
 		if (n_emissions >= 0xFFFFFFF0ull) { set_last_error("agpu_supporting_begin: more than 2^32-16 records in the files of the rows"); return AGPU_ERR_INVALID; }
@@ -410,10 +387,10 @@ int agpu_supporting_begin(agpu_ctx* ctx, const agpu_supporting_rows* rows, int64
 		ALLOC(unsorted, emission_room * 8); ALLOC(sizes, (emission_room + 1) * 4);
 		{ KernelTimer timer(ctx, "support_join_kernel(emit)", m * 28 + n_emissions * 8);
 		  support_join_kernel<true><<<grid_for(m + 1), BLOCK, 0, s>>>(pairs_sorted.as<uint64_t>(), n_entries, row_ref.as<int32_t>(), row_breakpoint.as<int32_t>(), window, pool_ref, pool_pos, pool_end_flag, pool_name, m, nullptr, offsets.as<uint64_t>(), unsorted.as<uint64_t>()); }
-		TRY(with_temporary(ctx, "support rocprim::radix_sort_keys(emissions)", n_emissions * 16, [&](void* t, size_t& b) { return rocprim::radix_sort_keys(t, b, unsorted.as<uint64_t>(), emissions.as<uint64_t>(), (size_t) n_emissions, 0, 64, s); }));
+		TRY(with_temporary(ctx, state.buffer("support.tmp.rocprim"), "support rocprim::radix_sort_keys(emissions)", n_emissions * 16, [&](void* t, size_t& b) { return rocprim::radix_sort_keys(t, b, unsorted.as<uint64_t>(), emissions.as<uint64_t>(), (size_t) n_emissions, 0, 64, s); }));
 		{ KernelTimer timer(ctx, "support_emission_size_kernel", n_emissions * 16);
 		  support_emission_size_kernel<<<grid_for(n_emissions + 1), BLOCK, 0, s>>>(emissions.as<uint64_t>(), n_emissions, state.buffer("support.pool_size").as<uint32_t>(), sizes.as<uint32_t>()); }
-		TRY(with_temporary(ctx, "support rocprim::exclusive_scan(emission sizes)", n_emissions * 12, [&](void* t, size_t& b) { return rocprim::exclusive_scan(t, b, sizes.as<uint32_t>(), emission_offset.as<uint64_t>(), (uint64_t) 0, (size_t) n_emissions + 1, rocprim::plus<uint64_t>(), s); }));
+		TRY(with_temporary(ctx, state.buffer("support.tmp.rocprim"), "support rocprim::exclusive_scan(emission sizes)", n_emissions * 12, [&](void* t, size_t& b) { return rocprim::exclusive_scan(t, b, sizes.as<uint32_t>(), emission_offset.as<uint64_t>(), (uint64_t) 0, (size_t) n_emissions + 1, rocprim::plus<uint64_t>(), s); }));
 	} else HIP_CHECK(hipMemsetAsync(emission_offset.ptr, 0, 8, s));
 	// where the rows begin: records, bytes, blocks, framed bytes
 	DeviceBuffer& row_first = state.buffer("support.files.row_first"); DeviceBuffer& row_byte = state.buffer("support.files.row_byte"); DeviceBuffer& row_block_begin = state.buffer("support.files.row_block_begin"); DeviceBuffer& row_out_offset = state.buffer("support.files.row_out_offset");

@@ -16,7 +16,8 @@
 #include <string>
 #include <vector>
 #include <rocprim/rocprim.hpp>
-#include "agpu_context.hpp"
+#define AGPU_OPTION "--virus-expression"
+#include "resident_stream.hpp"
 #include "device_utils.hpp"
 #include "virus_core.hpp"
 
@@ -24,14 +25,7 @@ using namespace agpu;
 
 namespace {
 
-const int BLOCK = 256;
 const uint64_t DEFAULT_KMER_WINDOW = 1ull << 25; // keys of one emission: 256 MiB
-
-#define HIP_CHECK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { set_last_error(std::string(#call) + ": " + hipGetErrorString(e_)); return AGPU_ERR_DEVICE; } } while (0)
-#define ALLOC(buffer, bytes) do { if (!(buffer).allocate(bytes)) { set_last_error("--virus-expression: hipMalloc failed (" #buffer ")"); return AGPU_ERR_NO_MEMORY; } } while (0)
-#define TRY(call) do { int s_ = (call); if (s_ != AGPU_OK) return s_; } while (0)
-
-inline unsigned int grid_for(uint64_t n) { return (unsigned int) std::max<uint64_t>((n + BLOCK - 1) / BLOCK, 1); }
 
 enum { COUNTER_TOTAL = 0, COUNTER_CANDIDATES = 1, COUNTER_WORDS = 2 }; // 64-bit words; the cursor of the candidates is the low half of its word
 
@@ -143,22 +137,12 @@ __global__ void __launch_bounds__(BLOCK) virus_covered_kernel(const uint32_t* __
 	if (lane == 0) covered[v] = bits;
 }
 
-template <class Call> int with_temporary(agpu_ctx* ctx, const char* name, uint64_t bytes, Call call) {
-	DeviceBuffer& temporary_buffer = ctx->virus.buffer("virus.rocprim");
-	size_t temporary = 0;
-	HIP_CHECK(call(nullptr, temporary));
-	if (temporary > temporary_buffer.capacity) ALLOC(temporary_buffer, temporary);
-	KernelTimer timer(ctx, name, bytes);
-	HIP_CHECK(call(temporary_buffer.ptr, temporary));
-	return AGPU_OK;
-}
-
-int run(agpu_ctx* ctx, const int32_t* viral_ref, const uint32_t* viral_length, uint32_t n_viruses, uint32_t n_ref, agpu_virus_counters* out, hipEvent_t* marks, uint64_t& peak) {
+int run(agpu_ctx* ctx, const ResidentStream& resident, const int32_t* viral_ref, const uint32_t* viral_length, uint32_t n_viruses, uint32_t n_ref, agpu_virus_counters* out, hipEvent_t* marks, uint64_t& peak) {
 	hipStream_t s = ctx->stream;
 	VirusState& state = ctx->virus;
-	const uint64_t size = ctx->last_ingest_stream_size, n = ctx->last_ingest_records;
-	const uint8_t* stream = ctx->ingest_stream.as<uint8_t>();
-	const uint64_t* record_offset = ctx->scratch("ingest.record_offset").as<uint64_t>();
+	const uint64_t size = resident.stream_size, n = resident.records;
+	const uint8_t* stream = resident.stream;
+	const uint64_t* record_offset = resident.record_offset;
 	uint64_t window = DEFAULT_KMER_WINDOW;
 	{ const char* knob = getenv("ARRIBA_VIRUS_KMER_WINDOW"); if (knob != nullptr && knob[0] != 0) window = std::max<uint64_t>(strtoull(knob, nullptr, 10), 1); }
 	window = std::min<uint64_t>(window, 1ull << 31);
@@ -205,7 +189,7 @@ int run(agpu_ctx* ctx, const int32_t* viral_ref, const uint32_t* viral_length, u
 		{ KernelTimer timer(ctx, "virus_candidate_kernel", m * 128);
 		  virus_candidate_kernel<<<grid_for(m + 1), BLOCK, 0, s>>>(stream, size, record_offset, candidates.as<uint32_t>(), m, slot_of_ref.as<uint32_t>(), lengths.as<uint32_t>(), bitmap_offset.as<uint64_t>(), bitmap.as<uint32_t>(), reads,
 			kmers.as<uint32_t>(), candidate_seq.as<uint64_t>(), candidate_slot.as<uint32_t>()); }
-		TRY(with_temporary(ctx, "virus rocprim::exclusive_scan(k-mers)", m * 12, [&](void* t, size_t& b) { return rocprim::exclusive_scan(t, b, kmers.as<uint32_t>(), kmer_offset.as<uint64_t>(), (uint64_t) 0, (size_t) m + 1, rocprim::plus<uint64_t>(), s); }));
+		TRY(with_temporary(ctx, state.buffer("virus.rocprim"), "virus rocprim::exclusive_scan(k-mers)", m * 12, [&](void* t, size_t& b) { return rocprim::exclusive_scan(t, b, kmers.as<uint32_t>(), kmer_offset.as<uint64_t>(), (uint64_t) 0, (size_t) m + 1, rocprim::plus<uint64_t>(), s); }));
 		HIP_CHECK(hipMemcpyAsync(&all_keys, kmer_offset.as<uint64_t>() + m, 8, hipMemcpyDeviceToHost, s));
 	}
 	state.reads.assign(n_viruses, 0);
@@ -235,11 +219,11 @@ int run(agpu_ctx* ctx, const int32_t* viral_ref, const uint32_t* viral_length, u
 		}
 		{ KernelTimer timer(ctx, "virus_kmer_emit_kernel", count * 24);
 		  virus_kmer_emit_kernel<<<grid_for(count), BLOCK, 0, s>>>(stream, kmer_offset.as<uint64_t>(), m, candidate_seq.as<uint64_t>(), candidate_slot.as<uint32_t>(), first, count, work.as<uint64_t>() + distinct); }
-		TRY(with_temporary(ctx, "virus rocprim::radix_sort_keys(k-mers)", held * 16, [&](void* t, size_t& b) { return rocprim::radix_sort_keys(t, b, work.as<uint64_t>(), sorted.as<uint64_t>(), (size_t) held, 0, 64, s); }));
+		TRY(with_temporary(ctx, state.buffer("virus.rocprim"), "virus rocprim::radix_sort_keys(k-mers)", held * 16, [&](void* t, size_t& b) { return rocprim::radix_sort_keys(t, b, work.as<uint64_t>(), sorted.as<uint64_t>(), (size_t) held, 0, 64, s); }));
 		note();
 		{ KernelTimer timer(ctx, "virus_head_kernel", held * 12);
 		  virus_head_kernel<<<grid_for(held + 1), BLOCK, 0, s>>>(sorted.as<uint64_t>(), held, heads.as<uint32_t>()); }
-		TRY(with_temporary(ctx, "virus rocprim::exclusive_scan(heads)", held * 12, [&](void* t, size_t& b) { return rocprim::exclusive_scan(t, b, heads.as<uint32_t>(), place.as<uint64_t>(), (uint64_t) 0, (size_t) held + 1, rocprim::plus<uint64_t>(), s); }));
+		TRY(with_temporary(ctx, state.buffer("virus.rocprim"), "virus rocprim::exclusive_scan(heads)", held * 12, [&](void* t, size_t& b) { return rocprim::exclusive_scan(t, b, heads.as<uint32_t>(), place.as<uint64_t>(), (uint64_t) 0, (size_t) held + 1, rocprim::plus<uint64_t>(), s); }));
 		{ KernelTimer timer(ctx, "virus_compact_kernel", held * 28);
 		  virus_compact_kernel<<<grid_for(held), BLOCK, 0, s>>>(sorted.as<uint64_t>(), heads.as<uint32_t>(), place.as<uint64_t>(), held, work.as<uint64_t>()); }
 		HIP_CHECK(hipMemcpyAsync(&distinct, place.as<uint64_t>() + held, 8, hipMemcpyDeviceToHost, s));
@@ -291,23 +275,15 @@ int agpu_virus_expression(agpu_ctx* ctx, const int32_t* viral_ref, const uint32_
 	if (n_viruses > VIRUS_MAX_SLOTS) { set_last_error("--virus-expression: " + std::to_string(n_viruses) + " viral contigs, more than the 65535 that a k-mer key can name"); return AGPU_ERR_INVALID; }
 	for (uint32_t v = 0; v < n_viruses; ++v)
 		if (viral_ref[v] < 0 || (uint32_t) viral_ref[v] >= n_ref || (v > 0 && viral_ref[v] <= viral_ref[v - 1])) { set_last_error("agpu_virus_expression: the viral refIDs must ascend and lie below n_ref"); return AGPU_ERR_INVALID; }
-	if (ctx->ingest_active) { set_last_error("agpu_virus_expression: an ingest is under way on this context (it comes behind agpu_ingest_finish)"); return AGPU_ERR_INVALID; }
-	if (ctx->virus.active) { set_last_error("agpu_virus_expression: a call is under way on this context"); return AGPU_ERR_INVALID; }
-	if (ctx->last_ingest_part_of_sample) { set_last_error("a virus expression table of one sample over several GPUs is not supported"); return AGPU_ERR_INVALID; }
-	const uint64_t size = ctx->last_ingest_stream_size, base = ctx->last_ingest_first_record, n = ctx->last_ingest_records;
-	DeviceBuffer& record_offset = ctx->scratch("ingest.record_offset");
-	if (!ctx->batch_from_ingest || !ctx->last_ingest_kept || ctx->ingest_stream.ptr == nullptr || record_offset.ptr == nullptr || ctx->ingest_stream.capacity < (size + 3) / 4 * 4 || record_offset.capacity < n * 8) {
-		set_last_error("agpu_virus_expression: the record stream of the last ingest is not on the device any more (it was given back under memory pressure, another ingest has begun, or there was no ingest)");
-		return AGPU_ERR_INVALID;
-	}
-	if (n >= 0xFFFFFFF0ull || base > size) { set_last_error("agpu_virus_expression: more than 2^32-16 alignment records"); return AGPU_ERR_INVALID; }
+	ResidentStream resident;
+	TRY(resident_stream(ctx, "agpu_virus_expression", "a virus expression table of one sample over several GPUs is not supported", ctx->virus.active ? "a call is under way on this context" : nullptr, resident));
 	HIP_CHECK(hipSetDevice(ctx->device));
 	ctx->virus.active = true; // (the stream is read from here on: nothing of this context is given back when an allocation fails)
 	hipEvent_t marks[5] = { nullptr, nullptr, nullptr, nullptr, nullptr };
 	struct Guard { agpu_ctx* ctx; hipEvent_t* marks; ~Guard() { (void) hipStreamSynchronize(ctx->stream); for (int k = 0; k < 5; ++k) if (marks[k]) (void) hipEventDestroy(marks[k]); ctx->virus.release_all(); ctx->virus.active = false; } } guard = { ctx, marks };
 	for (int k = 0; k < 5; ++k) HIP_CHECK(hipEventCreate(&marks[k]));
 	uint64_t peak = 0;
-	const int status = run(ctx, viral_ref, viral_length, n_viruses, n_ref, counters, marks, peak);
+	const int status = run(ctx, resident, viral_ref, viral_length, n_viruses, n_ref, counters, marks, peak);
 	if (status == AGPU_OK) counters->peak_bytes = peak;
 	collect_kernel_samples(ctx);
 	return status;

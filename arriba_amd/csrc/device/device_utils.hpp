@@ -56,6 +56,15 @@ __device__ __forceinline__ void block_tally(uint32_t mine, unsigned int* counter
 	__syncthreads();
 	if (threadIdx.x == 0 && *block_sum) atomicAdd(counter, *block_sum);
 }
+// The sum of `mine` over the wavefront, in lane 0.  Every lane of the wavefront calls it.
+__device__ __forceinline__ unsigned int wave_sum(unsigned int mine) {
+	for (int offset = 32; offset > 0; offset >>= 1) mine += __shfl_down(mine, offset);
+	return mine; // (of lane 0)
+}
+__device__ __forceinline__ unsigned long long wave_sum(unsigned long long mine) {
+	for (int offset = 32; offset > 0; offset >>= 1) mine += __shfl_down(mine, offset);
+	return mine; // (of lane 0)
+}
 // A launch takes fewer than 2^32 work-items.  A kernel that gives every ITEM a wavefront (a candidate with its read lists, a bucket of discordant mates, a group of candidates) would
 // exceed that at 2^26 = 67 M items -- a sample of 2 x 10^8 fragments has that many candidates -- and the runtime refuses such a launch without a word to the caller (the bug of
 // round 5 in agpu_get_candidate_read_lists_of).  These kernels take the index of their first item, and the host launches them in chunks: for_each_wave_chunk(items, launch(first, count)).

@@ -74,6 +74,18 @@ int g_error_code = 0; // the status of the device library behind g_error (AGPU_E
 struct Failure { std::string text; int code = 0; Failure(const std::string& t, int c = 0) : text(t), code(c) {} };
 void device_check(int status) { if (status != AGPU_OK) throw Failure{ std::string("ERROR: ") + agpu_last_error(), status }; }
 void host_check(int status) { if (status != 0) throw Failure{ std::string("ERROR: ") + ahost_last_error() }; }
+// The outputs that are made from the record stream while it is in HBM behind the ingest (write_virus_expression ... build_support_pool).  need_device: `entry`, the first of the
+// entry points of `option`, is linked.  device_call: the status of such an entry point; when the device ran out of memory the message names the option.  append_windows: the windows
+// of text that next(window) fetches -- through two pinned buffers in turn, 0 bytes behind the last -- go to `file`, the open `temporary`.
+void need_device(const char* option, const char* entry, bool linked) { if (!linked) throw Failure{ std::string("ERROR: ") + option + " needs the device library (" + entry + "), which this build is not linked with" }; }
+void device_call(const char* option, int status) { if (status == AGPU_ERR_NO_MEMORY) throw Failure{ std::string("ERROR: ") + option + ": " + agpu_last_error(), status }; device_check(status); }
+template <class Next> void append_windows(FILE* file, const std::string& temporary, uint8_t* const windows[2], Next next) {
+	for (unsigned int turn = 0; ; ++turn) {
+		const uint64_t bytes = next(windows[turn & 1]);
+		if (bytes == 0) break;
+		if (fwrite(windows[turn & 1], 1, bytes, file) != bytes) throw Failure{ "ERROR: failed to write '" + temporary + "'" };
+	}
+}
 
 // filter ids (positions in FILTERS, source/common.hpp:29-67) of the filters main() asks about itself
 enum { F_known_fusions = 18, F_blacklist = 20, F_no_genomic_support = 29, F_genomic_support = 34, F_many_spliced = 28, F_select_best = 24 };
@@ -356,25 +368,25 @@ void feed_one_file(Run& run, const char* path, int role) {
 	const double started = now_seconds();
 	if (role != AGPU_ROLE_SEPARATE_RNA) run.feed_started = started;
 	check_mark_duplicates(o);
-	if (o.mark_duplicates && (!agpu_sorted_bam_set_mark_duplicates || !agpu_markdup_stats)) throw Failure{ "ERROR: --mark-duplicates needs the device library (agpu_sorted_bam_set_mark_duplicates), which this build is not linked with" }; // (before the feed, not behind it)
+	if (o.mark_duplicates) need_device("--mark-duplicates", "agpu_sorted_bam_set_mark_duplicates", agpu_sorted_bam_set_mark_duplicates && agpu_markdup_stats); // (before the feed, not behind it)
 	if (run.ranks != nullptr && o.sorted_bam_file != nullptr) throw Failure{ "ERROR: a sorted BAM file of one sample over several GPUs is not supported" };
 	if (run.ranks != nullptr && o.supporting_alignments_prefix != nullptr) throw Failure{ "ERROR: supporting alignments of one sample over several GPUs are not supported" };
 	if (run.ranks != nullptr && o.virus_expression_file != nullptr) throw Failure{ "ERROR: a virus expression table of one sample over several GPUs is not supported" };
 	if (run.ranks != nullptr && o.coverage_file != nullptr) throw Failure{ "ERROR: a coverage track of one sample over several GPUs is not supported" };
-	if (o.coverage_file != nullptr && (!agpu_depth_begin || !agpu_depth_next || !agpu_depth_end)) throw Failure{ "ERROR: --coverage needs the device library (agpu_depth_begin), which this build is not linked with" }; // (before the feed, not behind it)
+	if (o.coverage_file != nullptr) need_device("--coverage", "agpu_depth_begin", agpu_depth_begin && agpu_depth_next && agpu_depth_end); // (before the feed, not behind it)
 	if (run.ranks != nullptr && o.gene_counts_file != nullptr) throw Failure{ "ERROR: gene counts of one sample over several GPUs are not supported" };
-	if (o.gene_counts_file != nullptr && !agpu_gene_counts) throw Failure{ "ERROR: --gene-counts needs the device library (agpu_gene_counts), which this build is not linked with" }; // (likewise)
+	if (o.gene_counts_file != nullptr) need_device("--gene-counts", "agpu_gene_counts", agpu_gene_counts); // (likewise)
 	if (run.ranks != nullptr && o.splice_junctions_file != nullptr) throw Failure{ "ERROR: splice junctions of one sample over several GPUs are not supported" };
-	if (o.splice_junctions_file != nullptr && !agpu_splice_junctions) throw Failure{ "ERROR: --splice-junctions needs the device library (agpu_splice_junctions), which this build is not linked with" }; // (likewise)
-	if (o.virus_expression_file != nullptr && !agpu_virus_expression) throw Failure{ "ERROR: --virus-expression needs the device library (agpu_virus_expression), which this build is not linked with" }; // (before the feed, not behind it)
-	if (check_realign(run) && (!agpu_realign_begin || !agpu_realign_next || !agpu_realign_end)) throw Failure{ "ERROR: --realign-reads needs the device library (agpu_realign_begin), which this build is not linked with" }; // (likewise)
+	if (o.splice_junctions_file != nullptr) need_device("--splice-junctions", "agpu_splice_junctions", agpu_splice_junctions); // (likewise)
+	if (o.virus_expression_file != nullptr) need_device("--virus-expression", "agpu_virus_expression", agpu_virus_expression); // (before the feed, not behind it)
+	if (check_realign(run)) need_device("--realign-reads", "agpu_realign_begin", agpu_realign_begin && agpu_realign_next && agpu_realign_end); // (likewise)
 	ahost_allele_sites_free(&run.allele_sites); // (of a sample that failed between its feed and its counts)
 	if (check_allele_counts(run)) {
-		if (!agpu_allele_counts) throw Failure{ "ERROR: --allele-counts needs the device library (agpu_allele_counts), which this build is not linked with" }; // (likewise)
+		need_device("--allele-counts", "agpu_allele_counts", agpu_allele_counts); // (likewise)
 		host_check(ahost_allele_sites_load(o.allele_sites_file, nullptr, 0, &run.allele_sites)); // (a sites file that does not parse is refused here; its lines are placed when the header is known)
 	}
 	if (check_rna_metrics(run)) {
-		if (!agpu_rna_metrics) throw Failure{ "ERROR: --rna-metrics needs the device library (agpu_rna_metrics), which this build is not linked with" }; // (likewise)
+		need_device("--rna-metrics", "agpu_rna_metrics", agpu_rna_metrics); // (likewise)
 		agpu_region_track track;
 		host_check(ahost_region_track(run.host, o.rrna_intervals_file, &track, nullptr)); // (an interval file that does not parse is refused here; the track of the session is built once and kept)
 	}
@@ -605,10 +617,10 @@ bool shard_reads(Run& run, agpu_ingest_result& result, uint64_t windows, uint32_
 // they are removed and the sample fails with the message.  Windows come through two pinned buffers in turn: window k + 1 is gathered while window k is written.
 void write_sorted_bam(Run& run) {
 	const std::string path = run.options.sorted_bam_file, bam_tmp = path + ".tmp", bai_tmp = path + ".bai.tmp";
-	if (!agpu_sorted_bam_begin || !agpu_sorted_bam_next || !agpu_sorted_bam_index || !agpu_sorted_bam_end) throw Failure{ "ERROR: --sorted-bam needs the device library (agpu_sorted_bam_begin), which this build is not linked with" };
+	need_device("--sorted-bam", "agpu_sorted_bam_begin", agpu_sorted_bam_begin && agpu_sorted_bam_next && agpu_sorted_bam_index && agpu_sorted_bam_end);
 	const int level = run.options.sorted_bam_compression;
 	if (level != 0 && level != 1) throw Failure{ "ERROR: the compression level of a sorted BAM file is 0 (stored) or 1" };
-	if (level != 0 && (!agpu_sorted_bam_set_compression || !agpu_sorted_bam_compressed_bytes)) throw Failure{ "ERROR: --sorted-bam-compression needs the device library (agpu_sorted_bam_set_compression), which this build is not linked with" };
+	if (level != 0) need_device("--sorted-bam-compression", "agpu_sorted_bam_set_compression", agpu_sorted_bam_set_compression && agpu_sorted_bam_compressed_bytes);
 	const double started = now_seconds();
 	agpu_sorted_bam_info info;
 	if (level != 0) device_check(agpu_sorted_bam_set_compression(run.device, level));
@@ -665,14 +677,12 @@ void write_sorted_bam(Run& run) {
 // --virus-expression: behind the ingest, while the stream is in HBM, the counters of the table come from the device (include/arriba_gpu.h: agpu_virus_expression) for the viral
 // contigs that -v names in the header of the file; the host does the arithmetic, the removal of related strains and the text.  FILE.tmp is renamed when it is complete.
 void write_virus_expression(Run& run) {
-	if (!agpu_virus_expression) throw Failure{ "ERROR: --virus-expression needs the device library (agpu_virus_expression), which this build is not linked with" };
+	need_device("--virus-expression", "agpu_virus_expression", agpu_virus_expression);
 	const double started = now_seconds();
 	ahost_virus_contigs contigs;
 	host_check(ahost_virus_contigs_of_session(run.host, &contigs));
 	agpu_virus_counters counters;
-	const int status = agpu_virus_expression(run.device, contigs.viral_ref, contigs.viral_length, contigs.n_viruses, contigs.n_ref, &counters);
-	if (status == AGPU_ERR_NO_MEMORY) throw Failure{ std::string("ERROR: --virus-expression: ") + agpu_last_error(), status };
-	device_check(status);
+	device_call("--virus-expression", agpu_virus_expression(run.device, contigs.viral_ref, contigs.viral_length, contigs.n_viruses, contigs.n_ref, &counters));
 	host_check(ahost_virus_expression_write(&counters, &contigs, run.options.virus_expression_file));
 	run.virus_expression_seconds = now_seconds() - started;
 }
@@ -681,26 +691,20 @@ void write_virus_expression(Run& run) {
 // computes and formats; the host only appends the windows of text -- through two pinned buffers in turn -- to FILE.tmp, which is renamed when it is complete.  On a failure it is
 // removed and the sample fails with the message.
 void write_coverage(Run& run) {
-	if (!agpu_depth_begin || !agpu_depth_next || !agpu_depth_end) throw Failure{ "ERROR: --coverage needs the device library (agpu_depth_begin), which this build is not linked with" };
+	need_device("--coverage", "agpu_depth_begin", agpu_depth_begin && agpu_depth_next && agpu_depth_end);
 	const std::string path = run.options.coverage_file, temporary = path + ".tmp";
 	const double started = now_seconds();
 	ahost_depth_contigs contigs;
 	host_check(ahost_depth_contigs_of_session(run.host, &contigs));
 	agpu_depth_info info;
-	const auto check = [](int status) { if (status == AGPU_ERR_NO_MEMORY) throw Failure{ std::string("ERROR: --coverage: ") + agpu_last_error(), status }; device_check(status); };
-	check(agpu_depth_begin(run.device, contigs.length, contigs.names, contigs.name_offset, contigs.n_ref, &info));
+	device_call("--coverage", agpu_depth_begin(run.device, contigs.length, contigs.names, contigs.name_offset, contigs.n_ref, &info));
 	struct Ender { Run& run; ~Ender() { agpu_depth_end(run.device, nullptr); } } ender = { run };
 	FILE* file = nullptr;
 	try {
 		file = fopen(temporary.c_str(), "wb");
 		if (file == nullptr) throw Failure{ "ERROR: failed to open '" + temporary + "' for writing" };
 		uint8_t* windows[2] = { run.stage<uint8_t>("coverage.window0", info.window_bytes), run.stage<uint8_t>("coverage.window1", info.window_bytes) };
-		for (unsigned int turn = 0; ; ++turn) {
-			uint64_t bytes = 0;
-			check(agpu_depth_next(run.device, windows[turn & 1], info.window_bytes, &bytes));
-			if (bytes == 0) break;
-			if (fwrite(windows[turn & 1], 1, bytes, file) != bytes) throw Failure{ "ERROR: failed to write '" + temporary + "'" };
-		}
+		append_windows(file, temporary, windows, [&](uint8_t* window) { uint64_t bytes = 0; device_call("--coverage", agpu_depth_next(run.device, window, info.window_bytes, &bytes)); return bytes; });
 		const int closed = fclose(file); file = nullptr;
 		if (closed != 0) throw Failure{ "ERROR: failed to write '" + temporary + "'" };
 		if (rename(temporary.c_str(), path.c_str()) != 0) throw Failure{ "ERROR: failed to write '" + path + "'" };
@@ -712,7 +716,7 @@ void write_coverage(Run& run) {
 // --gene-counts: behind the ingest, while the stream is in HBM, the reads per gene in three columns (include/arriba_gpu.h: agpu_gene_counts).  The device counts;
 // the host turns the table into text with the gene ids of the session and writes it through FILE.tmp.  On a failure nothing is left and the sample fails with the message.
 void write_gene_counts(Run& run) {
-	if (!agpu_gene_counts) throw Failure{ "ERROR: --gene-counts needs the device library (agpu_gene_counts), which this build is not linked with" };
+	need_device("--gene-counts", "agpu_gene_counts", agpu_gene_counts);
 	const double started = now_seconds();
 	ahost_depth_contigs contigs;
 	host_check(ahost_depth_contigs_of_session(run.host, &contigs)); // (LN of the references of the header)
@@ -720,9 +724,7 @@ void write_gene_counts(Run& run) {
 	host_check(ahost_gene_counts_genes(run.host, &n_genes, nullptr, nullptr));
 	std::vector<uint64_t> counts(3 * ((size_t) n_genes + 4), 0);
 	agpu_gene_count_stats stats;
-	const int status = agpu_gene_counts(run.device, contigs.length, contigs.n_ref, counts.data(), &stats);
-	if (status == AGPU_ERR_NO_MEMORY) throw Failure{ std::string("ERROR: --gene-counts: ") + agpu_last_error(), status };
-	device_check(status);
+	device_call("--gene-counts", agpu_gene_counts(run.device, contigs.length, contigs.n_ref, counts.data(), &stats));
 	host_check(ahost_gene_counts_write(run.host, counts.data(), counts.size(), run.options.gene_counts_file));
 	run.say(gene_counts_line(stats));
 	run.gene_counts_seconds = now_seconds() - started;
@@ -732,15 +734,13 @@ void write_gene_counts(Run& run) {
 // the rows; the host turns them into text with the names of the references of the header and writes it through FILE.tmp.  On a failure nothing is left and the sample fails with
 // the message.
 void write_splice_junctions(Run& run) {
-	if (!agpu_splice_junctions) throw Failure{ "ERROR: --splice-junctions needs the device library (agpu_splice_junctions), which this build is not linked with" };
+	need_device("--splice-junctions", "agpu_splice_junctions", agpu_splice_junctions);
 	const double started = now_seconds();
 	ahost_depth_contigs contigs;
 	host_check(ahost_depth_contigs_of_session(run.host, &contigs)); // (names and LN of the references of the header)
 	const agpu_junction_row* rows = nullptr; uint64_t n_rows = 0;
 	agpu_junction_stats stats;
-	const int status = agpu_splice_junctions(run.device, contigs.length, contigs.n_ref, &rows, &n_rows, &stats);
-	if (status == AGPU_ERR_NO_MEMORY) throw Failure{ std::string("ERROR: --splice-junctions: ") + agpu_last_error(), status };
-	device_check(status);
+	device_call("--splice-junctions", agpu_splice_junctions(run.device, contigs.length, contigs.n_ref, &rows, &n_rows, &stats));
 	host_check(ahost_splice_junctions_write(&contigs, rows, n_rows, run.options.splice_junctions_file));
 	run.say(splice_junctions_line(stats));
 	run.splice_junctions_seconds = now_seconds() - started;
@@ -750,7 +750,7 @@ void write_splice_junctions(Run& run) {
 // lines of the sites file, read before the feed, are placed on the references of the header; the device counts; the host writes the text with the contigs as the sites file spells
 // them, through FILE.tmp.  On a failure nothing is left and the sample fails with the message.
 void write_allele_counts(Run& run) {
-	if (!agpu_allele_counts) throw Failure{ "ERROR: --allele-counts needs the device library (agpu_allele_counts), which this build is not linked with" };
+	need_device("--allele-counts", "agpu_allele_counts", agpu_allele_counts);
 	const double started = now_seconds();
 	struct Free { ahost_allele_sites& sites; ~Free() { ahost_allele_sites_free(&sites); } } free_sites = { run.allele_sites };
 	if (run.allele_sites.owner == nullptr) host_check(ahost_allele_sites_load(run.options.allele_sites_file, nullptr, 0, &run.allele_sites)); // (a sample that was not fed through feed_file)
@@ -759,9 +759,7 @@ void write_allele_counts(Run& run) {
 	host_check(ahost_depth_contigs_of_session(run.host, &contigs)); // (LN of the references of the header)
 	const agpu_allele_row* rows = nullptr;
 	agpu_allele_stats stats;
-	const int status = agpu_allele_counts(run.device, run.allele_sites.sites, run.allele_sites.n_sites, contigs.length, contigs.n_ref, run.options.allele_min_mapq, run.options.allele_min_baseq, &rows, &stats);
-	if (status == AGPU_ERR_NO_MEMORY) throw Failure{ std::string("ERROR: --allele-counts: ") + agpu_last_error(), status };
-	device_check(status);
+	device_call("--allele-counts", agpu_allele_counts(run.device, run.allele_sites.sites, run.allele_sites.n_sites, contigs.length, contigs.n_ref, run.options.allele_min_mapq, run.options.allele_min_baseq, &rows, &stats));
 	host_check(ahost_allele_counts_write(&run.allele_sites, rows, run.allele_sites.n_sites, run.options.allele_counts_file));
 	run.say(allele_counts_line(stats));
 	run.allele_counts_seconds = now_seconds() - started;
@@ -771,7 +769,7 @@ void write_allele_counts(Run& run) {
 // agpu_realign_*).  The device decides and formats; the host writes the header of the kept file and appends the windows of text -- through two pinned buffers in
 // turn -- to NAME.tmp, which is renamed when both files are complete.  On a failure both are removed and the sample fails with the message.
 void write_realign(Run& run) {
-	if (!agpu_realign_begin || !agpu_realign_next || !agpu_realign_end) throw Failure{ "ERROR: --realign-reads needs the device library (agpu_realign_begin), which this build is not linked with" };
+	need_device("--realign-reads", "agpu_realign_begin", agpu_realign_begin && agpu_realign_next && agpu_realign_end);
 	const double started = now_seconds();
 	const char* const paths[2] = { run.options.realign_reads_file, run.options.realign_kept_file };
 	ahost_depth_contigs contigs;
@@ -779,8 +777,7 @@ void write_realign(Run& run) {
 	ahost_realign_plan plan;
 	host_check(ahost_realign_plan_of_session(run.host, &plan));
 	agpu_realign_info info;
-	const auto check = [](int status) { if (status == AGPU_ERR_NO_MEMORY) throw Failure{ std::string("ERROR: --realign-reads: ") + agpu_last_error(), status }; device_check(status); };
-	check(agpu_realign_begin(run.device, plan.in_assembly, contigs.names, contigs.name_offset, contigs.n_ref, paths[1] != nullptr, &info));
+	device_call("--realign-reads", agpu_realign_begin(run.device, plan.in_assembly, contigs.names, contigs.name_offset, contigs.n_ref, paths[1] != nullptr, &info));
 	agpu_realign_stats stats;
 	struct Ender { Run& run; agpu_realign_stats& stats; bool done; ~Ender() { if (!done) agpu_realign_end(run.device, nullptr); } } ender = { run, stats, false };
 	FILE* file = nullptr;
@@ -792,12 +789,7 @@ void write_realign(Run& run) {
 			file = fopen(temporary.c_str(), "wb");
 			if (file == nullptr) throw Failure{ "ERROR: failed to open '" + temporary + "' for writing" };
 			if (which == 1 && fwrite(plan.header, 1, plan.header_bytes, file) != plan.header_bytes) throw Failure{ "ERROR: failed to write '" + temporary + "'" };
-			for (unsigned int turn = 0; ; ++turn) {
-				uint64_t bytes = 0;
-				check(agpu_realign_next(run.device, which, windows[turn & 1], info.window_bytes, &bytes));
-				if (bytes == 0) break;
-				if (fwrite(windows[turn & 1], 1, bytes, file) != bytes) throw Failure{ "ERROR: failed to write '" + temporary + "'" };
-			}
+			append_windows(file, temporary, windows, [&](uint8_t* window) { uint64_t bytes = 0; device_call("--realign-reads", agpu_realign_next(run.device, which, window, info.window_bytes, &bytes)); return bytes; });
 			const int closed = fclose(file); file = nullptr;
 			if (closed != 0) throw Failure{ "ERROR: failed to write '" + temporary + "'" };
 		}
@@ -805,7 +797,7 @@ void write_realign(Run& run) {
 	}
 	catch (...) { if (file) fclose(file); for (int which = 0; which < 2; ++which) if (paths[which] != nullptr) { remove((std::string(paths[which]) + ".tmp").c_str()); remove(paths[which]); } throw; }
 	ender.done = true;
-	check(agpu_realign_end(run.device, &stats));
+	device_call("--realign-reads", agpu_realign_end(run.device, &stats));
 	run.say(realign_line(stats));
 	run.realign_seconds = now_seconds() - started;
 }
@@ -814,7 +806,7 @@ void write_realign(Run& run) {
 // track of the session (once per interval file); the device sums; the host turns the counter block into text and writes it through FILE.tmp.  On a failure nothing is left and the
 // sample fails with the message.
 void write_rna_metrics(Run& run) {
-	if (!agpu_rna_metrics) throw Failure{ "ERROR: --rna-metrics needs the device library (agpu_rna_metrics), which this build is not linked with" };
+	need_device("--rna-metrics", "agpu_rna_metrics", agpu_rna_metrics);
 	const double started = now_seconds();
 	agpu_region_track track;
 	host_check(ahost_region_track(run.host, run.options.rrna_intervals_file, &track, nullptr));
@@ -822,9 +814,7 @@ void write_rna_metrics(Run& run) {
 	host_check(ahost_depth_contigs_of_session(run.host, &contigs)); // (LN of the references of the header)
 	std::vector<uint64_t> counters(AGPU_RNA_METRICS_WORDS, 0);
 	agpu_rna_metrics_stats stats;
-	const int status = agpu_rna_metrics(run.device, &track, contigs.length, contigs.n_ref, counters.data(), &stats);
-	if (status == AGPU_ERR_NO_MEMORY) throw Failure{ std::string("ERROR: --rna-metrics: ") + agpu_last_error(), status };
-	device_check(status);
+	device_call("--rna-metrics", agpu_rna_metrics(run.device, &track, contigs.length, contigs.n_ref, counters.data(), &stats));
 	host_check(ahost_rna_metrics_write(counters.data(), counters.size(), run.options.rna_metrics_file));
 	run.say(rna_metrics_line(stats));
 	run.rna_metrics_seconds = now_seconds() - started;
@@ -833,13 +823,10 @@ void write_rna_metrics(Run& run) {
 // --supporting-alignments, phase 1: behind the ingest, while the stream is in HBM, the records of the read names of the batch go into a pool of this lane's context
 // (include/arriba_gpu.h: agpu_support_pool_build).  Phase 2 follows when the rows of fusions.tsv are fixed (write_supporting_alignments).
 void build_support_pool(Run& run) {
-	if (!agpu_support_pool_build || !agpu_supporting_begin || !agpu_supporting_row_bytes || !agpu_supporting_next || !agpu_supporting_index || !agpu_supporting_end || !agpu_support_pool_release)
-		throw Failure{ "ERROR: --supporting-alignments needs the device library (agpu_support_pool_build), which this build is not linked with" };
+	need_device("--supporting-alignments", "agpu_support_pool_build", agpu_support_pool_build && agpu_supporting_begin && agpu_supporting_row_bytes && agpu_supporting_next && agpu_supporting_index && agpu_supporting_end && agpu_support_pool_release);
 	const double started = now_seconds();
 	agpu_support_pool_info info;
-	const int status = agpu_support_pool_build(run.device, nullptr, nullptr, 0, &info);
-	if (status == AGPU_ERR_NO_MEMORY) throw Failure{ std::string("ERROR: --supporting-alignments: ") + agpu_last_error(), status };
-	device_check(status);
+	device_call("--supporting-alignments", agpu_support_pool_build(run.device, nullptr, nullptr, 0, &info));
 	run.support_pool_built = true;
 	run.supporting_seconds = now_seconds() - started;
 }
