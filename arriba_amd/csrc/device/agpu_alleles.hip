@@ -10,6 +10,7 @@
 //                           The loop ends when no lane has a hit left; no lane leaves before that
 //   allele_rows_kernel      one lane per sorted site: its eight counters into the row of its line
 //   allele_ref_kernel       one lane per line: REF from the assembly through tid_to_contig, '.' for an unplaced line
+// The bitmap and the count work on sorted keys that lie on the device and are shared with --variant-sites: allele_count.hpp has the two kernels and their launches.
 // Counters are unsigned sums: the rows are the same under every schedule.  The stream is only read.
 // Integer work bound by dependent loads: record_offset -> the head of the record -> its CIGAR words -> (only where a window holds a site) the sorted keys, one SEQ and one QUAL
 // byte.  No MFMA, no LDS.
@@ -22,59 +23,13 @@
 #include <rocprim/rocprim.hpp>
 #define AGPU_OPTION "--allele-counts"
 #define ALLOC(buffer, bytes) AGPU_ALLOC(buffer, bytes, state.note_peak())
-#include "resident_stream.hpp"
-#include "device_utils.hpp"
-#include "allele_core.hpp"
+#include "allele_count.hpp"
 
 using namespace agpu;
 
 namespace {
 
 enum { PASS_SITES = 0, PASS_COUNT = 1, PASS_ROWS = 2, PASSES = 3 };
-
-// keys: the sorted placed sites.  The bitmap has a word for every 32 windows of window_offset[n_ref] and is zero before.
-__global__ void __launch_bounds__(BLOCK) allele_bitmap_kernel(const uint64_t* __restrict__ keys, uint64_t placed, const uint64_t* __restrict__ window_offset, uint32_t n_ref, uint32_t* bitmap) {
-	const uint64_t k = (uint64_t) blockIdx.x * BLOCK + threadIdx.x;
-	if (k >= placed) return;
-	const uint64_t key = keys[k];
-	const uint32_t ref = (uint32_t) (key >> 32);
-	if (ref >= n_ref) return; // (agpu_allele_counts admits no such site)
-	const uint64_t window = allele_window(window_offset, ref, (uint32_t) key);
-	if (window >= window_offset[n_ref]) return; // (likewise: pos < LN)
-	atomicOr(&bitmap[window >> 5], 1u << (window & 31u));
-}
-
-// counts: [sites.n][ALLELE_COLUMNS].  No lane leaves before the loop ends for the whole wavefront.
-template <bool LEADER> __global__ void __launch_bounds__(BLOCK) allele_count_kernel(const uint8_t* __restrict__ stream, uint64_t stream_size, const uint64_t* __restrict__ record_offset, uint64_t n, uint64_t first,
-		const uint32_t* __restrict__ ref_length, uint32_t n_ref, AlleleSites sites, uint32_t min_mapq, uint32_t min_baseq, uint32_t* counts, unsigned long long* contributing) {
-	const uint64_t r = first + (uint64_t) blockIdx.x * BLOCK + threadIdx.x;
-	const uint32_t lane = threadIdx.x & 63u;
-	AlleleWalk walk = {};
-	bool live = false;
-	if (r < n) {
-		AlleleRecord record;
-		if (allele_record(stream, record_offset[r], stream_size, n_ref, min_mapq, record)) { live = true; allele_walk_begin(walk, record, ref_length[record.ref]); }
-	}
-	{ const unsigned int sum = wave_sum(live ? 1u : 0u);
-	  if (lane == 0 && sum != 0) atomicAdd(contributing, (unsigned long long) sum); }
-	for (;;) {
-		uint32_t slot = 0, column = 0;
-		const bool hit = live && allele_walk_next(walk, stream, sites, min_baseq, slot, column);
-		live = hit;
-		unsigned long long todo = __ballot(hit);
-		if (todo == 0) break; // (the same in every lane)
-		const uint32_t value = slot << 3 | column; // (slot < 2^29)
-		if (LEADER) {
-			while (todo != 0) {
-				const int leader = __ffsll((long long) todo) - 1;
-				const uint32_t theirs = __shfl(value, leader);
-				const unsigned long long same = __ballot(hit && value == theirs);
-				if (lane == (uint32_t) leader) atomicAdd(&counts[theirs], (uint32_t) __popcll(same));
-				todo &= ~same;
-			}
-		} else if (hit) atomicAdd(&counts[value], 1u);
-	}
-}
 
 __global__ void __launch_bounds__(BLOCK) allele_rows_kernel(const uint32_t* __restrict__ counts, const uint32_t* __restrict__ line_of, uint64_t placed, uint64_t n_sites, agpu_allele_row* rows) {
 	const uint64_t k = (uint64_t) blockIdx.x * BLOCK + threadIdx.x;
@@ -93,39 +48,31 @@ __global__ void __launch_bounds__(BLOCK) allele_ref_kernel(const agpu_allele_sit
 	rows[line].ref_base = site.ref < n_ref && site.pos >= 0 ? allele_ref_base(genome, tid_to_contig[site.ref], (uint32_t) site.pos) : (uint8_t) '.';
 }
 
-bool knob(const char* name) { const char* value = getenv(name); return value != nullptr && value[0] == '1'; } // (for the measurements of DESIGN.md 4.17)
-
 int count(agpu_ctx* ctx, const ResidentStream& resident, const agpu_allele_site* sites, uint64_t n_sites, const uint32_t* ref_length, uint32_t n_ref, uint32_t min_mapq, uint32_t min_baseq, hipEvent_t* events) {
 	AlleleState& state = ctx->allele;
 	hipStream_t s = ctx->stream;
-	const uint64_t size = resident.stream_size, n = resident.records;
+	const uint64_t n = resident.records;
 	state.stats.records = n; state.stats.sites = n_sites;
-	// the placed sites as keys with their lines; the first window of every reference
-	std::vector<uint64_t> keys; std::vector<uint32_t> lines; std::vector<uint64_t> window_offset((size_t) n_ref + 1, 0);
+	// the placed sites as keys with their lines
+	std::vector<uint64_t> keys; std::vector<uint32_t> lines;
 	for (uint64_t line = 0; line < n_sites; ++line) {
 		const agpu_allele_site& site = sites[line];
 		if (site.ref == ALLELE_UNPLACED) continue;
 		if (site.ref >= n_ref || site.pos < 0 || (uint32_t) site.pos >= ref_length[site.ref]) { set_last_error("agpu_allele_counts: site " + std::to_string(line) + " lies on no reference of the header or beyond its length (unplaced sites have ref 0xFFFFFFFF)"); return AGPU_ERR_INVALID; }
 		keys.push_back(allele_key(site.ref, (uint32_t) site.pos)); lines.push_back((uint32_t) line);
 	}
-	for (uint32_t t = 0; t < n_ref; ++t) window_offset[t + 1] = window_offset[t] + allele_windows_of(ref_length[t]);
-	const uint64_t placed = keys.size(), words = window_offset[n_ref] / 32 + 1;
+	const uint64_t placed = keys.size();
 	state.stats.placed = placed;
 	state.rows.assign(n_sites, agpu_allele_row());
 	if (n_sites == 0 && n == 0) { for (int k = 0; k <= PASSES; ++k) HIP_CHECK(hipEventRecord(events[k], s)); return AGPU_OK; }
-	const bool with_bitmap = !knob("ARRIBA_ALLELE_NO_BITMAP");
-	DeviceBuffer& lengths = state.buffer("allele.ref_length"); DeviceBuffer& windows = state.buffer("allele.window_offset"); DeviceBuffer& contributing = state.buffer("allele.contributing");
 	DeviceBuffer& keys_in = state.buffer("allele.keys_in"); DeviceBuffer& lines_in = state.buffer("allele.lines_in"); DeviceBuffer& sorted_keys = state.buffer("allele.keys"); DeviceBuffer& sorted_lines = state.buffer("allele.lines");
-	DeviceBuffer& temporary_storage = state.buffer("allele.rocprim"); DeviceBuffer& bitmap = state.buffer("allele.bitmap"); DeviceBuffer& counts = state.buffer("allele.counts");
+	DeviceBuffer& temporary_storage = state.buffer("allele.rocprim"); DeviceBuffer& counts = state.buffer("allele.counts");
 	DeviceBuffer& device_sites = state.buffer("allele.sites"); DeviceBuffer& rows = state.buffer("allele.rows");
-	ALLOC(lengths, std::max<size_t>(n_ref, 1) * 4); ALLOC(windows, ((size_t) n_ref + 1) * 8); ALLOC(contributing, 8);
-	ALLOC(device_sites, std::max<size_t>(n_sites, 1) * sizeof(agpu_allele_site)); ALLOC(rows, std::max<size_t>(n_sites, 1) * sizeof(agpu_allele_row)); ALLOC(counts, std::max<size_t>(placed, 1) * ALLELE_COLUMNS * 4);
-	HIP_CHECK(hipMemsetAsync(contributing.ptr, 0, 8, s));
+	AlleleCounting counting = { state.buffer("allele.ref_length"), state.buffer("allele.window_offset"), state.buffer("allele.contributing"), state.buffer("allele.bitmap"), counts, 0, true };
+	DeviceBuffer& contributing = counting.contributing;
+	TRY(allele_counting_begin(ctx, state, counting, ref_length, n_ref, placed)); // (LN and the first window of every reference, the zeroed counters and bitmap)
+	ALLOC(device_sites, std::max<size_t>(n_sites, 1) * sizeof(agpu_allele_site)); ALLOC(rows, std::max<size_t>(n_sites, 1) * sizeof(agpu_allele_row));
 	HIP_CHECK(hipMemsetAsync(rows.ptr, 0, std::max<size_t>(n_sites, 1) * sizeof(agpu_allele_row), s));
-	HIP_CHECK(hipMemsetAsync(counts.ptr, 0, std::max<size_t>(placed, 1) * ALLELE_COLUMNS * 4, s));
-	if (with_bitmap) { ALLOC(bitmap, words * 4); HIP_CHECK(hipMemsetAsync(bitmap.ptr, 0, words * 4, s)); }
-	if (n_ref > 0) HIP_CHECK(hipMemcpyAsync(lengths.ptr, ref_length, (size_t) n_ref * 4, hipMemcpyHostToDevice, s));
-	HIP_CHECK(hipMemcpyAsync(windows.ptr, window_offset.data(), window_offset.size() * 8, hipMemcpyHostToDevice, s));
 	if (n_sites > 0) HIP_CHECK(hipMemcpyAsync(device_sites.ptr, sites, n_sites * sizeof(agpu_allele_site), hipMemcpyHostToDevice, s));
 	if (placed > 0) {
 		ALLOC(keys_in, placed * 8); ALLOC(lines_in, placed * 4); ALLOC(sorted_keys, placed * 8); ALLOC(sorted_lines, placed * 4);
@@ -142,22 +89,11 @@ int count(agpu_ctx* ctx, const ResidentStream& resident, const agpu_allele_site*
 		ALLOC(temporary_storage, std::max<size_t>(temporary, 4));
 		{ KernelTimer timer(ctx, "allele rocprim::radix_sort_pairs(sites)", placed * 24);
 		  HIP_CHECK(rocprim::radix_sort_pairs(temporary_storage.ptr, temporary, keys_in.as<uint64_t>(), sorted_keys.as<uint64_t>(), lines_in.as<uint32_t>(), sorted_lines.as<uint32_t>(), (size_t) placed, 0u, key_bits, s)); }
-		if (with_bitmap) { KernelTimer timer(ctx, "allele_bitmap_kernel", placed * 12);
-		  allele_bitmap_kernel<<<grid_for(placed), BLOCK, 0, s>>>(sorted_keys.as<uint64_t>(), placed, windows.as<uint64_t>(), n_ref, bitmap.as<uint32_t>()); }
+		allele_counting_bitmap(ctx, counting, sorted_keys.as<uint64_t>(), n_ref);
 	}
 	// the count over the records
 	HIP_CHECK(hipEventRecord(events[PASS_COUNT], s));
-	if (n > 0) { // (also without a placed site: `contributing` is the number of records that pass the filter, whatever the sites are)
-		const uint8_t* stream = resident.stream;
-		const uint64_t* record_offset = resident.record_offset;
-		const AlleleSites view = { placed > 0 ? sorted_keys.as<uint64_t>() : nullptr, placed, with_bitmap ? bitmap.as<uint32_t>() : nullptr, windows.as<uint64_t>() };
-		const bool plain = knob("ARRIBA_ALLELE_PLAIN_ATOMICS");
-		KernelTimer timer(ctx, "allele_count_kernel", n * 72);
-		for_each_launch_piece(n, [&](uint64_t first, unsigned int grid) {
-			if (plain) allele_count_kernel<false><<<grid, BLOCK, 0, s>>>(stream, size, record_offset, n, first, lengths.as<uint32_t>(), n_ref, view, min_mapq, min_baseq, counts.as<uint32_t>(), contributing.as<unsigned long long>());
-			else allele_count_kernel<true><<<grid, BLOCK, 0, s>>>(stream, size, record_offset, n, first, lengths.as<uint32_t>(), n_ref, view, min_mapq, min_baseq, counts.as<uint32_t>(), contributing.as<unsigned long long>());
-		});
-	}
+	allele_counting_records(ctx, counting, resident, sorted_keys.as<uint64_t>(), n_ref, min_mapq, min_baseq);
 	// REF and the rows in the order of the lines
 	HIP_CHECK(hipEventRecord(events[PASS_ROWS], s));
 	if (placed > 0) { KernelTimer timer(ctx, "allele_rows_kernel", placed * 68);

@@ -1,5 +1,5 @@
 // arriba_amd/csrc/device/resident_stream.hpp -- what the consumers of the record stream that the last ingest left in HBM have in common (--sorted-bam, --mark-duplicates,
-// --supporting-alignments, --virus-expression, --coverage, --gene-counts, --splice-junctions, --allele-counts, --realign-reads, --rna-metrics): the guard in front of the stream
+// --supporting-alignments, --virus-expression, --coverage, --gene-counts, --splice-junctions, --allele-counts, --realign-reads, --rna-metrics, --variant-sites): the guard in front of the stream
 // (resident_stream), the macros and launch helpers of their host code, and the frame of those that do their work inside one call (one_shot).  Their state is a StreamConsumer
 // (agpu_context.hpp).  A file names its option before it includes this header: #define AGPU_OPTION "--gene-counts".
 #ifndef AGPU_RESIDENT_STREAM_HPP
@@ -14,7 +14,7 @@
 #define HIP_CHECK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { set_last_error(std::string(#call) + ": " + hipGetErrorString(e_)); return AGPU_ERR_DEVICE; } } while (0)
 #define TRY(call) do { const int status_ = (call); if (status_ != AGPU_OK) return status_; } while (0)
 // AGPU_ALLOC_MESSAGE(buffer): what a failed allocation says, for the two files that do not say it like the others.  A file whose state keeps the peak of its buffers
-// (--splice-junctions, --allele-counts) defines ALLOC itself, with state.note_peak() for `then`.
+// (--splice-junctions, --allele-counts, --variant-sites) defines ALLOC itself, with state.note_peak() for `then`.
 #ifndef AGPU_ALLOC_MESSAGE
 #define AGPU_ALLOC_MESSAGE(buffer) AGPU_OPTION ": hipMalloc failed (" buffer ")"
 #endif
@@ -29,9 +29,9 @@ const int BLOCK = 256; // threads of a workgroup
 const uint64_t LAUNCH_ITEMS = 1ull << 30; // a kernel with one lane per record (or slot, or crossing) is launched in pieces that stay below 2^32 work-items
 
 inline unsigned int grid_for(uint64_t n) { return (unsigned int) std::max<uint64_t>((n + BLOCK - 1) / BLOCK, 1); }
-// launch(first, grid): the workgroups of items [first, first + LAUNCH_ITEMS) of n
-template <class Launch> inline void for_each_launch_piece(uint64_t n, Launch launch) {
-	for (uint64_t first = 0; first < n; first += LAUNCH_ITEMS) launch(first, grid_for(std::min(LAUNCH_ITEMS, n - first)));
+// launch(first, grid): the workgroups of items [first, first + items) of n; a kernel that gives an item more than one lane says how many items a launch may take
+template <class Launch> inline void for_each_launch_piece(uint64_t n, Launch launch, uint64_t items = LAUNCH_ITEMS) {
+	for (uint64_t first = 0; first < n; first += items) launch(first, grid_for(std::min(items, n - first)));
 }
 
 // a rocPRIM call with its temporary storage in a buffer of the consumer: call(nullptr, bytes) asks for the size, call(storage, bytes) does the work, timed as `name`

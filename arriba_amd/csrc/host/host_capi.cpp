@@ -1122,6 +1122,52 @@ int ahost_allele_counts_file(ahost_session* session, const char* input_path, con
 	} catch (const std::exception& e) { g_error = e.what(); return -1; }
 }
 
+// ---- --variant-sites (include/arriba_host.h) ----
+namespace {
+thread_local std::vector<agpu_variant_row> g_variant_rows; thread_local std::string g_variant_text;
+void variant_sites_with_header(ahost_session* session, const uint8_t* header, size_t header_size, const uint8_t* records, size_t size, uint32_t min_mapq, uint32_t min_baseq, uint32_t min_alt, uint32_t min_percent,
+                               std::vector<agpu_variant_row>& rows, agpu_variant_stats& stats) {
+	std::vector<uint32_t> tid_to_contig, ref_length;
+	if (header_size > 0) gene_count_references(session, header, header_size, tid_to_contig, ref_length);
+	variant_sites_of(allele_genome(session), tid_to_contig, ref_length, records, size, min_mapq, min_baseq, min_alt, min_percent, rows, stats);
+}
+}
+int ahost_variant_sites_of(ahost_session* session, const void* input_header, size_t header_size, const void* records, size_t size, uint32_t min_mapq, uint32_t min_baseq, uint32_t min_alt, uint32_t min_percent,
+                           const agpu_variant_row** rows, uint64_t* n_rows, agpu_variant_stats* stats) {
+	if (!session || (!input_header && header_size > 0) || (!records && size > 0) || !rows || !n_rows) { g_error = "null argument"; return -1; }
+	try {
+		agpu_variant_stats found;
+		variant_sites_with_header(session, (const uint8_t*) input_header, header_size, (const uint8_t*) records, size, min_mapq, min_baseq, min_alt, min_percent, g_variant_rows, found);
+		*rows = g_variant_rows.data(); *n_rows = g_variant_rows.size();
+		if (stats) *stats = found;
+		return 0;
+	} catch (const std::exception& e) { g_error = e.what(); return -1; }
+}
+int ahost_variant_sites_text(const ahost_depth_contigs* contigs, const agpu_variant_row* rows, uint64_t n_rows, const char** text, uint64_t* bytes) {
+	if (!contigs || (!rows && n_rows > 0) || !text || !bytes) { g_error = "null argument"; return -1; }
+	try { g_variant_text = variant_sites_text(*contigs, rows, n_rows); *text = g_variant_text.data(); *bytes = g_variant_text.size(); return 0; }
+	catch (const std::exception& e) { g_error = e.what(); return -1; }
+}
+int ahost_variant_sites_write(const ahost_depth_contigs* contigs, const agpu_variant_row* rows, uint64_t n_rows, const char* path) {
+	if (!contigs || (!rows && n_rows > 0) || !path) { g_error = "null argument"; return -1; }
+	try { virus_expression_write(variant_sites_text(*contigs, rows, n_rows), path); return 0; } // (the writer of a text through path.tmp)
+	catch (const std::exception& e) { g_error = e.what(); return -1; }
+}
+int ahost_variant_sites_file(ahost_session* session, const char* input_path, const char* path, uint32_t min_mapq, uint32_t min_baseq, uint32_t min_alt, uint32_t min_percent, agpu_variant_stats* stats) {
+	if (!session || !input_path || !path) { g_error = "null argument"; return -1; }
+	try {
+		std::vector<uint8_t> stream;
+		const uint64_t at = read_whole_bam(input_path, stream); // (SAM text comes out as the BAM stream of its alignments, behind a BAM header)
+		std::vector<agpu_variant_row> rows; agpu_variant_stats found;
+		variant_sites_with_header(session, stream.data(), at, stream.data() + at, stream.size() - at, min_mapq, min_baseq, min_alt, min_percent, rows, found);
+		DepthContigs contigs;
+		depth_contigs_of(stream.data(), at, contigs);
+		virus_expression_write(variant_sites_text(contigs.view(), rows.data(), rows.size()), path);
+		if (stats) *stats = found;
+		return 0;
+	} catch (const std::exception& e) { g_error = e.what(); return -1; }
+}
+
 // ---- --realign-reads (include/arriba_host.h) ----
 namespace {
 thread_local RealignPlan g_realign_plan; thread_local std::string g_realign_text, g_realign_kept;

@@ -56,7 +56,7 @@ void usage() {
 	             " -c FILE  chimeric alignments of STAR run with --chimOutType SeparateSAMold (Chimeric.out.sam): read in front of -x, which then adds read-throughs and tandem duplications only;\n"
 	             "          takes what -x takes.  The headers of -c and -x must list the same references in the same order, every record of -c needs a reference, the mates of\n"
 	             "          a split read of -c different first-in-pair flags; not together with\n"
-	             "          --sorted-bam, --supporting-alignments, --virus-expression, --coverage, --gene-counts, --splice-junctions, --allele-counts, --realign-reads, --rna-metrics\n"
+	             "          --sorted-bam, --supporting-alignments, --virus-expression, --coverage, --gene-counts, --splice-junctions, --allele-counts, --realign-reads, --rna-metrics, --variant-sites\n"
 	             " -g FILE  gene annotation (GTF)        -a FILE  assembly (FastA)          -o FILE  output file             -O FILE  discarded fusions\n"
 	             " -b FILE  blacklist                    -k FILE  known fusions             -t FILE  tags                    -p FILE  protein domains (GFF3)\n"
 	             " -d FILE  structural variants from WGS -D INT   max. distance to them (100000)\n"
@@ -90,7 +90,11 @@ void usage() {
 	             "                    with the contigs of -a: what scripts/run_arriba_on_prealigned_bam.sh of arriba feeds to STAR and passes on\n"
 	             " --rna-metrics FILE [--rrna-intervals FILE.bed]  the alignment QC table of -x: records by flag, MAPQ histogram, aligned bases by class (ribosomal -- the intervals of the BED\n"
 	             "                    file --, coding, UTR, intronic, intergenic), sense and antisense records, insert sizes with their median, and the coverage of gene bodies from 5' to\n"
-	             "                    3' in 100 bins: what Picard CollectRnaSeqMetrics / CollectInsertSizeMetrics, samtools flagstat and RSeQC are run for\n";
+	             "                    3' in 100 bins: what Picard CollectRnaSeqMetrics / CollectInsertSizeMetrics, samtools flagstat and RSeQC are run for\n"
+	             " --variant-sites FILE  the positions at which the records of -x show a base that differs from -a, a line per site: CONTIG POS REF ALT A C G T N DEL SKIP LOWQ, the counts as\n"
+	             "                    --allele-counts gives them there: the candidate sites of samtools mpileup | bcftools call -mv, without genotypes\n"
+	             " --variant-min-alt N  records that must show the base (default 3)    --variant-min-percent P  ... and their share of A + C + G + T, 0 to 100 (default 5)\n"
+	             " --variant-min-mapq N  records with a smaller MAPQ do not count (default 20)    --variant-min-baseq N  bases with a smaller quality are no evidence (default 13)\n";
 }
 
 }
@@ -114,7 +118,7 @@ int main(int argc, char** argv) {
 	require(argv[1][0] == '-' && argv[1][1] != '\0', std::string("cannot interpret the first argument: ") + argv[1]);
 	// the long options of this implementation are taken out first; the rest is the reference's getopt string (source/options.cpp:282)
 	std::vector<char*> arguments(1, argv[0]);
-	bool compression_given = false;
+	bool compression_given = false, variant_thresholds_given = false;
 	for (int a = 1; a < argc; ++a) {
 		if (strcmp(argv[a], "--host-ingest") == 0) options.host_ingest = 1;
 		else if (strcmp(argv[a], "--sorted-bam") == 0 && a + 1 < argc) { options.sorted_bam_file = argv[++a]; parent_exists(options.sorted_bam_file); }
@@ -133,6 +137,11 @@ int main(int argc, char** argv) {
 		else if (strcmp(argv[a], "--rrna-intervals") == 0 && a + 1 < argc) { options.rrna_intervals_file = argv[++a]; readable(options.rrna_intervals_file); }
 		else if (strcmp(argv[a], "--allele-min-mapq") == 0 && a + 1 < argc) { long value; require(parse_int(argv[++a], value) && value >= 0 && value <= 0xFFFFFFFFl, "invalid argument to --allele-min-mapq"); options.allele_min_mapq = (uint32_t) value; }
 		else if (strcmp(argv[a], "--allele-min-baseq") == 0 && a + 1 < argc) { long value; require(parse_int(argv[++a], value) && value >= 0 && value <= 0xFFFFFFFFl, "invalid argument to --allele-min-baseq"); options.allele_min_baseq = (uint32_t) value; }
+		else if (strcmp(argv[a], "--variant-sites") == 0 && a + 1 < argc) { options.variant_sites_file = argv[++a]; parent_exists(options.variant_sites_file); }
+		else if (strcmp(argv[a], "--variant-min-alt") == 0 && a + 1 < argc) { long value; require(parse_int(argv[++a], value) && value >= 0 && value <= 0xFFFFFFFFl, "invalid argument to --variant-min-alt"); options.variant_min_alt = (uint32_t) value; variant_thresholds_given = true; }
+		else if (strcmp(argv[a], "--variant-min-percent") == 0 && a + 1 < argc) { long value; require(parse_int(argv[++a], value) && value >= 0 && value <= 0xFFFFFFFFl, "invalid argument to --variant-min-percent"); options.variant_min_percent = (uint32_t) value; variant_thresholds_given = true; }
+		else if (strcmp(argv[a], "--variant-min-mapq") == 0 && a + 1 < argc) { long value; require(parse_int(argv[++a], value) && value >= 0 && value <= 0xFFFFFFFFl, "invalid argument to --variant-min-mapq"); options.variant_min_mapq = (uint32_t) value; variant_thresholds_given = true; }
+		else if (strcmp(argv[a], "--variant-min-baseq") == 0 && a + 1 < argc) { long value; require(parse_int(argv[++a], value) && value >= 0 && value <= 0xFFFFFFFFl, "invalid argument to --variant-min-baseq"); options.variant_min_baseq = (uint32_t) value; variant_thresholds_given = true; }
 		else if (strcmp(argv[a], "--supporting-window") == 0 && a + 1 < argc) { long window; require(parse_int(argv[++a], window) && window > 0 && window <= 0x7FFFFFFFl, "invalid argument to --supporting-window"); options.supporting_alignments_window = window; }
 		else if (strcmp(argv[a], "--device") == 0 && a + 1 < argc) { long device; require(parse_int(argv[++a], device) && device >= 0, "invalid argument to --device"); options.device_index = (int) device; }
 		else arguments.push_back(argv[a]);
@@ -140,6 +149,7 @@ int main(int argc, char** argv) {
 	require(!compression_given || options.sorted_bam_file != nullptr, "--sorted-bam-compression needs --sorted-bam");
 	require(!options.mark_duplicates || options.sorted_bam_file != nullptr, "--mark-duplicates needs --sorted-bam");
 	require(options.rrna_intervals_file == nullptr || options.rna_metrics_file != nullptr, "--rrna-intervals needs --rna-metrics");
+	require(!variant_thresholds_given || options.variant_sites_file != nullptr, "--variant-min-alt, --variant-min-percent, --variant-min-mapq and --variant-min-baseq need --variant-sites");
 	std::string interesting_contigs, viral_contigs;
 	bool seen[256]; memset(seen, 0, sizeof(seen));
 	bool blacklist_enabled = true;

@@ -562,6 +562,39 @@ typedef struct {
 int agpu_allele_counts(agpu_ctx* ctx, const agpu_allele_site* sites, uint64_t n_sites, const uint32_t* ref_length, uint32_t n_ref, uint32_t min_mapq, uint32_t min_baseq, const agpu_allele_row** rows,
                        agpu_allele_stats* stats /* may be NULL */);
 int agpu_allele_counts_allocated_bytes(agpu_ctx* ctx, uint64_t* bytes);
+/* --variant-sites: the positions at which the records of the last ingest show a base that differs from the assembly, found on the device while the stream is in HBM (DESIGN.md
+ * 4.21; arriba_amd/csrc/device/agpu_variants.hip, variant_core.hpp): the candidate sites of a variant caller with their full base counts, no genotypes.
+ *   agpu_variant_sites   behind agpu_ingest_finish, before the next agpu_ingest_begin on this context or its sibling (the refusals of agpu_allele_counts; the genome must be
+ *                        uploaded: REF is read from it).  ref_length: LN of every reference of the header of that ingest (n_ref of them, fewer than 2^30).  min_mapq, min_baseq:
+ *                        at most 255; min_alt: 1 .. 2^31-1; min_percent: 0 .. 100.  rows: the reported sites by (ref, pos); they belong to the context and are valid until the
+ *                        next call on it.  The "variant.*" buffers are freed before the call returns.
+ *   agpu_variant_sites_allocated_bytes   of those buffers: 0 outside the call
+ * ARRIBA_VARIANT_MAX_EVENTS (default and most 2^31): a call that finds more mismatch events is refused -- -a hardly matches the sample.
+ * ARRIBA_VARIANT_LAUNCH_RECORDS (a knob for the tests): the records of one launch of variant_event_kernel, at most 2^24.
+ * ARRIBA_ALLELE_PLAIN_ATOMICS, ARRIBA_ALLELE_NO_BITMAP: of the counters, as for agpu_allele_counts. */
+typedef struct {
+	uint32_t ref;                  /* index of the reference in the header */
+	int32_t pos;                   /* 0-based (the file prints it + 1) */
+	uint32_t a, c, g, t, n, del, skip, lowq; /* as agpu_allele_row: what agpu_allele_counts gives for the position with the same min_mapq and min_baseq */
+	uint8_t ref_base;              /* the upper-case base of the assembly: A, C, G or T */
+	uint8_t alt_mask;              /* bit 0: A is a reported alt, 1: C, 2: G, 3: T; never 0, never the bit of ref_base */
+	uint8_t reserved[2];
+} agpu_variant_row;
+typedef struct {
+	uint64_t records;              /* of the stream */
+	uint64_t contributing;         /* records that pass the filter */
+	uint64_t events;               /* mismatch events: bases A/C/G/T of at least min_baseq over another base A/C/G/T of the assembly */
+	uint64_t runs;                 /* distinct (site, alt) among them */
+	uint64_t candidates;           /* sites with an alt of at least min_alt events */
+	uint64_t reported;             /* rows: candidates with an alt that also passes min_percent */
+	uint64_t inconsistent;         /* candidates whose events disagree with their counters: 0, or the call fails */
+	uint64_t peak_bytes;           /* of the "variant.*" buffers (0 on the host) */
+	double seconds[5];             /* count pass; fill pass; sort, runs and candidates; the counters; the rows (device: from a HIP event in front of the first launch of the pass to
+	                                  one behind its last -- the read-backs and allocations between two passes are in none of them --, 0 on the host) */
+} agpu_variant_stats;
+int agpu_variant_sites(agpu_ctx* ctx, const uint32_t* ref_length, uint32_t n_ref, uint32_t min_mapq, uint32_t min_baseq, uint32_t min_alt, uint32_t min_percent, const agpu_variant_row** rows, uint64_t* n_rows,
+                       agpu_variant_stats* stats /* may be NULL */);
+int agpu_variant_sites_allocated_bytes(agpu_ctx* ctx, uint64_t* bytes);
 /* --realign-reads: the records of the last ingest split into the templates that must be aligned again and the templates that are passed on, both as SAM text (fields 1-11, what
  * `samtools view` prints), formatted on the device while the stream is in HBM (arriba_amd/csrc/device/agpu_realign.hip, realign_core.hpp).
  *   agpu_realign_begin   behind agpu_ingest_finish, before the next agpu_ingest_begin on this context or its sibling (the refusals of agpu_depth_begin).  in_assembly: a byte per

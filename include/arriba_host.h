@@ -242,6 +242,22 @@ int ahost_allele_counts_of(ahost_session* session, const void* input_header, siz
 int ahost_allele_counts_text(const ahost_allele_sites* sites, const agpu_allele_row* rows, uint64_t n_rows, const char** text, uint64_t* bytes);
 int ahost_allele_counts_write(const ahost_allele_sites* sites, const agpu_allele_row* rows, uint64_t n_rows, const char* path);
 int ahost_allele_counts_file(ahost_session* session, const char* input_path, const char* sites_path, const char* path, uint32_t min_mapq, uint32_t min_baseq, agpu_allele_stats* stats);
+/* ---- --variant-sites: the host side of agpu_variant_sites (include/arriba_gpu.h) -- the positions at which the records show a base that differs from the assembly, with their
+ * base counts (the rule: DESIGN.md 4.21).  A row table is what agpu_variant_sites gives: agpu_variant_row, ordered by (ref, pos) ----
+ *   ahost_variant_sites_of         arriba_amd/csrc/device/variant_core.hpp and allele_core.hpp stepped on the host over BAM records in host memory (the device's comparator; the
+ *                                  CPU tier).  input_header: the head of the input the records come from (a BAM header, or the '@' lines of SAM text): its references are looked
+ *                                  up among the contigs of the session by name (REF from its assembly), their LN bounds the positions.  min_mapq, min_baseq: at most 255;
+ *                                  min_alt: 1 .. 2^31-1; min_percent: 0 .. 100.  The rows are valid until the next call on the thread
+ *   ahost_variant_sites_text       a row table and the names of the references (ahost_depth_contigs_of / _of_session) -> the text of the file:
+ *                                  "#CONTIG\tPOS\tREF\tALT\tA\tC\tG\tT\tN\tDEL\tSKIP\tLOWQ\n", then a line per row, the reported alts joined by ',' in the order A, C, G, T; valid
+ *                                  until the next call on the thread
+ *   ahost_variant_sites_write      that text into `path`, through path.tmp; on a failure nothing is left behind
+ *   ahost_variant_sites_file       all of it for a file (BAM in BGZF, gzip or raw; SAM text): what --host-ingest runs; stats may be NULL */
+int ahost_variant_sites_of(ahost_session* session, const void* input_header, size_t header_size, const void* records, size_t size, uint32_t min_mapq, uint32_t min_baseq, uint32_t min_alt, uint32_t min_percent,
+                           const agpu_variant_row** rows, uint64_t* n_rows, agpu_variant_stats* stats /* may be NULL */);
+int ahost_variant_sites_text(const ahost_depth_contigs* contigs, const agpu_variant_row* rows, uint64_t n_rows, const char** text, uint64_t* bytes);
+int ahost_variant_sites_write(const ahost_depth_contigs* contigs, const agpu_variant_row* rows, uint64_t n_rows, const char* path);
+int ahost_variant_sites_file(ahost_session* session, const char* input_path, const char* path, uint32_t min_mapq, uint32_t min_baseq, uint32_t min_alt, uint32_t min_percent, agpu_variant_stats* stats);
 /* ---- --realign-reads: the host side of agpu_realign_* (include/arriba_gpu.h) -- the records split into the templates to realign and the templates to keep, as SAM text (the
  * rule: DESIGN.md 4.18) ----
  *   ahost_realign_plan_of          what the split needs from the assembly of the session for the references of input_header (a BAM header, or the '@' lines of SAM text): a byte

@@ -104,7 +104,17 @@ typedef struct {
 	                                         arriba_workflow_run's sample; the samples of a session say theirs with arriba_workflow_rna_metrics.  Not for one sample over several ranks. */
 	const char* separate_chimeric_file;   /* -c: the chimeric alignments of STAR --chimOutType SeparateSAMold (Chimeric.out.sam, or its BAM), read in front of chimeric_bam_file as the
 	                                         reference reads them (source/arriba.cpp:123-130); NULL (and a zero-initialised struct) = none.  Takes what chimeric_bam_file takes.  Refused
-	                                         with any of the side outputs above, over several ranks, and when the two headers do not list the same references in the same order. */
+	                                         with any of the side outputs above and below, over several ranks, and when the two headers do not list the same references in the same order. */
+	const char* variant_sites_file;       /* --variant-sites; NULL (and a zero-initialised struct) = none.  The positions at which the records of chimeric_bam_file show a base that differs from
+	                                         assembly_file, a line per site behind a header line: CONTIG POS REF ALT A C G T N DEL SKIP LOWQ, by reference in header order and position -- the
+	                                         candidate sites of a variant caller with the counts --allele-counts gives there, no genotypes --, found behind read_chimeric_alignments from the
+	                                         record stream in HBM (include/arriba_gpu.h: agpu_variant_sites; with host_ingest: the same code stepped on the host).  Of
+	                                         arriba_workflow_run's sample; the samples of a session say theirs with arriba_workflow_variant_sites.  Not for one sample over several ranks.
+	                                         The four thresholds below without it are refused. */
+	uint32_t variant_min_alt;             /* --variant-min-alt: a site is a candidate when a base that differs from REF is seen this often; 1 .. 2^31-1; arriba_workflow_default_options sets 3 */
+	uint32_t variant_min_percent;         /* --variant-min-percent: ... and reported when that is at least this share of A + C + G + T; 0 .. 100; arriba_workflow_default_options sets 5 */
+	uint32_t variant_min_mapq;            /* --variant-min-mapq: records with a smaller MAPQ do not count; at most 255; arriba_workflow_default_options sets 20 */
+	uint32_t variant_min_baseq;           /* --variant-min-baseq: bases with a smaller quality go to LOWQ and are no evidence; at most 255; arriba_workflow_default_options sets 13 */
 } arriba_workflow_options;
 
 /* what the reference prints as "(remaining=N)" / "(total=N)" / "(marked=N)", in the order of the stages; stage names as in the reference's source */
@@ -151,6 +161,7 @@ typedef struct { /* seconds of one sample, by part (wall clock of the calling th
 	double allele_counts;    /* --allele-counts: the sites placed and sorted, the count, the rows, the copy, the file (inside `ingest`; beside the sample in front when the ingest was finished ahead) */
 	double realign;          /* --realign-reads: name ids and claims, verdicts, scans, the windows of text, the copies, the files (inside `ingest`; beside the sample in front when the ingest was finished ahead) */
 	double rna_metrics;      /* --rna-metrics: the region track when it is built, the kernel, the copy, the file (inside `ingest`; beside the sample in front when the ingest was finished ahead) */
+	double variant_sites;    /* --variant-sites: the two event passes, sort and runs, the counters, the rows, the copy, the file (inside `ingest`; beside the sample in front when the ingest was finished ahead) */
 } arriba_workflow_timing;
 /* options->chimeric_bam_file, output_file and discarded_output_file are not used by open (they belong to a sample); NULL + arriba_workflow_last_error() on failure */
 arriba_workflow_session* arriba_workflow_open(const arriba_workflow_options* options);
@@ -194,6 +205,9 @@ int arriba_workflow_allele_counts(arriba_workflow_session* session, const char* 
 int arriba_workflow_realign(arriba_workflow_session* session, const char* reads_path, const char* kept_path);
 /* --rna-metrics and --rrna-intervals of the sample that is submitted NEXT, in the same way; path NULL: none.  The table is written by the thread that finishes its ingest. */
 int arriba_workflow_rna_metrics(arriba_workflow_session* session, const char* path, const char* rrna_intervals_path);
+/* --variant-sites, --variant-min-mapq, --variant-min-baseq, --variant-min-alt and --variant-min-percent of the sample that is submitted NEXT, in the same way; path NULL: none.  The
+ * table is written by the thread that finishes its ingest. */
+int arriba_workflow_variant_sites(arriba_workflow_session* session, const char* path, uint32_t min_mapq, uint32_t min_baseq, uint32_t min_alt, uint32_t min_percent);
 /* (If the device runs out of memory while two samples are in flight, arriba_workflow_sample throws away what was fed ahead, closes the second lane, runs its sample again with the device
  * to itself and submits the other sample again behind it -- once; a sample that does not fit the device alone fails the call.  INTEGRATION.md, "Memory".) */
 /* on: arriba_workflow_sample returns when the last output file of the sample (-O if given, else -o) has everything it needs off the device; the file is formatted and written
