@@ -191,6 +191,16 @@ class VariantStats(ctypes.Structure):
     _fields_ = [(name, c_uint64) for name in ("records", "contributing", "events", "runs", "candidates", "reported", "inconsistent", "peak_bytes")] + [("seconds", ctypes.c_double * 5)]
 
 
+class IndelRow(ctypes.Structure):
+    """agpu_indel_row: a reported event of --indel-sites"""
+    _fields_ = [("ref", c_uint32), ("pos", c_int32), ("bases", c_uint64), ("length", c_uint32), ("support", c_uint32), ("depth", c_uint32), ("type", c_uint8), ("ref_base", c_uint8), ("reserved", c_uint8 * 2)]
+
+
+class IndelStats(ctypes.Structure):
+    """agpu_indel_stats: what agpu_indel_sites / ahost_indel_sites_of count"""
+    _fields_ = [(name, c_uint64) for name in ("records", "contributing", "operations", "events", "unkeyed_insertions", "shift_capped", "runs", "candidates", "sites", "reported", "peak_bytes")] + [("seconds", ctypes.c_double * 5)]
+
+
 class RealignStats(ctypes.Structure):
     """agpu_realign_stats: what agpu_realign_end / ahost_realign_split_of count"""
     _fields_ = [(name, c_uint64) for name in ("records", "templates", "realign_templates", "kept_templates", "dropped_secondary", "extra", "orphans", "placeholder_cigar", "realign_bytes", "kept_bytes")] + [
@@ -401,6 +411,8 @@ def bind_device_api(lib, prefix="agpu_"):
         "allele_counts_allocated_bytes": (c_int, [ctx, POINTER(c_uint64)]),
         "variant_sites": (c_int, [ctx, c_void_p, c_uint32, c_uint32, c_uint32, c_uint32, c_uint32, POINTER(POINTER(VariantRow)), POINTER(c_uint64), POINTER(VariantStats)]),
         "variant_sites_allocated_bytes": (c_int, [ctx, POINTER(c_uint64)]),
+        "indel_sites": (c_int, [ctx, c_void_p, c_uint32, c_uint32, c_uint32, c_uint32, POINTER(POINTER(IndelRow)), POINTER(c_uint64), POINTER(IndelStats)]),
+        "indel_sites_allocated_bytes": (c_int, [ctx, POINTER(c_uint64)]),
         "realign_begin": (c_int, [ctx, c_void_p, c_void_p, c_void_p, c_uint32, c_int, POINTER(RealignInfo)]),
         "realign_next": (c_int, [ctx, c_int, c_void_p, c_uint64, POINTER(c_uint64)]),
         "realign_end": (c_int, [ctx, POINTER(RealignStats)]),
@@ -536,6 +548,10 @@ def bind_host_api(lib):
         "ahost_variant_sites_text": (c_int, [POINTER(DepthContigs), POINTER(VariantRow), c_uint64, POINTER(c_void_p), POINTER(c_uint64)]),
         "ahost_variant_sites_write": (c_int, [POINTER(DepthContigs), POINTER(VariantRow), c_uint64, c_char_p]),
         "ahost_variant_sites_file": (c_int, [session, c_char_p, c_char_p, c_uint32, c_uint32, c_uint32, c_uint32, POINTER(VariantStats)]),
+        "ahost_indel_sites_of": (c_int, [session, c_void_p, c_size_t, c_void_p, c_size_t, c_uint32, c_uint32, c_uint32, POINTER(POINTER(IndelRow)), POINTER(c_uint64), POINTER(IndelStats)]),
+        "ahost_indel_sites_text": (c_int, [session, POINTER(DepthContigs), POINTER(IndelRow), c_uint64, POINTER(c_void_p), POINTER(c_uint64)]),
+        "ahost_indel_sites_write": (c_int, [session, POINTER(DepthContigs), POINTER(IndelRow), c_uint64, c_char_p]),
+        "ahost_indel_sites_file": (c_int, [session, c_char_p, c_char_p, c_uint32, c_uint32, c_uint32, POINTER(IndelStats)]),
         "ahost_realign_plan_of": (c_int, [session, c_void_p, c_size_t, POINTER(RealignPlan)]),
         "ahost_realign_plan_of_session": (c_int, [session, POINTER(RealignPlan)]),
         "ahost_realign_split_of": (c_int, [session, c_void_p, c_size_t, c_void_p, c_size_t, c_int, POINTER(c_void_p), POINTER(c_uint64), POINTER(c_void_p), POINTER(c_uint64), POINTER(RealignStats)]),
@@ -568,7 +584,7 @@ class WorkflowOptions(ctypes.Structure):
                                               "protein_domains_file", "genomic_breakpoints_file", "interesting_contigs", "viral_contigs", "gtf_features")] + [
         ("device", Params), ("min_itd_support", c_uint32), ("min_itd_allele_fraction", c_float), ("high_expression_quantile", c_float), ("min_spliced_events", c_uint32), ("min_anchor_length", c_uint32),
         ("max_homolog_identity", c_float), ("top_viral_contigs", c_uint32), ("viral_contig_min_covered_fraction", c_float), ("max_genomic_breakpoint_distance", c_int32),
-        ("print_extra_info_for_discarded_fusions", c_uint8), ("fill_sequence_gaps", c_uint8), ("device_index", c_int), ("log_to_stdout", c_uint8), ("host_ingest", c_uint8), ("sorted_bam_file", c_char_p), ("supporting_alignments_prefix", c_char_p), ("supporting_alignments_window", ctypes.c_int64), ("sorted_bam_compression", c_int), ("virus_expression_file", c_char_p), ("coverage_file", c_char_p), ("mark_duplicates", c_int), ("gene_counts_file", c_char_p), ("splice_junctions_file", c_char_p), ("allele_sites_file", c_char_p), ("allele_counts_file", c_char_p), ("allele_min_mapq", c_uint32), ("allele_min_baseq", c_uint32), ("realign_reads_file", c_char_p), ("realign_kept_file", c_char_p), ("rna_metrics_file", c_char_p), ("rrna_intervals_file", c_char_p), ("separate_chimeric_file", c_char_p), ("variant_sites_file", c_char_p), ("variant_min_alt", c_uint32), ("variant_min_percent", c_uint32), ("variant_min_mapq", c_uint32), ("variant_min_baseq", c_uint32)]
+        ("print_extra_info_for_discarded_fusions", c_uint8), ("fill_sequence_gaps", c_uint8), ("device_index", c_int), ("log_to_stdout", c_uint8), ("host_ingest", c_uint8), ("sorted_bam_file", c_char_p), ("supporting_alignments_prefix", c_char_p), ("supporting_alignments_window", ctypes.c_int64), ("sorted_bam_compression", c_int), ("virus_expression_file", c_char_p), ("coverage_file", c_char_p), ("mark_duplicates", c_int), ("gene_counts_file", c_char_p), ("splice_junctions_file", c_char_p), ("allele_sites_file", c_char_p), ("allele_counts_file", c_char_p), ("allele_min_mapq", c_uint32), ("allele_min_baseq", c_uint32), ("realign_reads_file", c_char_p), ("realign_kept_file", c_char_p), ("rna_metrics_file", c_char_p), ("rrna_intervals_file", c_char_p), ("separate_chimeric_file", c_char_p), ("variant_sites_file", c_char_p), ("variant_min_alt", c_uint32), ("variant_min_percent", c_uint32), ("variant_min_mapq", c_uint32), ("variant_min_baseq", c_uint32), ("indel_sites_file", c_char_p), ("indel_min_alt", c_uint32), ("indel_min_percent", c_uint32), ("indel_min_mapq", c_uint32)]
 
 
 class WorkflowStage(ctypes.Structure):
@@ -580,7 +596,7 @@ class WorkflowReport(ctypes.Structure):
 
 
 class WorkflowTiming(ctypes.Structure):
-    _fields_ = [(name, ctypes.c_double) for name in ("total", "feed", "ingest", "adopt", "stages", "filter_mismappers", "output", "output_results", "output_rows", "output_format", "feed_read", "feed_push", "feed_total", "exchange_parts", "exchange_verdicts", "exchange_rows", "shard_fragments", "exchanged_bytes", "sorted_bam", "supporting_alignments", "virus_expression", "coverage", "gene_counts", "splice_junctions", "allele_counts", "realign", "rna_metrics", "variant_sites")]
+    _fields_ = [(name, ctypes.c_double) for name in ("total", "feed", "ingest", "adopt", "stages", "filter_mismappers", "output", "output_results", "output_rows", "output_format", "feed_read", "feed_push", "feed_total", "exchange_parts", "exchange_verdicts", "exchange_rows", "shard_fragments", "exchanged_bytes", "sorted_bam", "supporting_alignments", "virus_expression", "coverage", "gene_counts", "splice_junctions", "allele_counts", "realign", "rna_metrics", "variant_sites", "indel_sites")]
 
 
 WORKFLOW_MAX, WORKFLOW_MIN, WORKFLOW_SUM = 0, 1, 2
@@ -622,6 +638,7 @@ def workflow_library():
         lib.arriba_workflow_realign.argtypes = [c_void_p, c_char_p, c_char_p]; lib.arriba_workflow_realign.restype = c_int
         lib.arriba_workflow_rna_metrics.argtypes = [c_void_p, c_char_p, c_char_p]; lib.arriba_workflow_rna_metrics.restype = c_int
         lib.arriba_workflow_variant_sites.argtypes = [c_void_p, c_char_p, c_uint32, c_uint32, c_uint32, c_uint32]; lib.arriba_workflow_variant_sites.restype = c_int
+        lib.arriba_workflow_indel_sites.argtypes = [c_void_p, c_char_p, c_uint32, c_uint32, c_uint32]; lib.arriba_workflow_indel_sites.restype = c_int
         lib.arriba_workflow_sorted_bam_compression.argtypes = [c_void_p, c_int]; lib.arriba_workflow_sorted_bam_compression.restype = c_int
         lib.arriba_workflow_sorted_bam_mark_duplicates.argtypes = [c_void_p, c_int]; lib.arriba_workflow_sorted_bam_mark_duplicates.restype = c_int
         lib.arriba_workflow_cancel.argtypes = [c_void_p]; lib.arriba_workflow_cancel.restype = c_int

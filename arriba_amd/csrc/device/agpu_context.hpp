@@ -178,6 +178,12 @@ struct VariantState : StreamConsumer {
 	agpu_variant_stats stats = {};
 	std::vector<agpu_variant_row> rows;
 };
+// --indel-sites (agpu_indels.hip): the "indel.*" buffers live inside one agpu_indel_sites; the rows stay until the next call
+struct IndelState : StreamConsumer {
+	using StreamConsumer::StreamConsumer;
+	agpu_indel_stats stats = {};
+	std::vector<agpu_indel_row> rows;
+};
 // --realign-reads (agpu_realign.hip): the "realign.*" buffers live between agpu_realign_begin and _end
 struct RealignState : StreamConsumer {
 	using StreamConsumer::StreamConsumer;
@@ -301,6 +307,7 @@ struct agpu_ctx {
 	agpu::AlleleState allele{consumers};         // --allele-counts (agpu_alleles.hip)
 	agpu::RnametricsState rnametrics{consumers}; // --rna-metrics (agpu_rnametrics.hip)
 	agpu::VariantState variant{consumers};       // --variant-sites (agpu_variants.hip)
+	agpu::IndelState indel{consumers};           // --indel-sites (agpu_indels.hip)
 	agpu::RealignState realign{consumers};       // --realign-reads (agpu_realign.hip)
 	// A pushed piece: copied on the context's stream (piece_copied: the caller's buffer is free), unwrapped and CRC-checked on a stream of its own (piece_stream; piece_ready: its
 	// bytes are in the stream, piece_done: the raw bytes are not needed any more), so that the copy of the next piece never waits for a kernel; AGPU_PIECE_SLOTS raw buffers in turn

@@ -1,5 +1,5 @@
 // arriba_amd/csrc/device/resident_stream.hpp -- what the consumers of the record stream that the last ingest left in HBM have in common (--sorted-bam, --mark-duplicates,
-// --supporting-alignments, --virus-expression, --coverage, --gene-counts, --splice-junctions, --allele-counts, --realign-reads, --rna-metrics, --variant-sites): the guard in front of the stream
+// --supporting-alignments, --virus-expression, --coverage, --gene-counts, --splice-junctions, --allele-counts, --realign-reads, --rna-metrics, --variant-sites, --indel-sites): the guard in front of the stream
 // (resident_stream), the macros and launch helpers of their host code, and the frame of those that do their work inside one call (one_shot).  Their state is a StreamConsumer
 // (agpu_context.hpp).  A file names its option before it includes this header: #define AGPU_OPTION "--gene-counts".
 #ifndef AGPU_RESIDENT_STREAM_HPP
@@ -14,7 +14,7 @@
 #define HIP_CHECK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { set_last_error(std::string(#call) + ": " + hipGetErrorString(e_)); return AGPU_ERR_DEVICE; } } while (0)
 #define TRY(call) do { const int status_ = (call); if (status_ != AGPU_OK) return status_; } while (0)
 // AGPU_ALLOC_MESSAGE(buffer): what a failed allocation says, for the two files that do not say it like the others.  A file whose state keeps the peak of its buffers
-// (--splice-junctions, --allele-counts, --variant-sites) defines ALLOC itself, with state.note_peak() for `then`.
+// (--splice-junctions, --allele-counts, --variant-sites, --indel-sites) defines ALLOC itself, with state.note_peak() for `then`.
 #ifndef AGPU_ALLOC_MESSAGE
 #define AGPU_ALLOC_MESSAGE(buffer) AGPU_OPTION ": hipMalloc failed (" buffer ")"
 #endif

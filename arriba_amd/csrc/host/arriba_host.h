@@ -324,6 +324,12 @@ std::string allele_counts_text(const AlleleSiteList& list, const agpu_allele_row
 void variant_sites_of(const agpu::GenomeView& genome, const std::vector<uint32_t>& tid_to_contig, const std::vector<uint32_t>& ref_length, const uint8_t* records, uint64_t size, uint32_t min_mapq, uint32_t min_baseq,
                       uint32_t min_alt, uint32_t min_percent, std::vector<agpu_variant_row>& rows, agpu_variant_stats& stats);
 std::string variant_sites_text(const ahost_depth_contigs& contigs, const agpu_variant_row* rows, uint64_t n_rows);
+// --indel-sites on the host (indel_sites.cpp): arriba_amd/csrc/device/indel_core.hpp and allele_core.hpp stepped over records in host memory, normalised against the assembly of a
+// session (genome: pointers into the session) -- the comparator of agpu_indels.hip, and what --host-ingest and the CPU tier run; and the text of the file from a row table, the
+// host's or the device's (the deleted bases are read from the assembly: tid_to_contig says where the references of the header lie in it)
+void indel_sites_of(const agpu::GenomeView& genome, const std::vector<uint32_t>& tid_to_contig, const std::vector<uint32_t>& ref_length, const uint8_t* records, uint64_t size, uint32_t min_mapq, uint32_t min_alt,
+                    uint32_t min_percent, std::vector<agpu_indel_row>& rows, agpu_indel_stats& stats);
+std::string indel_sites_text(const agpu::GenomeView& genome, const std::vector<uint32_t>& tid_to_contig, const ahost_depth_contigs& contigs, const agpu_indel_row* rows, uint64_t n_rows);
 // --realign-reads on the host (realign_split.cpp): which references of a header are contigs of the assembly and the header of the file of the kept templates; and
 // arriba_amd/csrc/device/realign_core.hpp stepped over records in host memory -- the comparator of agpu_realign.hip, and what --host-ingest and the CPU tier run.  kept: the lines
 // without the header (empty unless want_kept)

@@ -1168,6 +1168,61 @@ int ahost_variant_sites_file(ahost_session* session, const char* input_path, con
 	} catch (const std::exception& e) { g_error = e.what(); return -1; }
 }
 
+// ---- --indel-sites (include/arriba_host.h) ----
+namespace {
+thread_local std::vector<agpu_indel_row> g_indel_rows; thread_local std::string g_indel_text;
+void indel_sites_with_header(ahost_session* session, const uint8_t* header, size_t header_size, const uint8_t* records, size_t size, uint32_t min_mapq, uint32_t min_alt, uint32_t min_percent,
+                             std::vector<agpu_indel_row>& rows, agpu_indel_stats& stats) {
+	std::vector<uint32_t> tid_to_contig, ref_length;
+	if (header_size > 0) gene_count_references(session, header, header_size, tid_to_contig, ref_length);
+	indel_sites_of(allele_genome(session), tid_to_contig, ref_length, records, size, min_mapq, min_alt, min_percent, rows, stats);
+}
+// the text of a row table whose references are `contigs`: they are looked up among the contigs of the session by name, as gene_count_references looks up those of a header
+std::string indel_sites_text_of(ahost_session* session, const ahost_depth_contigs& contigs, const agpu_indel_row* rows, uint64_t n_rows) {
+	std::vector<uint32_t> tid_to_contig(contigs.n_ref, 0xFFFFFFFFu);
+	for (uint32_t t = 0; t < contigs.n_ref; ++t) {
+		std::map<std::string, contig_t>::const_iterator known = session->contigs.by_name.find(remove_chr(std::string(contigs.names + contigs.name_offset[t], contigs.name_offset[t + 1] - contigs.name_offset[t])));
+		if (known != session->contigs.by_name.end()) tid_to_contig[t] = known->second;
+	}
+	return indel_sites_text(allele_genome(session), tid_to_contig, contigs, rows, n_rows);
+}
+}
+int ahost_indel_sites_of(ahost_session* session, const void* input_header, size_t header_size, const void* records, size_t size, uint32_t min_mapq, uint32_t min_alt, uint32_t min_percent,
+                         const agpu_indel_row** rows, uint64_t* n_rows, agpu_indel_stats* stats) {
+	if (!session || (!input_header && header_size > 0) || (!records && size > 0) || !rows || !n_rows) { g_error = "null argument"; return -1; }
+	try {
+		agpu_indel_stats found;
+		indel_sites_with_header(session, (const uint8_t*) input_header, header_size, (const uint8_t*) records, size, min_mapq, min_alt, min_percent, g_indel_rows, found);
+		*rows = g_indel_rows.data(); *n_rows = g_indel_rows.size();
+		if (stats) *stats = found;
+		return 0;
+	} catch (const std::exception& e) { g_error = e.what(); return -1; }
+}
+int ahost_indel_sites_text(ahost_session* session, const ahost_depth_contigs* contigs, const agpu_indel_row* rows, uint64_t n_rows, const char** text, uint64_t* bytes) {
+	if (!session || !contigs || (!rows && n_rows > 0) || !text || !bytes) { g_error = "null argument"; return -1; }
+	try { g_indel_text = indel_sites_text_of(session, *contigs, rows, n_rows); *text = g_indel_text.data(); *bytes = g_indel_text.size(); return 0; }
+	catch (const std::exception& e) { g_error = e.what(); return -1; }
+}
+int ahost_indel_sites_write(ahost_session* session, const ahost_depth_contigs* contigs, const agpu_indel_row* rows, uint64_t n_rows, const char* path) {
+	if (!session || !contigs || (!rows && n_rows > 0) || !path) { g_error = "null argument"; return -1; }
+	try { virus_expression_write(indel_sites_text_of(session, *contigs, rows, n_rows), path); return 0; } // (the writer of a text through path.tmp)
+	catch (const std::exception& e) { g_error = e.what(); return -1; }
+}
+int ahost_indel_sites_file(ahost_session* session, const char* input_path, const char* path, uint32_t min_mapq, uint32_t min_alt, uint32_t min_percent, agpu_indel_stats* stats) {
+	if (!session || !input_path || !path) { g_error = "null argument"; return -1; }
+	try {
+		std::vector<uint8_t> stream;
+		const uint64_t at = read_whole_bam(input_path, stream); // (SAM text comes out as the BAM stream of its alignments, behind a BAM header)
+		std::vector<agpu_indel_row> rows; agpu_indel_stats found;
+		indel_sites_with_header(session, stream.data(), at, stream.data() + at, stream.size() - at, min_mapq, min_alt, min_percent, rows, found);
+		DepthContigs contigs;
+		depth_contigs_of(stream.data(), at, contigs);
+		virus_expression_write(indel_sites_text_of(session, contigs.view(), rows.data(), rows.size()), path);
+		if (stats) *stats = found;
+		return 0;
+	} catch (const std::exception& e) { g_error = e.what(); return -1; }
+}
+
 // ---- --realign-reads (include/arriba_host.h) ----
 namespace {
 thread_local RealignPlan g_realign_plan; thread_local std::string g_realign_text, g_realign_kept;

@@ -56,7 +56,7 @@ void usage() {
 	             " -c FILE  chimeric alignments of STAR run with --chimOutType SeparateSAMold (Chimeric.out.sam): read in front of -x, which then adds read-throughs and tandem duplications only;\n"
 	             "          takes what -x takes.  The headers of -c and -x must list the same references in the same order, every record of -c needs a reference, the mates of\n"
 	             "          a split read of -c different first-in-pair flags; not together with\n"
-	             "          --sorted-bam, --supporting-alignments, --virus-expression, --coverage, --gene-counts, --splice-junctions, --allele-counts, --realign-reads, --rna-metrics, --variant-sites\n"
+	             "          --sorted-bam, --supporting-alignments, --virus-expression, --coverage, --gene-counts, --splice-junctions, --allele-counts, --realign-reads, --rna-metrics, --variant-sites, --indel-sites\n"
 	             " -g FILE  gene annotation (GTF)        -a FILE  assembly (FastA)          -o FILE  output file             -O FILE  discarded fusions\n"
 	             " -b FILE  blacklist                    -k FILE  known fusions             -t FILE  tags                    -p FILE  protein domains (GFF3)\n"
 	             " -d FILE  structural variants from WGS -D INT   max. distance to them (100000)\n"
@@ -94,7 +94,12 @@ void usage() {
 	             " --variant-sites FILE  the positions at which the records of -x show a base that differs from -a, a line per site: CONTIG POS REF ALT A C G T N DEL SKIP LOWQ, the counts as\n"
 	             "                    --allele-counts gives them there: the candidate sites of samtools mpileup | bcftools call -mv, without genotypes\n"
 	             " --variant-min-alt N  records that must show the base (default 3)    --variant-min-percent P  ... and their share of A + C + G + T, 0 to 100 (default 5)\n"
-	             " --variant-min-mapq N  records with a smaller MAPQ do not count (default 20)    --variant-min-baseq N  bases with a smaller quality are no evidence (default 13)\n";
+	             " --variant-min-mapq N  records with a smaller MAPQ do not count (default 20)    --variant-min-baseq N  bases with a smaller quality are no evidence (default 13)\n"
+	             " --indel-sites FILE  the insertions and deletions the records of -x carry in their CIGARs, moved to the left as far as -a allows, a line per distinct event: CONTIG POS REF TYPE\n"
+	             "                    LENGTH BASES SUPPORT DEPTH (POS and REF: the base in front of it; DEPTH: the records over that base): the candidate indels of samtools mpileup |\n"
+	             "                    bcftools call -mv, without genotypes; insertions of more than 28 bases or with an N are counted, not listed\n"
+	             " --indel-min-alt N  records that must carry the event (default 3)    --indel-min-percent P  ... and their share of DEPTH, 0 to 100 (default 5)\n"
+	             " --indel-min-mapq N  records with a smaller MAPQ do not count (default 20)\n";
 }
 
 }
@@ -118,7 +123,7 @@ int main(int argc, char** argv) {
 	require(argv[1][0] == '-' && argv[1][1] != '\0', std::string("cannot interpret the first argument: ") + argv[1]);
 	// the long options of this implementation are taken out first; the rest is the reference's getopt string (source/options.cpp:282)
 	std::vector<char*> arguments(1, argv[0]);
-	bool compression_given = false, variant_thresholds_given = false;
+	bool compression_given = false, variant_thresholds_given = false, indel_thresholds_given = false;
 	for (int a = 1; a < argc; ++a) {
 		if (strcmp(argv[a], "--host-ingest") == 0) options.host_ingest = 1;
 		else if (strcmp(argv[a], "--sorted-bam") == 0 && a + 1 < argc) { options.sorted_bam_file = argv[++a]; parent_exists(options.sorted_bam_file); }
@@ -142,6 +147,10 @@ int main(int argc, char** argv) {
 		else if (strcmp(argv[a], "--variant-min-percent") == 0 && a + 1 < argc) { long value; require(parse_int(argv[++a], value) && value >= 0 && value <= 0xFFFFFFFFl, "invalid argument to --variant-min-percent"); options.variant_min_percent = (uint32_t) value; variant_thresholds_given = true; }
 		else if (strcmp(argv[a], "--variant-min-mapq") == 0 && a + 1 < argc) { long value; require(parse_int(argv[++a], value) && value >= 0 && value <= 0xFFFFFFFFl, "invalid argument to --variant-min-mapq"); options.variant_min_mapq = (uint32_t) value; variant_thresholds_given = true; }
 		else if (strcmp(argv[a], "--variant-min-baseq") == 0 && a + 1 < argc) { long value; require(parse_int(argv[++a], value) && value >= 0 && value <= 0xFFFFFFFFl, "invalid argument to --variant-min-baseq"); options.variant_min_baseq = (uint32_t) value; variant_thresholds_given = true; }
+		else if (strcmp(argv[a], "--indel-sites") == 0 && a + 1 < argc) { options.indel_sites_file = argv[++a]; parent_exists(options.indel_sites_file); }
+		else if (strcmp(argv[a], "--indel-min-alt") == 0 && a + 1 < argc) { long value; require(parse_int(argv[++a], value) && value >= 0 && value <= 0xFFFFFFFFl, "invalid argument to --indel-min-alt"); options.indel_min_alt = (uint32_t) value; indel_thresholds_given = true; }
+		else if (strcmp(argv[a], "--indel-min-percent") == 0 && a + 1 < argc) { long value; require(parse_int(argv[++a], value) && value >= 0 && value <= 0xFFFFFFFFl, "invalid argument to --indel-min-percent"); options.indel_min_percent = (uint32_t) value; indel_thresholds_given = true; }
+		else if (strcmp(argv[a], "--indel-min-mapq") == 0 && a + 1 < argc) { long value; require(parse_int(argv[++a], value) && value >= 0 && value <= 0xFFFFFFFFl, "invalid argument to --indel-min-mapq"); options.indel_min_mapq = (uint32_t) value; indel_thresholds_given = true; }
 		else if (strcmp(argv[a], "--supporting-window") == 0 && a + 1 < argc) { long window; require(parse_int(argv[++a], window) && window > 0 && window <= 0x7FFFFFFFl, "invalid argument to --supporting-window"); options.supporting_alignments_window = window; }
 		else if (strcmp(argv[a], "--device") == 0 && a + 1 < argc) { long device; require(parse_int(argv[++a], device) && device >= 0, "invalid argument to --device"); options.device_index = (int) device; }
 		else arguments.push_back(argv[a]);
@@ -150,6 +159,7 @@ int main(int argc, char** argv) {
 	require(!options.mark_duplicates || options.sorted_bam_file != nullptr, "--mark-duplicates needs --sorted-bam");
 	require(options.rrna_intervals_file == nullptr || options.rna_metrics_file != nullptr, "--rrna-intervals needs --rna-metrics");
 	require(!variant_thresholds_given || options.variant_sites_file != nullptr, "--variant-min-alt, --variant-min-percent, --variant-min-mapq and --variant-min-baseq need --variant-sites");
+	require(!indel_thresholds_given || options.indel_sites_file != nullptr, "--indel-min-alt, --indel-min-percent and --indel-min-mapq need --indel-sites");
 	std::string interesting_contigs, viral_contigs;
 	bool seen[256]; memset(seen, 0, sizeof(seen));
 	bool blacklist_enabled = true;

@@ -69,6 +69,9 @@ extern "C" int agpu_rna_metrics(agpu_ctx* ctx, const agpu_region_track* track, c
 // ... and the one of --variant-sites
 extern "C" int agpu_variant_sites(agpu_ctx* ctx, const uint32_t* ref_length, uint32_t n_ref, uint32_t min_mapq, uint32_t min_baseq, uint32_t min_alt, uint32_t min_percent, const agpu_variant_row** rows, uint64_t* n_rows,
                                   agpu_variant_stats* stats) __attribute__((weak));
+// ... and the one of --indel-sites
+extern "C" int agpu_indel_sites(agpu_ctx* ctx, const uint32_t* ref_length, uint32_t n_ref, uint32_t min_mapq, uint32_t min_alt, uint32_t min_percent, const agpu_indel_row** rows, uint64_t* n_rows,
+                                agpu_indel_stats* stats) __attribute__((weak));
 
 namespace {
 
@@ -121,6 +124,15 @@ struct VariantChoice {
 	}
 };
 
+// --indel-sites of one sample of a session (arriba_workflow_indel_sites): the path (empty: none) and the three thresholds
+struct IndelChoice {
+	std::string path; uint32_t min_mapq = 20, min_alt = 3, min_percent = 5;
+	void apply(std::string& path_of_lane, arriba_workflow_options& o) const {
+		path_of_lane = path; o.indel_sites_file = path_of_lane.empty() ? nullptr : path_of_lane.c_str();
+		o.indel_min_mapq = min_mapq; o.indel_min_alt = min_alt; o.indel_min_percent = min_percent;
+	}
+};
+
 // A session (arriba_workflow_open): what is loaded once, and what a sample leaves behind for the next one.  `options` points at copies of the caller's strings.
 struct Run {
 	arriba_workflow_options options;
@@ -140,7 +152,7 @@ struct Run {
 	// read_chimeric_alignments in two halves (feed_file: the bytes of the file into HBM, on a thread of its own when the sample was submitted ahead; finish_device_ingest: what is
 	// left behind the last piece): what the first half leaves for the second
 	bool bam_open = false; uint64_t coverage_windows = 0; uint32_t bam_contigs = 0; double feed_started = 0, feed_finished = 0, feed_reading = 0, feed_pushing = 0;
-	std::string bam_path, output_path, discarded_path, sorted_bam_path, supporting_prefix, virus_expression_path, coverage_path, gene_counts_path, splice_junctions_path, allele_sites_path, allele_counts_path, realign_reads_path, realign_kept_path, rna_metrics_path, rrna_intervals_path, variant_sites_path; // of the sample this lane works on (options.* point at them)
+	std::string bam_path, output_path, discarded_path, sorted_bam_path, supporting_prefix, virus_expression_path, coverage_path, gene_counts_path, splice_junctions_path, allele_sites_path, allele_counts_path, realign_reads_path, realign_kept_path, rna_metrics_path, rrna_intervals_path, variant_sites_path, indel_sites_path; // of the sample this lane works on (options.* point at them)
 	double sorted_bam_seconds = 0; // --sorted-bam of the sample at work
 	double virus_expression_seconds = 0; // --virus-expression of the sample at work
 	double coverage_seconds = 0; // --coverage of the sample at work
@@ -150,6 +162,7 @@ struct Run {
 	double realign_seconds = 0; // --realign-reads of the sample at work
 	double rna_metrics_seconds = 0; // --rna-metrics of the sample at work
 	double variant_sites_seconds = 0; // --variant-sites of the sample at work
+	double indel_sites_seconds = 0; // --indel-sites of the sample at work
 	ahost_allele_sites allele_sites = {}; // --allele-sites of the sample at work: read (and refused) before the feed, placed on the references of the header behind it
 	double supporting_seconds = 0; bool support_pool_built = false; // --supporting-alignments of the sample at work: the pool behind the ingest and the files behind fusions.tsv
 	std::function<void()> after_ingest; // a session with two lanes: the stream and the tables of the ingest are free for the feed of the next sample
@@ -188,7 +201,7 @@ struct Run {
 	Run(const arriba_workflow_options& o): options(o), report(nullptr), timing(nullptr), host(nullptr), device(nullptr), dummy_genes(0), n_candidates(0), n_fragments(0), mapped_reads(0), device_ingest(false) {
 		for (int k = 0; k < FEED_BUFFERS; ++k) { pieces[k] = nullptr; tables[k] = nullptr; }
 		const char** texts[] = { &options.assembly_file, &options.gene_annotation_file, &options.chimeric_bam_file, &options.output_file, &options.discarded_output_file, &options.blacklist_file, &options.known_fusions_file,
-		                         &options.tags_file, &options.protein_domains_file, &options.genomic_breakpoints_file, &options.interesting_contigs, &options.viral_contigs, &options.gtf_features, &options.sorted_bam_file, &options.supporting_alignments_prefix, &options.virus_expression_file, &options.coverage_file, &options.gene_counts_file, &options.splice_junctions_file, &options.allele_sites_file, &options.allele_counts_file, &options.realign_reads_file, &options.realign_kept_file, &options.rna_metrics_file, &options.rrna_intervals_file, &options.variant_sites_file };
+		                         &options.tags_file, &options.protein_domains_file, &options.genomic_breakpoints_file, &options.interesting_contigs, &options.viral_contigs, &options.gtf_features, &options.sorted_bam_file, &options.supporting_alignments_prefix, &options.virus_expression_file, &options.coverage_file, &options.gene_counts_file, &options.splice_junctions_file, &options.allele_sites_file, &options.allele_counts_file, &options.realign_reads_file, &options.realign_kept_file, &options.rna_metrics_file, &options.rrna_intervals_file, &options.variant_sites_file, &options.indel_sites_file };
 		strings.reserve(sizeof(texts) / sizeof(texts[0]));
 		for (size_t k = 0; k < sizeof(texts) / sizeof(texts[0]); ++k) if (*texts[k] != nullptr) { strings.push_back(*texts[k]); *texts[k] = strings.back().c_str(); }
 	}
@@ -372,6 +385,34 @@ bool check_variant_sites(const Run& run) {
 	return true;
 }
 
+std::string indel_sites_line(const agpu_indel_stats& c) {
+	std::ostringstream text;
+	text << "Finding indel sites (records=" << c.records << ", contributing=" << c.contributing << ", operations=" << c.operations << ", events=" << c.events << ", unkeyed_insertions=" << c.unkeyed_insertions
+	     << ", shift_capped=" << c.shift_capped << ", runs=" << c.runs << ", candidates=" << c.candidates << ", reported=" << c.reported << ")";
+	return text.str();
+}
+// --indel-sites and its thresholds: what can be refused without the input; true if the option is on.  Without the file "a threshold was given" is told by the three values, as
+// check_variant_sites tells it: all at the defaults of arriba_workflow_default_options or all zero (a zero-initialised struct) is "none given", anything else is refused.
+bool check_indel_sites(const Run& run) {
+	const arriba_workflow_options& o = run.options;
+	if (o.indel_sites_file == nullptr) {
+		const bool defaults = o.indel_min_alt == 3 && o.indel_min_percent == 5 && o.indel_min_mapq == 20;
+		const bool zeroes = o.indel_min_alt == 0 && o.indel_min_percent == 0 && o.indel_min_mapq == 0; // (a zero-initialised struct)
+		if (!defaults && !zeroes) throw Failure{ "ERROR: --indel-min-alt, --indel-min-percent and --indel-min-mapq need --indel-sites: the file the indels go to" };
+		return false;
+	}
+	if (o.indel_min_alt < 1 || o.indel_min_alt > 0x7FFFFFFFu) throw Failure{ "ERROR: --indel-min-alt is 1 to 2147483647" };
+	if (o.indel_min_percent > 100) throw Failure{ "ERROR: --indel-min-percent is 0 to 100" };
+	if (o.indel_min_mapq > 255) throw Failure{ "ERROR: --indel-min-mapq is at most 255 (MAPQ is a byte)" };
+	if (run.ranks != nullptr) throw Failure{ "ERROR: indel sites of one sample over several GPUs are not supported" };
+	{ std::string copy(o.indel_sites_file); // (a missing directory is refused before the feed, not behind the call)
+	  const size_t slash = copy.rfind('/');
+	  const std::string parent = slash == std::string::npos ? "." : slash == 0 ? "/" : copy.substr(0, slash);
+	  struct stat status;
+	  if (stat(parent.c_str(), &status) != 0 || !S_ISDIR(status.st_mode)) throw Failure{ std::string("ERROR: parent directory of output file '") + o.indel_sites_file + "' does not exist" }; }
+	return true;
+}
+
 // -c (separate_chimeric_file): what is refused with it, before any input is read -- the side outputs read the resident stream of ONE file, the parts of a sample are cut from one file
 void check_separate_chimeric(const arriba_workflow_options& o, bool over_ranks) {
 	if (o.separate_chimeric_file == nullptr) return;
@@ -380,7 +421,7 @@ void check_separate_chimeric(const arriba_workflow_options& o, bool over_ranks) 
 	if (over_ranks) throw Failure{ "ERROR: -c (separate chimeric alignments) of one sample over several ranks is not supported" };
 	const struct { const char* value; const char* name; } excluded[] = { { o.sorted_bam_file, "--sorted-bam" }, { o.supporting_alignments_prefix, "--supporting-alignments" }, { o.virus_expression_file, "--virus-expression" },
 		{ o.coverage_file, "--coverage" }, { o.gene_counts_file, "--gene-counts" }, { o.splice_junctions_file, "--splice-junctions" }, { o.allele_counts_file, "--allele-counts" }, { o.realign_reads_file, "--realign-reads" },
-		{ o.rna_metrics_file, "--rna-metrics" }, { o.variant_sites_file, "--variant-sites" } };
+		{ o.rna_metrics_file, "--rna-metrics" }, { o.variant_sites_file, "--variant-sites" }, { o.indel_sites_file, "--indel-sites" } };
 	for (size_t k = 0; k < sizeof(excluded) / sizeof(excluded[0]); ++k)
 		if (excluded[k].value != nullptr) throw Failure{ std::string("ERROR: -c (separate chimeric alignments) and ") + excluded[k].name + " exclude each other: " + excluded[k].name + " reads the records of one file, the alignments of the sample are in two" };
 }
@@ -435,6 +476,7 @@ void feed_one_file(Run& run, const char* path, int role) {
 		host_check(ahost_region_track(run.host, o.rrna_intervals_file, &track, nullptr)); // (an interval file that does not parse is refused here; the track of the session is built once and kept)
 	}
 	if (check_variant_sites(run)) need_device("--variant-sites", "agpu_variant_sites", agpu_variant_sites); // (likewise)
+	if (check_indel_sites(run)) need_device("--indel-sites", "agpu_indel_sites", agpu_indel_sites); // (likewise)
 	agpu_ingest_config config;
 	if (run.ranks != nullptr) host_check(ahost_bam_open_part(run.host, path, o.device.external_duplicate_marking, o.device.max_itd_length, run.ranks->rank, run.ranks->size, &config)); // this rank's part of the records
 	else if (role != AGPU_ROLE_WHOLE) host_check(ahost_bam_open_role(run.host, path, o.device.external_duplicate_marking, o.device.max_itd_length, role, &config));
@@ -827,6 +869,23 @@ void write_variant_sites(Run& run) {
 	run.variant_sites_seconds = now_seconds() - started;
 }
 
+// --indel-sites: behind the ingest, while the stream is in HBM, the insertions and deletions of the records (include/arriba_gpu.h: agpu_indel_sites).  The device
+// makes the rows; the host turns them into text with the names of the references of the header and the deleted bases of the assembly and writes it through FILE.tmp.  On a failure
+// nothing is left and the sample fails with the message.
+void write_indel_sites(Run& run) {
+	need_device("--indel-sites", "agpu_indel_sites", agpu_indel_sites);
+	const double started = now_seconds();
+	const arriba_workflow_options& o = run.options;
+	ahost_depth_contigs contigs;
+	host_check(ahost_depth_contigs_of_session(run.host, &contigs)); // (names and LN of the references of the header)
+	const agpu_indel_row* rows = nullptr; uint64_t n_rows = 0;
+	agpu_indel_stats stats;
+	device_call("--indel-sites", agpu_indel_sites(run.device, contigs.length, contigs.n_ref, o.indel_min_mapq, o.indel_min_alt, o.indel_min_percent, &rows, &n_rows, &stats));
+	host_check(ahost_indel_sites_write(run.host, &contigs, rows, n_rows, o.indel_sites_file));
+	run.say(indel_sites_line(stats));
+	run.indel_sites_seconds = now_seconds() - started;
+}
+
 // --realign-reads: behind the ingest, while the stream is in HBM, the records split into the templates to realign and the templates to keep, as SAM text (include/arriba_gpu.h:
 // agpu_realign_*).  The device decides and formats; the host writes the header of the kept file and appends the windows of text -- through two pinned buffers in
 // turn -- to NAME.tmp, which is renamed when both files are complete.  On a failure both are removed and the sample fails with the message.
@@ -972,6 +1031,8 @@ void finish_device_ingest(Run& run, double waited_since) {
 	if (run.options.rna_metrics_file != nullptr) write_rna_metrics(run); // (likewise)
 	run.variant_sites_seconds = 0;
 	if (run.options.variant_sites_file != nullptr) write_variant_sites(run); // (likewise)
+	run.indel_sites_seconds = 0;
+	if (run.options.indel_sites_file != nullptr) write_indel_sites(run); // (likewise)
 	run.supporting_seconds = 0; run.support_pool_built = false;
 	if (run.options.supporting_alignments_prefix != nullptr) build_support_pool(run); // (before after_ingest as well; the pool is this lane's own and outlives the hand-over of the stream)
 	run.sharded = false; run.first_rank = 0; run.exchanged_bytes = 0;
@@ -1007,6 +1068,7 @@ void note_device_ingest(Run& run, double waited_since) {
 	if (run.timing) run.timing->realign = run.realign_seconds;
 	if (run.timing) run.timing->rna_metrics = run.rna_metrics_seconds;
 	if (run.timing) run.timing->variant_sites = run.variant_sites_seconds;
+	if (run.timing) run.timing->indel_sites = run.indel_sites_seconds;
 	run.note("bam_records", run.ingest_records); // (for the report only: no line of the reference's log)
 	run.note("bam_stream_bytes", run.ingest_stream_bytes);
 }
@@ -1580,6 +1642,7 @@ void run_sample(Run& run, bool already_fed, double sample_started) {
 		const bool realign = check_realign(run); // (refused before the input is read)
 		if (check_rna_metrics(run)) { agpu_region_track track; host_check(ahost_region_track(run.host, o.rrna_intervals_file, &track, nullptr)); } // (likewise)
 		const bool variant_sites = check_variant_sites(run); // (likewise)
+		const bool indel_sites = check_indel_sites(run); // (likewise)
 		if (o.separate_chimeric_file != nullptr) host_check(ahost_ingest_separate(run.host, o.separate_chimeric_file, o.chimeric_bam_file, o.device.external_duplicate_marking, o.device.max_itd_length, &run.separate_fragments, nullptr));
 		else host_check(ahost_ingest_bam_file(run.host, o.chimeric_bam_file, o.device.external_duplicate_marking, o.device.max_itd_length));
 		if (o.sorted_bam_file != nullptr) { // (the host's stepping of the same code)
@@ -1632,6 +1695,13 @@ void run_sample(Run& run, bool already_fed, double sample_started) {
 			host_check(ahost_variant_sites_file(run.host, o.chimeric_bam_file, o.variant_sites_file, o.variant_min_mapq, o.variant_min_baseq, o.variant_min_alt, o.variant_min_percent, &stats));
 			run.say(variant_sites_line(stats));
 			if (run.timing) run.timing->variant_sites = now_seconds() - before;
+		}
+		if (indel_sites) { // (likewise)
+			const double before = now_seconds();
+			agpu_indel_stats stats;
+			host_check(ahost_indel_sites_file(run.host, o.chimeric_bam_file, o.indel_sites_file, o.indel_min_mapq, o.indel_min_alt, o.indel_min_percent, &stats));
+			run.say(indel_sites_line(stats));
+			if (run.timing) run.timing->indel_sites = now_seconds() - before;
 		}
 		device_check(agpu_upload_genome(run.device, ahost_genome_view(run.host)));
 		device_check(agpu_upload_batch(run.device, ahost_batch_view(run.host)));
@@ -1793,6 +1863,7 @@ void arriba_workflow_default_options(arriba_workflow_options* options) {
 	options->max_homolog_identity = 0.3f; options->top_viral_contigs = 5; options->viral_contig_min_covered_fraction = 0.05f; options->max_genomic_breakpoint_distance = 100000;
 	options->allele_min_baseq = 13; // (--allele-min-baseq: samtools mpileup's -Q)
 	options->variant_min_alt = 3; options->variant_min_percent = 5; options->variant_min_mapq = 20; options->variant_min_baseq = 13; // (--variant-min-*)
+	options->indel_min_alt = 3; options->indel_min_percent = 5; options->indel_min_mapq = 20; // (--indel-min-*)
 }
 
 const char* arriba_workflow_last_error(void) { return g_error.c_str(); }
@@ -1821,7 +1892,7 @@ int arriba_workflow_run(const arriba_workflow_options* options, arriba_workflow_
 struct arriba_workflow_session {
 	Run* lanes[2];
 	int processed_lane = 0; // of the sample arriba_workflow_sample worked on last
-	struct Submitted { std::string bam, sorted_bam, supporting, virus_expression, coverage, gene_counts, splice_junctions, allele_sites, allele_counts, realign_reads, realign_kept, rna_metrics, rrna_intervals; VariantChoice variant; uint32_t allele_min_mapq = 0, allele_min_baseq = 0; int sorted_bam_level = 0, mark_duplicates = 0; int lane = 0; std::thread feeder; bool fed = false, ingest_finished = false, started = false; std::string error; int error_code = 0; };
+	struct Submitted { std::string bam, sorted_bam, supporting, virus_expression, coverage, gene_counts, splice_junctions, allele_sites, allele_counts, realign_reads, realign_kept, rna_metrics, rrna_intervals; VariantChoice variant; IndelChoice indel; uint32_t allele_min_mapq = 0, allele_min_baseq = 0; int sorted_bam_level = 0, mark_duplicates = 0; int lane = 0; std::thread feeder; bool fed = false, ingest_finished = false, started = false; std::string error; int error_code = 0; };
 	std::deque<std::unique_ptr<Submitted>> queue; // oldest first; at most two
 	std::mutex mutex; std::condition_variable changed;
 	bool ingest_busy = false; // a lane is between agpu_ingest_begin and agpu_ingest_finish
@@ -1835,6 +1906,7 @@ struct arriba_workflow_session {
 	std::string next_realign_reads, next_realign_kept; // arriba_workflow_realign: likewise
 	std::string next_rna_metrics, next_rrna_intervals; // arriba_workflow_rna_metrics: likewise
 	VariantChoice next_variant; // arriba_workflow_variant_sites: likewise
+	IndelChoice next_indel; // arriba_workflow_indel_sites: likewise
 	int mark_duplicates = 0;  // arriba_workflow_sorted_bam_mark_duplicates: of the samples submitted from now on (at first: options.mark_duplicates of arriba_workflow_open)
 	int sorted_bam_level = 0; // arriba_workflow_sorted_bam_compression: of the samples submitted from now on (at first: options.sorted_bam_compression of arriba_workflow_open)
 	bool defer_output = false;
@@ -1915,10 +1987,11 @@ struct arriba_workflow_session {
 		run.rna_metrics_path.swap(next_rna_metrics); next_rna_metrics.clear(); run.options.rna_metrics_file = run.rna_metrics_path.empty() ? nullptr : run.rna_metrics_path.c_str();
 		run.rrna_intervals_path.swap(next_rrna_intervals); next_rrna_intervals.clear(); run.options.rrna_intervals_file = run.rrna_intervals_path.empty() ? nullptr : run.rrna_intervals_path.c_str();
 		const VariantChoice variant = next_variant; next_variant = VariantChoice(); variant.apply(run.variant_sites_path, run.options);
+		const IndelChoice indel = next_indel; next_indel = IndelChoice(); indel.apply(run.indel_sites_path, run.options);
 		run.timing = nullptr; run.report = nullptr;
 		prepare_sample(run);
 		std::unique_ptr<Submitted> sample(new Submitted());
-		sample->bam = bam; sample->sorted_bam = run.sorted_bam_path; sample->supporting = run.supporting_prefix; sample->virus_expression = run.virus_expression_path; sample->coverage = run.coverage_path; sample->gene_counts = run.gene_counts_path; sample->splice_junctions = run.splice_junctions_path; sample->allele_sites = run.allele_sites_path; sample->allele_counts = run.allele_counts_path; sample->allele_min_mapq = run.options.allele_min_mapq; sample->allele_min_baseq = run.options.allele_min_baseq; sample->realign_reads = run.realign_reads_path; sample->realign_kept = run.realign_kept_path; sample->rna_metrics = run.rna_metrics_path; sample->rrna_intervals = run.rrna_intervals_path; sample->variant = variant; sample->sorted_bam_level = sorted_bam_level; sample->mark_duplicates = mark_duplicates; sample->lane = lane;
+		sample->bam = bam; sample->sorted_bam = run.sorted_bam_path; sample->supporting = run.supporting_prefix; sample->virus_expression = run.virus_expression_path; sample->coverage = run.coverage_path; sample->gene_counts = run.gene_counts_path; sample->splice_junctions = run.splice_junctions_path; sample->allele_sites = run.allele_sites_path; sample->allele_counts = run.allele_counts_path; sample->allele_min_mapq = run.options.allele_min_mapq; sample->allele_min_baseq = run.options.allele_min_baseq; sample->realign_reads = run.realign_reads_path; sample->realign_kept = run.realign_kept_path; sample->rna_metrics = run.rna_metrics_path; sample->rrna_intervals = run.rrna_intervals_path; sample->variant = variant; sample->indel = indel; sample->sorted_bam_level = sorted_bam_level; sample->mark_duplicates = mark_duplicates; sample->lane = lane;
 		Submitted* mine = sample.get();
 		{ std::lock_guard<std::mutex> lock(mutex); queue.push_back(std::move(sample)); }
 		if (!run.device_ingest) { join_writer_of(lane); std::lock_guard<std::mutex> lock(mutex); mine->fed = true; return; } // (the host ingest reads the file inside arriba_workflow_sample)
@@ -2023,6 +2096,13 @@ int arriba_workflow_variant_sites(arriba_workflow_session* session, const char* 
 	return 0;
 }
 
+int arriba_workflow_indel_sites(arriba_workflow_session* session, const char* path, uint32_t min_mapq, uint32_t min_alt, uint32_t min_percent) {
+	if (!session) { g_error = "ERROR: null argument"; return -1; }
+	session->next_indel.path = path ? path : "";
+	session->next_indel.min_mapq = min_mapq; session->next_indel.min_alt = min_alt; session->next_indel.min_percent = min_percent;
+	return 0;
+}
+
 int arriba_workflow_realign(arriba_workflow_session* session, const char* reads_path, const char* kept_path) {
 	if (!session) { g_error = "ERROR: null argument"; return -1; }
 	session->next_realign_reads = reads_path ? reads_path : ""; session->next_realign_kept = kept_path ? kept_path : "";
@@ -2077,7 +2157,7 @@ int arriba_workflow_sample(arriba_workflow_session* session, const char* chimeri
 	}
 	catch (const Failure& failure) { g_error = failure.text; g_error_code = failure.code; status = -1; }
 	catch (const std::exception& e) { g_error = std::string("ERROR: ") + e.what(); g_error_code = 0; status = -1; }
-	if (lane) { lane->after_ingest = nullptr; lane->before_host_writer = nullptr; lane->options.chimeric_bam_file = nullptr; lane->options.sorted_bam_file = nullptr; lane->options.supporting_alignments_prefix = nullptr; lane->options.virus_expression_file = nullptr; lane->options.coverage_file = nullptr; lane->options.gene_counts_file = nullptr; lane->options.splice_junctions_file = nullptr; lane->options.allele_sites_file = nullptr; lane->options.allele_counts_file = nullptr; lane->options.realign_reads_file = nullptr; lane->options.realign_kept_file = nullptr; lane->options.rna_metrics_file = nullptr; lane->options.rrna_intervals_file = nullptr; lane->options.variant_sites_file = nullptr; lane->options.output_file = nullptr; lane->options.discarded_output_file = nullptr; lane->report = nullptr; lane->timing = nullptr; session->processed_lane = (int) (lane == session->lanes[1]); }
+	if (lane) { lane->after_ingest = nullptr; lane->before_host_writer = nullptr; lane->options.chimeric_bam_file = nullptr; lane->options.sorted_bam_file = nullptr; lane->options.supporting_alignments_prefix = nullptr; lane->options.virus_expression_file = nullptr; lane->options.coverage_file = nullptr; lane->options.gene_counts_file = nullptr; lane->options.splice_junctions_file = nullptr; lane->options.allele_sites_file = nullptr; lane->options.allele_counts_file = nullptr; lane->options.realign_reads_file = nullptr; lane->options.realign_kept_file = nullptr; lane->options.rna_metrics_file = nullptr; lane->options.rrna_intervals_file = nullptr; lane->options.variant_sites_file = nullptr; lane->options.indel_sites_file = nullptr; lane->options.output_file = nullptr; lane->options.discarded_output_file = nullptr; lane->report = nullptr; lane->timing = nullptr; session->processed_lane = (int) (lane == session->lanes[1]); }
 	// The device ran out of memory while the session had two lanes (advisor, round 4): their contexts share one pool of scratch buffers, of which nothing is idle while one lane
 	// feeds and the other runs its stages, so the device library gives nothing back by itself (DeviceBuffer::release_idle_buffers).  The session does what INTEGRATION.md ("Memory")
 	// used to ask of the caller: what was fed ahead is thrown away, the second lane is closed -- the pool belongs to one context again, which gives back what it keeps for its next
@@ -2103,6 +2183,8 @@ int arriba_workflow_sample(arriba_workflow_session* session, const char* chimeri
 		const uint32_t behind_allele_baseq = session->queue.empty() ? 13 : session->queue.front()->allele_min_baseq, again_allele_baseq = lane->options.allele_min_baseq;
 		const VariantChoice behind_variant = session->queue.empty() ? VariantChoice() : session->queue.front()->variant;
 		VariantChoice again_variant; again_variant.path = lane->variant_sites_path; again_variant.min_mapq = lane->options.variant_min_mapq; again_variant.min_baseq = lane->options.variant_min_baseq; again_variant.min_alt = lane->options.variant_min_alt; again_variant.min_percent = lane->options.variant_min_percent;
+		const IndelChoice behind_indel = session->queue.empty() ? IndelChoice() : session->queue.front()->indel;
+		IndelChoice again_indel; again_indel.path = lane->indel_sites_path; again_indel.min_mapq = lane->options.indel_min_mapq; again_indel.min_alt = lane->options.indel_min_alt; again_indel.min_percent = lane->options.indel_min_percent;
 		session->drain();
 		session->join_writer_of(0); session->join_writer_of(1);
 		// (an I/O error on the deferred file of an EARLIER sample stays noted -- advisor, round 5: it was dropped here, and the caller never learnt that the file is incomplete -- and is
@@ -2111,11 +2193,11 @@ int arriba_workflow_sample(arriba_workflow_session* session, const char* chimeri
 		delete session->lanes[1]; session->lanes[1] = nullptr; session->processed_lane = 0;
 		fprintf(stderr, "arriba_workflow_sample: %s -- with two samples in flight; '%s' is run again with the device to itself\n", first_error.c_str(), chimeric_bam_file);
 		session->retrying = true;
-		session->next_sorted_bam = again_sorted_bam; session->next_supporting = again_supporting; session->next_virus_expression = again_virus; session->next_coverage = again_coverage; session->next_gene_counts = again_gene_counts; session->next_splice_junctions = again_splice_junctions; session->next_allele_sites = again_allele_sites; session->next_allele_counts = again_allele_counts; session->next_allele_min_mapq = again_allele_mapq; session->next_allele_min_baseq = again_allele_baseq; session->next_realign_reads = again_realign_reads; session->next_realign_kept = again_realign_kept; session->next_rna_metrics = again_rna_metrics; session->next_rrna_intervals = again_rrna_intervals; session->next_variant = again_variant; session->sorted_bam_level = again_level; session->mark_duplicates = again_marks;
+		session->next_sorted_bam = again_sorted_bam; session->next_supporting = again_supporting; session->next_virus_expression = again_virus; session->next_coverage = again_coverage; session->next_gene_counts = again_gene_counts; session->next_splice_junctions = again_splice_junctions; session->next_allele_sites = again_allele_sites; session->next_allele_counts = again_allele_counts; session->next_allele_min_mapq = again_allele_mapq; session->next_allele_min_baseq = again_allele_baseq; session->next_realign_reads = again_realign_reads; session->next_realign_kept = again_realign_kept; session->next_rna_metrics = again_rna_metrics; session->next_rrna_intervals = again_rrna_intervals; session->next_variant = again_variant; session->next_indel = again_indel; session->sorted_bam_level = again_level; session->mark_duplicates = again_marks;
 		status = arriba_workflow_sample(session, chimeric_bam_file, output_file, discarded_output_file, report, timing);
 		session->retrying = false;
 		if (status == 0 && !behind.empty()) { // (as its caller submitted it: a failure to feed it is reported by the call that asks for it)
-			try { session->next_sorted_bam = behind_sorted_bam; session->next_supporting = behind_supporting; session->next_virus_expression = behind_virus; session->next_coverage = behind_coverage; session->next_gene_counts = behind_gene_counts; session->next_splice_junctions = behind_splice_junctions; session->next_allele_sites = behind_allele_sites; session->next_allele_counts = behind_allele_counts; session->next_allele_min_mapq = behind_allele_mapq; session->next_allele_min_baseq = behind_allele_baseq; session->next_realign_reads = behind_realign_reads; session->next_realign_kept = behind_realign_kept; session->next_rna_metrics = behind_rna_metrics; session->next_rrna_intervals = behind_rrna_intervals; session->next_variant = behind_variant; session->sorted_bam_level = behind_level; session->mark_duplicates = behind_marks; session->submit(behind.c_str()); }
+			try { session->next_sorted_bam = behind_sorted_bam; session->next_supporting = behind_supporting; session->next_virus_expression = behind_virus; session->next_coverage = behind_coverage; session->next_gene_counts = behind_gene_counts; session->next_splice_junctions = behind_splice_junctions; session->next_allele_sites = behind_allele_sites; session->next_allele_counts = behind_allele_counts; session->next_allele_min_mapq = behind_allele_mapq; session->next_allele_min_baseq = behind_allele_baseq; session->next_realign_reads = behind_realign_reads; session->next_realign_kept = behind_realign_kept; session->next_rna_metrics = behind_rna_metrics; session->next_rrna_intervals = behind_rrna_intervals; session->next_variant = behind_variant; session->next_indel = behind_indel; session->sorted_bam_level = behind_level; session->mark_duplicates = behind_marks; session->submit(behind.c_str()); }
 			catch (const Failure&) {} catch (const std::exception&) {}
 		}
 		session->sorted_bam_level = session_level; session->mark_duplicates = session_marks;

@@ -77,6 +77,13 @@ def variant_stats_of(stats):
     return out
 
 
+def indel_stats_of(stats):
+    """agpu_indel_stats (the device's or the host's) as a dict"""
+    out = {name: int(getattr(stats, name)) for name in ("records", "contributing", "operations", "events", "unkeyed_insertions", "shift_capped", "runs", "candidates", "sites", "reported", "peak_bytes")}
+    out["seconds"] = dict(zip(("count", "fill", "group", "counters", "rows"), stats.seconds))
+    return out
+
+
 def rna_metrics_stats_of(stats):
     """agpu_rna_metrics_stats (the device's or the host's) as a dict"""
     out = {name: int(getattr(stats, name)) for name in ("records", "base_records", "blocks", "segments", "track_runs", "peak_bytes")}
@@ -254,7 +261,7 @@ class WorkflowSession(object):
         if self._lib.arriba_workflow_sorted_bam_mark_duplicates(self._session, int(bool(on))) != 0:
             raise ArribaError(self._lib.arriba_workflow_last_error().decode())
 
-    def submit(self, bam, sorted_bam_file=None, supporting_alignments_prefix=None, sorted_bam_compression=None, virus_expression_file=None, coverage_file=None, mark_duplicates=None, gene_counts_file=None, splice_junctions_file=None, allele_sites_file=None, allele_counts_file=None, allele_min_mapq=0, allele_min_baseq=13, realign_reads_file=None, realign_kept_file=None, rna_metrics_file=None, rrna_intervals_file=None, variant_sites_file=None, variant_min_mapq=20, variant_min_baseq=13, variant_min_alt=3, variant_min_percent=5):
+    def submit(self, bam, sorted_bam_file=None, supporting_alignments_prefix=None, sorted_bam_compression=None, virus_expression_file=None, coverage_file=None, mark_duplicates=None, gene_counts_file=None, splice_junctions_file=None, allele_sites_file=None, allele_counts_file=None, allele_min_mapq=0, allele_min_baseq=13, realign_reads_file=None, realign_kept_file=None, rna_metrics_file=None, rrna_intervals_file=None, variant_sites_file=None, variant_min_mapq=20, variant_min_baseq=13, variant_min_alt=3, variant_min_percent=5, indel_sites_file=None, indel_min_mapq=20, indel_min_alt=3, indel_min_percent=5):
         """the sample that comes after the one `sample` is called for next: its file is fed (PCIe, the front of read_chimeric_alignments) while the stages of that one run;
         sorted_bam_file: its records in coordinate order with their index (--sorted-bam), written when its ingest is finished; sorted_bam_compression: its level (None: as it is)"""
         if sorted_bam_compression is not None:
@@ -271,6 +278,7 @@ class WorkflowSession(object):
         self._lib.arriba_workflow_realign(self._session, realign_reads_file.encode() if realign_reads_file else None, realign_kept_file.encode() if realign_kept_file else None)  # (--realign-reads: likewise)
         self._lib.arriba_workflow_rna_metrics(self._session, rna_metrics_file.encode() if rna_metrics_file else None, rrna_intervals_file.encode() if rrna_intervals_file else None)  # (--rna-metrics: its QC table, likewise)
         self._lib.arriba_workflow_variant_sites(self._session, variant_sites_file.encode() if variant_sites_file else None, variant_min_mapq, variant_min_baseq, variant_min_alt, variant_min_percent)  # (--variant-sites: likewise)
+        self._lib.arriba_workflow_indel_sites(self._session, indel_sites_file.encode() if indel_sites_file else None, indel_min_mapq, indel_min_alt, indel_min_percent)  # (--indel-sites: likewise)
         if self._lib.arriba_workflow_submit(self._session, bam.encode()) != 0:
             raise ArribaError(self._lib.arriba_workflow_last_error().decode())
         if self._profiling_on:
@@ -365,7 +373,7 @@ class WorkflowSession(object):
     def _lane_contexts(self):
         return [ctx for ctx in (self._lib.arriba_workflow_lane_device(self._session, lane) for lane in (0, 1)) if ctx]
 
-    def sample(self, bam, output_file, discarded_output_file=None, sorted_bam_file=None, supporting_alignments_prefix=None, sorted_bam_compression=None, virus_expression_file=None, coverage_file=None, mark_duplicates=None, gene_counts_file=None, splice_junctions_file=None, allele_sites_file=None, allele_counts_file=None, allele_min_mapq=0, allele_min_baseq=13, realign_reads_file=None, realign_kept_file=None, rna_metrics_file=None, rrna_intervals_file=None, variant_sites_file=None, variant_min_mapq=20, variant_min_baseq=13, variant_min_alt=3, variant_min_percent=5):
+    def sample(self, bam, output_file, discarded_output_file=None, sorted_bam_file=None, supporting_alignments_prefix=None, sorted_bam_compression=None, virus_expression_file=None, coverage_file=None, mark_duplicates=None, gene_counts_file=None, splice_junctions_file=None, allele_sites_file=None, allele_counts_file=None, allele_min_mapq=0, allele_min_baseq=13, realign_reads_file=None, realign_kept_file=None, rna_metrics_file=None, rrna_intervals_file=None, variant_sites_file=None, variant_min_mapq=20, variant_min_baseq=13, variant_min_alt=3, variant_min_percent=5, indel_sites_file=None, indel_min_mapq=20, indel_min_alt=3, indel_min_percent=5):
         """one sample, BAM file -> fusions.tsv (and discarded.tsv); returns the stages with their "(remaining=N)" counts.  sorted_bam_file (--sorted-bam): for a sample that was
         not submitted ahead; one that was says it to `submit`"""
         report, timing = _capi.WorkflowReport(), _capi.WorkflowTiming()
@@ -393,6 +401,8 @@ class WorkflowSession(object):
             self._lib.arriba_workflow_rna_metrics(self._session, rna_metrics_file.encode() if rna_metrics_file else None, rrna_intervals_file.encode() if rrna_intervals_file else None)
         if variant_sites_file or (variant_min_mapq, variant_min_baseq, variant_min_alt, variant_min_percent) != (20, 13, 3, 5):  # (likewise; thresholds without the file are refused by the sample)
             self._lib.arriba_workflow_variant_sites(self._session, variant_sites_file.encode() if variant_sites_file else None, variant_min_mapq, variant_min_baseq, variant_min_alt, variant_min_percent)
+        if indel_sites_file or (indel_min_mapq, indel_min_alt, indel_min_percent) != (20, 3, 5):  # (likewise; thresholds without the file are refused by the sample)
+            self._lib.arriba_workflow_indel_sites(self._session, indel_sites_file.encode() if indel_sites_file else None, indel_min_mapq, indel_min_alt, indel_min_percent)
         if self._lib.arriba_workflow_sample(self._session, bam.encode(), output_file.encode(), discarded_output_file.encode() if discarded_output_file else None, byref(report), byref(timing)) != 0:
             raise ArribaError(self._lib.arriba_workflow_last_error().decode())
         self.ctx = self._lib.arriba_workflow_device(self._session)  # (the lane that worked on this sample)
@@ -927,6 +937,38 @@ class DevicePipeline(object):
         self._check(self.api.variant_sites_allocated_bytes(self.ctx, byref(count)))
         return int(count.value)
 
+    def indel_sites(self, min_mapq=20, min_alt=3, min_percent=5):
+        """--indel-sites: the insertions and deletions the records of the last read_chimeric_alignments carry in their CIGARs, left-normalised against the assembly, found on the
+        device from the record stream that is still in HBM (agpu_indel_sites).  Valid after read_chimeric_alignments and before the next one.  Returns (rows,
+        stats): rows a ctypes array of _capi.IndelRow (a copy), ordered by (ref, pos, type, length, bases), and the statistics of indel_stats_of."""
+        if not self.device_ingest or not hasattr(self.api, "indel_sites"):
+            raise ArribaError("ERROR: indel sites need the record stream of an ingest on the device (DevicePipeline(bam=...))")
+        lib, handle = self.session._lib, self.session._session
+        contigs = _capi.DepthContigs()
+        if lib.ahost_depth_contigs_of_session(handle, byref(contigs)) != 0:
+            raise ArribaError("ERROR: " + lib.ahost_last_error().decode())
+        rows, n_rows, stats = ctypes.POINTER(_capi.IndelRow)(), c_uint64(), _capi.IndelStats()
+        self._check(self.api.indel_sites(self.ctx, contigs.length, contigs.n_ref, min_mapq, min_alt, min_percent, byref(rows), byref(n_rows), byref(stats)))
+        copy = (_capi.IndelRow * n_rows.value)()
+        if n_rows.value:
+            ctypes.memmove(copy, rows, ctypes.sizeof(copy))
+        return copy, indel_stats_of(stats)
+
+    def write_indel_sites(self, path, min_mapq=20, min_alt=3, min_percent=5):
+        """--indel-sites: the rows of `indel_sites` as the text of the file (a header line, then CONTIG POS REF TYPE LENGTH BASES SUPPORT DEPTH per event), written through
+        `path`.tmp; returns the statistics"""
+        lib, handle = self.session._lib, self.session._session
+        rows, stats = self.indel_sites(min_mapq, min_alt, min_percent)  # (refused before anything is written)
+        contigs = _capi.DepthContigs()
+        if lib.ahost_depth_contigs_of_session(handle, byref(contigs)) != 0 or lib.ahost_indel_sites_write(handle, byref(contigs), rows, len(rows), path.encode()) != 0:
+            raise ArribaError("ERROR: " + lib.ahost_last_error().decode())
+        return stats
+
+    def indel_sites_allocated_bytes(self):
+        count = c_uint64()
+        self._check(self.api.indel_sites_allocated_bytes(self.ctx, byref(count)))
+        return int(count.value)
+
     def realign_split(self, realign_path, kept_path=None):
         """--realign-reads [--realign-kept]: the records of the last read_chimeric_alignments split into the templates that must be aligned again and the templates that are passed
         on, as SAM text (fields 1-11; `kept_path` behind a header with the contigs of the assembly), decided and formatted on the device from the record stream that is still in
@@ -1286,7 +1328,7 @@ class DevicePipeline(object):
                      max_genomic_breakpoint_distance=100000, strandedness=None, evalue_cutoff=0.3,
                      min_itd_support=10, min_itd_allele_fraction=0.07, high_expression_quantile=0.998, min_spliced_events=4, min_anchor_length=23,
                      max_homolog_identity=0.3, max_itd_length=100, fill_sequence_gaps=False, top_viral_contigs=5, viral_contig_min_covered_fraction=0.05,
-                     print_extra_info_for_discarded_fusions=False, log=None, sorted_bam_file=None, supporting_alignments_prefix=None, supporting_alignments_window=1000000, virus_expression_file=None, coverage_file=None, mark_duplicates=False, gene_counts_file=None, splice_junctions_file=None, allele_sites_file=None, allele_counts_file=None, allele_min_mapq=0, allele_min_baseq=13, realign_reads_file=None, realign_kept_file=None, rna_metrics_file=None, rrna_intervals_file=None, variant_sites_file=None, variant_min_mapq=20, variant_min_baseq=13, variant_min_alt=3, variant_min_percent=5):
+                     print_extra_info_for_discarded_fusions=False, log=None, sorted_bam_file=None, supporting_alignments_prefix=None, supporting_alignments_window=1000000, virus_expression_file=None, coverage_file=None, mark_duplicates=False, gene_counts_file=None, splice_junctions_file=None, allele_sites_file=None, allele_counts_file=None, allele_min_mapq=0, allele_min_baseq=13, realign_reads_file=None, realign_kept_file=None, rna_metrics_file=None, rrna_intervals_file=None, variant_sites_file=None, variant_min_mapq=20, variant_min_baseq=13, variant_min_alt=3, variant_min_percent=5, indel_sites_file=None, indel_min_mapq=20, indel_min_alt=3, indel_min_percent=5):
         """The reference's main() behind read_chimeric_alignments (source/arriba.cpp:119-610) with its default parameters: the read-level cascade, find_fusions,
         every candidate-level filter in the reference's order, assign_confidence, and the two output files.  `log` receives (stage, remaining) pairs --
         the numbers the reference prints as "(remaining=N)".  Filters switched off with -f are skipped by the stages themselves (agpu_params.filter_enabled)."""
@@ -1319,6 +1361,10 @@ class DevicePipeline(object):
             raise ArribaError("ERROR: --variant-min-alt, --variant-min-percent, --variant-min-mapq and --variant-min-baseq need --variant-sites: the file the sites go to")
         if variant_sites_file:  # (--variant-sites: likewise)
             self.write_variant_sites(variant_sites_file, variant_min_mapq, variant_min_baseq, variant_min_alt, variant_min_percent)
+        if not indel_sites_file and (indel_min_mapq, indel_min_alt, indel_min_percent) != (20, 3, 5):
+            raise ArribaError("ERROR: --indel-min-alt, --indel-min-percent and --indel-min-mapq need --indel-sites: the file the indels go to")
+        if indel_sites_file:  # (--indel-sites: likewise)
+            self.write_indel_sites(indel_sites_file, indel_min_mapq, indel_min_alt, indel_min_percent)
         if supporting_alignments_prefix:  # (--supporting-alignments, phase 1: the records of the names of the batch leave the stream while it is there)
             self.build_support_pool()
         self.run_read_level(strandedness, top_viral_contigs, viral_contig_min_covered_fraction)

@@ -595,6 +595,47 @@ typedef struct {
 int agpu_variant_sites(agpu_ctx* ctx, const uint32_t* ref_length, uint32_t n_ref, uint32_t min_mapq, uint32_t min_baseq, uint32_t min_alt, uint32_t min_percent, const agpu_variant_row** rows, uint64_t* n_rows,
                        agpu_variant_stats* stats /* may be NULL */);
 int agpu_variant_sites_allocated_bytes(agpu_ctx* ctx, uint64_t* bytes);
+/* --indel-sites: the insertions and deletions the records of the last ingest carry in their CIGARs, left-normalised against the assembly, with their support and the depth at their
+ * anchor, found on the device while the stream is in HBM (arriba_amd/csrc/device/agpu_indels.hip, indel_core.hpp): the candidate indels of a variant caller, no
+ * genotypes.
+ *   agpu_indel_sites     behind agpu_ingest_finish, before the next agpu_ingest_begin on this context or its sibling (the refusals of agpu_variant_sites; the genome must be
+ *                        uploaded: the events are normalised against it).  ref_length: LN of every reference of the header of that ingest (n_ref of them).  min_mapq: at most
+ *                        255; min_alt: 1 .. 2^31-1; min_percent: 0 .. 100.  rows: the reported events by (ref, pos), deletions before insertions, by length, by bases; they
+ *                        belong to the context and are valid until the next call on it.  The "indel.*" buffers are freed before the call returns.
+ *   agpu_indel_sites_allocated_bytes   of those buffers: 0 outside the call
+ * ARRIBA_INDEL_MAX_EVENTS (default and most 2^31): a call that finds more events is refused; the stream stays usable.
+ * ARRIBA_INDEL_MAX_SHIFT (default and most 4096): the steps one event is moved to the left at the most; the host stepping reads it as well.
+ * ARRIBA_INDEL_LAUNCH_RECORDS (a knob for the tests): the records of one launch of indel_event_kernel, at most 2^30.
+ * ARRIBA_ALLELE_PLAIN_ATOMICS, ARRIBA_ALLELE_NO_BITMAP: of the counters, as for agpu_allele_counts. */
+typedef struct {
+	uint32_t ref;                  /* index of the reference in the header */
+	int32_t pos;                   /* 0-based anchor: the base in front of the inserted or deleted bases (the file prints it + 1) */
+	uint64_t bases;                /* of an insertion: 2 bits a base (A 0, C 1, G 2, T 3), the first base in bits 55 and 54; 0 for a deletion */
+	uint32_t length;               /* inserted or deleted bases */
+	uint32_t support;              /* records that carry the event */
+	uint32_t depth;                /* A + C + G + T + N + DEL of agpu_allele_counts at the anchor with the same min_mapq and min_baseq 0 */
+	uint8_t type;                  /* 0: deletion, 1: insertion */
+	uint8_t ref_base;              /* the upper-case base of the assembly at the anchor, N where the session holds none */
+	uint8_t reserved[2];
+} agpu_indel_row;
+typedef struct {
+	uint64_t records;              /* of the stream */
+	uint64_t contributing;         /* records that pass the filter */
+	uint64_t operations;           /* I and D operations between two aligned blocks, inside the reference */
+	uint64_t events;               /* of them: deletions, and insertions of at most 28 bases A/C/G/T */
+	uint64_t unkeyed_insertions;   /* the other insertions: operations - events */
+	uint64_t shift_capped;         /* events whose normalisation stopped at ARRIBA_INDEL_MAX_SHIFT */
+	uint64_t runs;                 /* distinct events */
+	uint64_t candidates;           /* distinct events with a support of at least min_alt */
+	uint64_t sites;                /* distinct anchors of the candidates: the sites whose depth is counted */
+	uint64_t reported;             /* rows: candidates that also pass min_percent */
+	uint64_t peak_bytes;           /* of the "indel.*" buffers (0 on the host) */
+	double seconds[5];             /* count pass; fill pass; sort, runs and candidates; the counters; the rows (device: from a HIP event in front of the first launch of the pass to
+	                                  one behind its last, 0 on the host) */
+} agpu_indel_stats;
+int agpu_indel_sites(agpu_ctx* ctx, const uint32_t* ref_length, uint32_t n_ref, uint32_t min_mapq, uint32_t min_alt, uint32_t min_percent, const agpu_indel_row** rows, uint64_t* n_rows,
+                     agpu_indel_stats* stats /* may be NULL */);
+int agpu_indel_sites_allocated_bytes(agpu_ctx* ctx, uint64_t* bytes);
 /* --realign-reads: the records of the last ingest split into the templates that must be aligned again and the templates that are passed on, both as SAM text (fields 1-11, what
  * `samtools view` prints), formatted on the device while the stream is in HBM (arriba_amd/csrc/device/agpu_realign.hip, realign_core.hpp).
  *   agpu_realign_begin   behind agpu_ingest_finish, before the next agpu_ingest_begin on this context or its sibling (the refusals of agpu_depth_begin).  in_assembly: a byte per

@@ -258,6 +258,23 @@ int ahost_variant_sites_of(ahost_session* session, const void* input_header, siz
 int ahost_variant_sites_text(const ahost_depth_contigs* contigs, const agpu_variant_row* rows, uint64_t n_rows, const char** text, uint64_t* bytes);
 int ahost_variant_sites_write(const ahost_depth_contigs* contigs, const agpu_variant_row* rows, uint64_t n_rows, const char* path);
 int ahost_variant_sites_file(ahost_session* session, const char* input_path, const char* path, uint32_t min_mapq, uint32_t min_baseq, uint32_t min_alt, uint32_t min_percent, agpu_variant_stats* stats);
+/* ---- --indel-sites: the host side of agpu_indel_sites (include/arriba_gpu.h) -- the insertions and deletions of the CIGARs, left-normalised against the assembly, with their
+ * support and the depth at their anchor (the rule: DESIGN.md 4.22).  A row table is what agpu_indel_sites gives: agpu_indel_row, ordered by (ref, pos, type, length, bases) ----
+ *   ahost_indel_sites_of           arriba_amd/csrc/device/indel_core.hpp and allele_core.hpp stepped on the host over BAM records in host memory (the device's comparator; the CPU
+ *                                  tier).  input_header: the head of the input the records come from (a BAM header, or the '@' lines of SAM text): its references are looked up
+ *                                  among the contigs of the session by name (the events are normalised against its assembly), their LN bounds the positions.  min_mapq: at most
+ *                                  255; min_alt: 1 .. 2^31-1; min_percent: 0 .. 100.  ARRIBA_INDEL_MAX_SHIFT is read as the device reads it.  The rows are valid until the next
+ *                                  call on the thread
+ *   ahost_indel_sites_text         a row table and the names of the references (ahost_depth_contigs_of / _of_session) -> the text of the file:
+ *                                  "#CONTIG\tPOS\tREF\tTYPE\tLENGTH\tBASES\tSUPPORT\tDEPTH\n", then a line per row; BASES: the inserted bases, or the deleted bases of the assembly of
+ *                                  the session in upper case up to 64 of them, else "."; valid until the next call on the thread
+ *   ahost_indel_sites_write        that text into `path`, through path.tmp; on a failure nothing is left behind
+ *   ahost_indel_sites_file         all of it for a file (BAM in BGZF, gzip or raw; SAM text): what --host-ingest runs; stats may be NULL */
+int ahost_indel_sites_of(ahost_session* session, const void* input_header, size_t header_size, const void* records, size_t size, uint32_t min_mapq, uint32_t min_alt, uint32_t min_percent,
+                         const agpu_indel_row** rows, uint64_t* n_rows, agpu_indel_stats* stats /* may be NULL */);
+int ahost_indel_sites_text(ahost_session* session, const ahost_depth_contigs* contigs, const agpu_indel_row* rows, uint64_t n_rows, const char** text, uint64_t* bytes);
+int ahost_indel_sites_write(ahost_session* session, const ahost_depth_contigs* contigs, const agpu_indel_row* rows, uint64_t n_rows, const char* path);
+int ahost_indel_sites_file(ahost_session* session, const char* input_path, const char* path, uint32_t min_mapq, uint32_t min_alt, uint32_t min_percent, agpu_indel_stats* stats);
 /* ---- --realign-reads: the host side of agpu_realign_* (include/arriba_gpu.h) -- the records split into the templates to realign and the templates to keep, as SAM text (the
  * rule: DESIGN.md 4.18) ----
  *   ahost_realign_plan_of          what the split needs from the assembly of the session for the references of input_header (a BAM header, or the '@' lines of SAM text): a byte

@@ -115,6 +115,15 @@ typedef struct {
 	uint32_t variant_min_percent;         /* --variant-min-percent: ... and reported when that is at least this share of A + C + G + T; 0 .. 100; arriba_workflow_default_options sets 5 */
 	uint32_t variant_min_mapq;            /* --variant-min-mapq: records with a smaller MAPQ do not count; at most 255; arriba_workflow_default_options sets 20 */
 	uint32_t variant_min_baseq;           /* --variant-min-baseq: bases with a smaller quality go to LOWQ and are no evidence; at most 255; arriba_workflow_default_options sets 13 */
+	const char* indel_sites_file;         /* --indel-sites; NULL (and a zero-initialised struct) = none.  The insertions and deletions the records of chimeric_bam_file carry in their CIGARs, moved to
+	                                         the left as far as assembly_file allows, a line per distinct event behind a header line: CONTIG POS REF TYPE LENGTH BASES SUPPORT DEPTH, by
+	                                         reference in header order, anchor, deletions before insertions, length and bases -- the candidate indels of a variant caller, no genotypes --,
+	                                         found behind read_chimeric_alignments from the record stream in HBM (include/arriba_gpu.h: agpu_indel_sites; with host_ingest: the
+	                                         same code stepped on the host).  Of arriba_workflow_run's sample; the samples of a session say theirs with arriba_workflow_indel_sites.  Not for
+	                                         one sample over several ranks, not with separate_chimeric_file.  The three thresholds below without it are refused. */
+	uint32_t indel_min_alt;               /* --indel-min-alt: an event is a candidate when this many records carry it; 1 .. 2^31-1; arriba_workflow_default_options sets 3 */
+	uint32_t indel_min_percent;           /* --indel-min-percent: ... and reported when that is at least this share of the depth at its anchor; 0 .. 100; arriba_workflow_default_options sets 5 */
+	uint32_t indel_min_mapq;              /* --indel-min-mapq: records with a smaller MAPQ do not count; at most 255; arriba_workflow_default_options sets 20 */
 } arriba_workflow_options;
 
 /* what the reference prints as "(remaining=N)" / "(total=N)" / "(marked=N)", in the order of the stages; stage names as in the reference's source */
@@ -162,6 +171,7 @@ typedef struct { /* seconds of one sample, by part (wall clock of the calling th
 	double realign;          /* --realign-reads: name ids and claims, verdicts, scans, the windows of text, the copies, the files (inside `ingest`; beside the sample in front when the ingest was finished ahead) */
 	double rna_metrics;      /* --rna-metrics: the region track when it is built, the kernel, the copy, the file (inside `ingest`; beside the sample in front when the ingest was finished ahead) */
 	double variant_sites;    /* --variant-sites: the two event passes, sort and runs, the counters, the rows, the copy, the file (inside `ingest`; beside the sample in front when the ingest was finished ahead) */
+	double indel_sites;      /* --indel-sites: the two event passes with the scan between them, sort and runs, the counters, the rows, the copy, the file (inside `ingest`; beside the sample in front when the ingest was finished ahead) */
 } arriba_workflow_timing;
 /* options->chimeric_bam_file, output_file and discarded_output_file are not used by open (they belong to a sample); NULL + arriba_workflow_last_error() on failure */
 arriba_workflow_session* arriba_workflow_open(const arriba_workflow_options* options);
@@ -208,6 +218,9 @@ int arriba_workflow_rna_metrics(arriba_workflow_session* session, const char* pa
 /* --variant-sites, --variant-min-mapq, --variant-min-baseq, --variant-min-alt and --variant-min-percent of the sample that is submitted NEXT, in the same way; path NULL: none.  The
  * table is written by the thread that finishes its ingest. */
 int arriba_workflow_variant_sites(arriba_workflow_session* session, const char* path, uint32_t min_mapq, uint32_t min_baseq, uint32_t min_alt, uint32_t min_percent);
+/* --indel-sites, --indel-min-mapq, --indel-min-alt and --indel-min-percent of the sample that is submitted NEXT, in the same way; path NULL: none.  The table is written by the
+ * thread that finishes its ingest. */
+int arriba_workflow_indel_sites(arriba_workflow_session* session, const char* path, uint32_t min_mapq, uint32_t min_alt, uint32_t min_percent);
 /* (If the device runs out of memory while two samples are in flight, arriba_workflow_sample throws away what was fed ahead, closes the second lane, runs its sample again with the device
  * to itself and submits the other sample again behind it -- once; a sample that does not fit the device alone fails the call.  INTEGRATION.md, "Memory".) */
 /* on: arriba_workflow_sample returns when the last output file of the sample (-O if given, else -o) has everything it needs off the device; the file is formatted and written
