@@ -25,7 +25,14 @@ inline unsigned int grid_for(uint64_t n) { return (unsigned int) ((n + BLOCK - 1
 #define HIP_CHECK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { set_last_error(std::string(#call) + ": " + hipGetErrorString(e_)); return AGPU_ERR_DEVICE; } } while (0)
 #define ALLOC(buffer, bytes) do { if (!(buffer).allocate(bytes)) { set_last_error("hipMalloc failed (" #buffer ")"); return AGPU_ERR_NO_MEMORY; } } while (0)
 
-// sort keys of the candidate at position j of the current order, least significant criterion first (pass 0) to most significant (pass 3)
+// sort keys of the candidate at position j of the current order, least significant criteria first (pass 0) to most significant (pass 3).  Every criterion of
+// fusion_has_more_support goes into a key whole -- the supporting reads as the 32-bit sum the counters give (more support = smaller key), the breakpoints as the non-negative
+// 32-bit positions they are -- so the order is exact for every support a counter can hold:
+//   pass 0  gene1 << 32 | gene2                                     64 bits
+//   pass 1  breakpoint2 << 2 | direction1 << 1 | direction2         34 bits
+//   pass 2  contig1 << 48 | contig2 << 32 | breakpoint1             64 bits
+//   pass 3  ~supporting_reads << 2 | not_coding1 << 1 | not_coding2 34 bits
+// (SUPPORT_KEY_BITS below: the bits the sort of a pass looks at)
 __global__ void support_key_kernel(AnnotationView ann, CandidateTable t, const uint32_t* order, int pass, uint64_t* keys) {
 	uint32_t j = blockIdx.x * BLOCK + threadIdx.x;
 	if (j >= t.n) return;
@@ -33,15 +40,16 @@ __global__ void support_key_kernel(AnnotationView ann, CandidateTable t, const u
 	const uint32_t flags = t.flags[c];
 	uint64_t key;
 	if (pass == 0) key = (uint64_t) t.gene1[c] << 32 | t.gene2[c];
-	else if (pass == 1) key = ((flags & CFLAG_UPSTREAM1) ? 2u : 0u) | ((flags & CFLAG_UPSTREAM2) ? 1u : 0u);
-	else if (pass == 2) key = (uint64_t) (uint32_t) t.breakpoint1[c] << 32 | (uint32_t) t.breakpoint2[c];
+	else if (pass == 1) key = (uint64_t) (uint32_t) t.breakpoint2[c] << 2 | ((flags & CFLAG_UPSTREAM1) ? 2u : 0u) | ((flags & CFLAG_UPSTREAM2) ? 1u : 0u);
+	else if (pass == 2) key = (uint64_t) t.contigs[c] << 32 | (uint32_t) t.breakpoint1[c]; // contigs = contig1 << 16 | contig2
 	else {
-		const uint64_t supporting_reads = t.split_reads1[c] + t.split_reads2[c] + t.discordant_mates[c];
+		const uint32_t supporting_reads = t.split_reads1[c] + t.split_reads2[c] + t.discordant_mates[c];
 		const uint64_t not_coding1 = (ann.gene_bits[t.gene1[c]] & GBIT_PROTEIN_CODING) ? 0 : 1, not_coding2 = (ann.gene_bits[t.gene2[c]] & GBIT_PROTEIN_CODING) ? 0 : 1;
-		key = (0x1FFFFull - (supporting_reads < 0x1FFFFull ? supporting_reads : 0x1FFFFull)) << 34 | not_coding1 << 33 | not_coding2 << 32 | t.contigs[c]; // contigs = contig1 << 16 | contig2
+		key = (uint64_t) ~supporting_reads << 2 | not_coding1 << 1 | not_coding2;
 	}
 	keys[j] = key;
 }
+const int SUPPORT_KEY_BITS[4] = { 64, 34, 64, 34 };
 __global__ void rank_from_order_kernel(const uint32_t* order, uint32_t n, uint32_t* rank) {
 	uint32_t j = blockIdx.x * BLOCK + threadIdx.x;
 	if (j < n) rank[order[j]] = j;
@@ -196,20 +204,19 @@ int compute_support_rank(agpu_ctx* ctx, uint32_t* rank) {
 	ALLOC(keys_in, (size_t) C * 8); ALLOC(keys_out, (size_t) C * 8); ALLOC(order_a, (size_t) C * 4); ALLOC(order_b, (size_t) C * 4);
 	const CandidateTable& t = ctx->candidates;
 	uint32_t* order = nullptr; uint32_t* next = order_a.as<uint32_t>();
-	const int end_bits[4] = { 64, 2, 64, 51 };
 	for (int pass = 0; pass < 4; ++pass) {
 		support_key_kernel<<<grid_for(C), BLOCK, 0, s>>>(ctx->annotation, t, order, pass, keys_in.as<uint64_t>());
 		size_t bytes = 0;
 		if (order == nullptr) {
-			HIP_CHECK(rocprim::radix_sort_pairs(nullptr, bytes, keys_in.as<uint64_t>(), keys_out.as<uint64_t>(), rocprim::counting_iterator<uint32_t>(0), next, C, 0, end_bits[pass], s));
+			HIP_CHECK(rocprim::radix_sort_pairs(nullptr, bytes, keys_in.as<uint64_t>(), keys_out.as<uint64_t>(), rocprim::counting_iterator<uint32_t>(0), next, C, 0, SUPPORT_KEY_BITS[pass], s));
 			if (bytes > scratch.capacity) ALLOC(scratch, bytes);
 			KernelTimer timer(ctx, "rocprim::radix_sort_pairs(support rank)", (uint64_t) C * 24);
-			HIP_CHECK(rocprim::radix_sort_pairs(scratch.ptr, bytes, keys_in.as<uint64_t>(), keys_out.as<uint64_t>(), rocprim::counting_iterator<uint32_t>(0), next, C, 0, end_bits[pass], s));
+			HIP_CHECK(rocprim::radix_sort_pairs(scratch.ptr, bytes, keys_in.as<uint64_t>(), keys_out.as<uint64_t>(), rocprim::counting_iterator<uint32_t>(0), next, C, 0, SUPPORT_KEY_BITS[pass], s));
 		} else {
-			HIP_CHECK(rocprim::radix_sort_pairs(nullptr, bytes, keys_in.as<uint64_t>(), keys_out.as<uint64_t>(), order, next, C, 0, end_bits[pass], s));
+			HIP_CHECK(rocprim::radix_sort_pairs(nullptr, bytes, keys_in.as<uint64_t>(), keys_out.as<uint64_t>(), order, next, C, 0, SUPPORT_KEY_BITS[pass], s));
 			if (bytes > scratch.capacity) ALLOC(scratch, bytes);
 			KernelTimer timer(ctx, "rocprim::radix_sort_pairs(support rank)", (uint64_t) C * 24);
-			HIP_CHECK(rocprim::radix_sort_pairs(scratch.ptr, bytes, keys_in.as<uint64_t>(), keys_out.as<uint64_t>(), order, next, C, 0, end_bits[pass], s));
+			HIP_CHECK(rocprim::radix_sort_pairs(scratch.ptr, bytes, keys_in.as<uint64_t>(), keys_out.as<uint64_t>(), order, next, C, 0, SUPPORT_KEY_BITS[pass], s));
 		}
 		order = next;
 		next = (order == order_a.as<uint32_t>()) ? order_b.as<uint32_t>() : order_a.as<uint32_t>();

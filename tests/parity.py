@@ -22,6 +22,20 @@ def open_session(prefix):
     return session
 
 
+def implicit_lists(window_entries):
+    """context manager: the discordant-mate lists of the candidates implicit (fusion_core.hpp: CandidateTable::discordant_before), expanded in windows of so many entries"""
+    import contextlib
+    @contextlib.contextmanager
+    def manager():
+        os.environ["ARRIBA_IMPLICIT_LISTS"] = "1"
+        os.environ["ARRIBA_LIST_WINDOW_ENTRIES"] = str(window_entries)
+        try:
+            yield
+        finally:
+            del os.environ["ARRIBA_IMPLICIT_LISTS"], os.environ["ARRIBA_LIST_WINDOW_ENTRIES"]
+    return manager()
+
+
 def check_ingest(session, golden):
     """packed batch vs the reference's read table after annotation (ingest-time fields only)"""
     reads = golden_io.read_reads(golden_io.find_dump(golden, "reads", "annotated"))

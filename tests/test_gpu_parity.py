@@ -545,18 +545,7 @@ def test_workflow_from_input_files_to_output_files(built, dataset_files, tmp_pat
     assert stages[-1][1] > 300 and dict(stages)["mark_genomic_support"] > 10000
 
 
-def _with_implicit_lists(window_entries):
-    """context manager: the discordant-mate lists of the candidates implicit (fusion_core.hpp: CandidateTable::discordant_before), expanded in windows of so many entries"""
-    import contextlib
-    @contextlib.contextmanager
-    def manager():
-        os.environ["ARRIBA_IMPLICIT_LISTS"] = "1"
-        os.environ["ARRIBA_LIST_WINDOW_ENTRIES"] = str(window_entries)
-        try:
-            yield
-        finally:
-            del os.environ["ARRIBA_IMPLICIT_LISTS"], os.environ["ARRIBA_LIST_WINDOW_ENTRIES"]
-    return manager()
+_with_implicit_lists = parity.implicit_lists  # (shared with tests/test_multimapper_states.py)
 
 
 def test_kernels_of_a_wavefront_per_item_are_launched_in_chunks(built, dataset_files, tmp_path):
